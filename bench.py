@@ -17,17 +17,26 @@ With more than one rank the line ALWAYS carries the one exchange the path has --
 (sampling, then one blocking all-gather), `value_overlapped`, `collate_GBps`, and the RCCL rank count.  `--collate` does the same at one GPU
 (a one-rank communicator: the code path, not a transfer).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline figure needs: set up, warm up, time the N steps, write
+the outputs of the last step (--dump-outputs DIR), print the line.  Everything else below -- ESS/sec, counter traffic from rocprofv3
+child runs, the CPU baselines, the other configs, the extra legs and the scaling proxy -- runs with --full only.
+
+--dump-outputs DIR: after the timed steps, what the last step handed its caller, as DIR/<name>.npy (float64): the kept draws and
+final states of a fixed seeded sample of the chains (DUMP_CHAINS, fewer when the draws would pass DUMP_DRAW_BYTES), every chain's
+accept count, leapfrog counts (hmc, nuts) and adapted step size (nuts), and the ids of the sampled chains.  The inputs are seeded, so
+two builds run with the same arguments can be compared array for array.
+
+Prints ONE JSON line on rank 0 with two extra objects:
   roofline     -- the dominant kernel (named by the engine: mi_mcmc_last_kernel) against the resource that bounds it: algorithmic
                   flops per launch / HIP-event duration measured here on the launch stream; `traffic` = HBM bytes per
-                  launch, measured by two rocprofv3 --pmc child runs of this workload when rocprofv3 is on the box (--traffic),
-                  else from the committed passes of this exact workload (profiles/r*_c<N>_pmc.json), else null
-  other_configs-- (default run, one GPU) BASELINE configs 3, 4, 5 under the same clock at --other-steps steps, each with its roofline, its own
+                  launch, measured by two rocprofv3 --pmc child runs of this workload when rocprofv3 is on the box (--traffic, with
+                  --full by default), else from the committed passes of this exact workload (profiles/r*_c<N>_pmc.json), else null
+  other_configs-- (--full run, one GPU) BASELINE configs 3, 4, 5 under the same clock at --other-steps steps, each with its roofline, its own
                   cpu_baseline and -- where BASELINE's frozen settings do not converge (configs[2], configs[4]) -- a `converged` leg outside the
                   timed region that makes ESS/sec an estimate (CONVERGED below, frozen in BASELINE.md section 9)
-  scaling_proxy-- (default run, one GPU) the share of one GPU at N = 1, 2, 4, 8 (chains_total / N) of configs[1] and configs[3], timed here:
+  scaling_proxy-- (--full run, one GPU) the share of one GPU at N = 1, 2, 4, 8 (chains_total / N) of configs[1] and configs[3], timed here:
                   a one-GPU PROXY of north_star's strong-scaling curve, labelled as such
-  cpu_baseline -- the CPU oracle (oracle/, a port of the reference algorithm) timed on this box's host cores on a
+  cpu_baseline -- (--full run) the CPU oracle (oracle/, a port of the reference algorithm) timed on this box's host cores on a
                   bounded sample of the same workload: Mode A (reference-faithful work profile) and Mode B
                   (optimised CPU: same bits, gradient reuse, no identity mat-vecs, SIMD mat-vec), built with the
                   reference's own flags (-O3 -march=native -ffp-contract=fast -fopenmp, ref: configure:196-214).
@@ -521,6 +530,37 @@ def time_collation(args, ctx, cfg, algo, target, skw, theta, theta0, draws, chai
     return out
 
 
+DUMP_SEED = 20240601             # --dump-outputs: which chains are sampled (fixed, so that two runs dump the same chains)
+DUMP_CHAINS = 256                # chains whose draws and final states are written
+DUMP_DRAW_BYTES = 32 << 20       # cap on the sampled draws (d = 512 x 100 kept draws: 81 chains)
+DUMP_FULL_CHAINS = 1 << 19       # per-chain counts of every chain up to this many (4 MiB each), of the sampled chains beyond
+
+
+def dump_outputs(path, algo, C, chain0, d, n_keep, theta, draws, n_accept, n_leap, n_exec, eps_out):
+    """--dump-outputs: the outputs of the last timed step of this rank (module docstring) as float64 DIR/<name>.npy; under 64 MB in all."""
+    import torch
+    k = min(C, DUMP_CHAINS, max(1, DUMP_DRAW_BYTES // max(1, n_keep * d * 8)))
+    ids = np.arange(C) if k == C else np.sort(np.random.default_rng(DUMP_SEED).choice(C, k, replace=False))
+    idx = torch.from_numpy(ids).to(draws.device)
+
+    def per_chain(v):
+        return v[:C] if C <= DUMP_FULL_CHAINS else v[:C].index_select(0, idx)
+
+    out = {"chain_ids": chain0 + ids, "draws": draws[:, :, :C].index_select(2, idx), "theta": theta[:, :C].index_select(1, idx),
+           "n_accept": per_chain(n_accept)}
+    if algo != "mala":
+        out["n_leapfrogs"], out["n_leapfrogs_executed"] = per_chain(n_leap), per_chain(n_exec)
+    if algo == "nuts":
+        out["step_size"] = per_chain(eps_out)
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in out.items():
+        a = np.ascontiguousarray(a.double().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64_000_000, total
+
+
 def measure(cfg_id, steps, warmup, args, ctx, headline, chains_override=None, want_traffic=True):
     """Times `steps` steps of one BASELINE config on this rank's GPU (barrier + synchronize on both sides, max over ranks).
     Returns the result dict on rank 0 (None elsewhere)."""
@@ -586,6 +626,8 @@ def measure(cfg_id, steps, warmup, args, ctx, headline, chains_override=None, wa
     elapsed = time.perf_counter() - t0
     kernel_ms = [a.elapsed_time(b) for a, b in events]
     kernel_name = mcmc_amd.last_kernel() if C > 0 else cfg["kernel"]   # what the engine actually launched (mi_mcmc_last_kernel)
+    if headline and args.dump_outputs and rank == 0 and C > 0:          # before anything below reuses the buffers
+        dump_outputs(args.dump_outputs, algo, C, chain0, d, n_keep, theta, draws, n_accept, n_leap, n_exec, eps_out)
 
     # units of this rank per step: EXECUTED leapfrog steps x dims (hmc, nuts) or draws x dims (mala).  nuts on the memoised kernel
     # (nuts_memo.hpp) computes every distinct state of a doubling once: it executes fewer leapfrogs than mcmc::nuts does for the same draws --
@@ -749,8 +791,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: ESS/sec, rocprofv3 traffic, CPU baselines and, without --config, the other "
+                         "configs, the extra legs and the scaling proxy (the --no-* options below leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step of the headline config to DIR/<name>.npy (float64)")
     ap.add_argument("--config", type=int, default=None, choices=sorted(WORKLOADS),
-                    help="one BASELINE config only; default: the headline (2) with --steps/--warmup, then configs 3, 4, 5 at "
+                    help="one BASELINE config only; default: the headline (2) with --steps/--warmup, then (--full) configs 3, 4, 5 at "
                          "--other-steps (one GPU only), attached as other_configs")
     ap.add_argument("--other-steps", type=int, default=2)
     ap.add_argument("--other-warmup", type=int, default=1)
@@ -759,16 +806,23 @@ def main():
     ap.add_argument("--chains", type=int, default=None, help="chains: total (strong) / per GPU (weak)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ess", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra (non-BASELINE) measurements of the default run")
-    ap.add_argument("--traffic", choices=["headline", "all", "none"], default="all",
+    ap.add_argument("--no-extra", action="store_true", help="skip the extra (non-BASELINE) measurements of the --full run")
+    ap.add_argument("--traffic", choices=["headline", "all", "none"], default=None,
                     help="measure roofline.traffic with two rocprofv3 --pmc child runs per config (one GPU only); headline: only the headline "
-                         "config that way, the others from the committed profiles/ of the same kernel; none: committed profiles only")
+                         "config that way, the others from the committed profiles/ of the same kernel; none: committed profiles only. "
+                         "Default: all with --full, none without")
     ap.add_argument("--proxy-scaling", action="store_true", help="with --config N: also time chains/2, /4, /8 on this GPU (scaling_proxy)")
-    ap.add_argument("--no-proxy", action="store_true", help="skip scaling_proxy in the default run")
-    ap.add_argument("--converged", action="store_true", help="with --config 3 | 5: also run that config's converged ESS leg (the default run always does)")
+    ap.add_argument("--no-proxy", action="store_true", help="skip scaling_proxy in the --full run")
+    ap.add_argument("--converged", action="store_true", help="with --config 3 | 5: also run that config's converged ESS leg (a --full run without --config always does)")
     ap.add_argument("--collate", action="store_true",
                     help="one GPU: run the C-ABI collation over a one-rank RCCL communicator too (with N > 1 ranks it always runs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.traffic is None:
+        args.traffic = "all" if args.full else "none"
+    if not args.full:           # a plain run: the headline figure only (module docstring)
+        args.no_cpu_baseline = args.no_ess = True
 
     import torch
 
@@ -833,7 +887,7 @@ def main():
     out, cfg = measure(head_id, args.steps, args.warmup, args, ctx, headline=True)
     if ctx.rank == 0:
         out["ranks"] = {"world_size": ranks_seen, "backend": backend, "devices_visible": n_vis}
-    single = args.config is None and ctx.world == 1 and args.chains is None
+    single = args.full and args.config is None and ctx.world == 1 and args.chains is None
     if single:
         # the other single-GPU BASELINE configs under the same clock, at a reduced step count
         others = []

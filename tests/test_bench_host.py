@@ -45,3 +45,27 @@ def test_gpus_flag_must_match_the_launcher():
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--steps", "1", "--warmup", "0"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """--dump-outputs: the same seeded chains every time, draws capped (d = 512 x 100 kept draws: 81 chains), every chain's counts,
+    everything float64 and under 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    C, d, n_keep, chain0 = 3000, 512, 100, 7
+    draws = torch.arange(n_keep * d * C, dtype=torch.float64).view(n_keep, d, C)
+    theta = -torch.arange(d * C, dtype=torch.float64).view(d, C)
+    n_acc, n_leap, n_exec = (torch.arange(C, dtype=torch.int64) + k for k in (1, 2, 3))
+    eps = torch.linspace(0.1, 0.2, C, dtype=torch.float64)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), "nuts", C, chain0, d, n_keep, theta, draws, n_acc, n_leap, n_exec, eps)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["chain_ids", "draws", "n_accept", "n_leapfrogs", "n_leapfrogs_executed", "step_size", "theta"]
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64_000_000
+    ids = got["chain_ids"].astype(np.int64) - chain0
+    assert len(ids) == 81 and (np.diff(ids) > 0).all() and ids.max() < C
+    assert np.array_equal(got["draws"], draws.numpy()[:, :, ids]) and np.array_equal(got["theta"], theta.numpy()[:, ids])
+    assert np.array_equal(got["n_leapfrogs_executed"], n_exec.numpy()) and np.array_equal(got["step_size"], eps.numpy())
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name

@@ -17,8 +17,8 @@ def _line(out):
 
 
 def test_single_gpu_line():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--chains", "8192", "--no-cpu-baseline", "--traffic", "none"],
-                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--chains", "8192", "--no-cpu-baseline",
+                          "--traffic", "none"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _line(out.stdout)
     assert KEYS <= set(j) and j["n_gpus"] == 1 and j["steps"] == 2 and j["vs_baseline"] is None and j["dtype"] == "f64"
@@ -28,11 +28,33 @@ def test_single_gpu_line():
     assert "ess_per_sec" in j and j["ess_per_sec_incl_reducer"] < j["ess_per_sec"]
 
 
+def test_plain_line_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline figure alone; --dump-outputs writes what the last timed step computed, and the same arrays
+    whatever the step count (seeded inputs, every step starts from them)."""
+    import numpy as np
+    for steps in (1, 2):
+        out = subprocess.run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "0", "--chains", "4096",
+                              "--dump-outputs", str(tmp_path / f"s{steps}")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        j = _line(out.stdout)
+        assert KEYS <= set(j) and j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0
+        assert not {"ess_per_sec", "cpu_baseline", "other_configs", "extra", "scaling_proxy"} & set(j), sorted(j)
+    names = sorted(p.name for p in (tmp_path / "s1").iterdir())
+    assert names == ["chain_ids.npy", "draws.npy", "n_accept.npy", "n_leapfrogs.npy", "n_leapfrogs_executed.npy", "theta.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "s1" / n), np.load(tmp_path / "s2" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    dr = np.load(tmp_path / "s1" / "draws.npy")
+    assert dr.shape == (100, 128, 256) and np.isfinite(dr).all()
+    assert np.load(tmp_path / "s1" / "n_accept.npy").shape == (4096,)
+    assert (np.load(tmp_path / "s1" / "n_leapfrogs_executed.npy") == 200 * 16).all()
+
+
 def test_traffic_is_measured_by_rocprofv3_child_runs():
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("no rocprofv3 on this box")
-    out = subprocess.run([sys.executable, "bench.py", "--config", "5", "--steps", "1", "--warmup", "0", "--chains", "4096",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--config", "5", "--steps", "1", "--warmup", "0", "--chains", "4096",
                           "--no-cpu-baseline", "--no-ess", "--traffic", "all"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _line(out.stdout)["roofline"]
