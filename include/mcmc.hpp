@@ -515,6 +515,64 @@ rwmh_impl(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals
     return ok;
 }
 
+// mcmc::de (ref: src/de.cpp:28-232): draws_out (n_pop, d, n_keep), draws_out.mat(k) the population after generation n_burnin + k.  The device
+// tag (mi355x::device_value_kernel with a mi355x::target_t) runs target_t::n_chains populations in one launch (draws_out (n_pop, d * n_chains,
+// n_keep), population c in columns c d .. c d + d - 1; initial_vals d or d * n_chains values); any other callback runs one population with the
+// callback on the host (mi_mcmc_de_run_callback).  n_accept_draws: the first population's accepts (all of them in target_t::n_accept_draws).
+inline bool
+de_impl(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel, Cube_t& draws_out,
+        void* target_data, algo_settings_t* settings_inp)
+{
+    algo_settings_t settings;
+    if (settings_inp) settings = *settings_inp;
+    const de_settings_t& ds = settings.de_settings;
+    mi_settings m = flatten_common(settings);
+    m.n_burnin_draws = ds.n_burnin_draws;
+    m.n_keep_draws = ds.n_keep_draws;
+    const size_t n_init = size_t(initial_vals.size());
+    const bool device = mi355x::is_device_route(target_log_kernel);
+    const size_t d = device ? size_t(static_cast<mi355x::target_t*>(target_data)->desc.d) : n_init;
+    mi_de_settings de; mi_de_settings_default(&de);
+    de.jumps = ds.jumps ? 1 : 0; de.n_pop = ds.n_pop; de.par_b = ds.par_b; de.par_gamma_jump = ds.par_gamma_jump; de.par_gamma = ds.par_gamma;
+    de.initial_lb = (size_t(ds.initial_lb.size()) == d) ? ds.initial_lb.data() : nullptr;      // de.cpp:65-66: only a table of size d counts
+    de.initial_ub = (size_t(ds.initial_ub.size()) == d) ? ds.initial_ub.data() : nullptr;
+    const size_t n_pop = ds.n_pop, n_keep = ds.n_keep_draws;
+    size_t C = 1;
+    std::vector<double> draws;
+    uint64_t n_accept = 0;
+    bool ok;
+    if (device) {
+        mi355x::target_t& tgt = *static_cast<mi355x::target_t*>(target_data);
+        C = tgt.n_chains ? tgt.n_chains : 1;
+        if (d == 0 || (n_init != d && n_init != d * C)) { tgt.last_error = "initial_vals must hold d or d*n_chains values"; return false; }
+        std::vector<double> init(d * C), pop(n_pop * d * C);
+        for (size_t c = 0; c < C; ++c)
+            for (size_t j = 0; j < d; ++j) init[j * C + c] = initial_vals(n_init == d ? j : c * d + j);
+        draws.assign(n_keep * n_pop * d * C, 0.0);
+        tgt.n_accept_draws.assign(C, 0);
+        mi_populations p{};
+        p.struct_size = sizeof p; p.mem = MI_MEM_HOST; p.n_populations = C; p.population0 = tgt.chain0;
+        p.initial_vals = init.data(); p.population = pop.data(); p.draws = draws.data(); p.n_accept = tgt.n_accept_draws.data();
+        tgt.desc.struct_size = sizeof(mi_target);
+        ok = mi_mcmc_de_run(&tgt.desc, &m, &de, &p, nullptr) == MI_OK;
+        if (!ok) tgt.last_error = mi_mcmc_last_error();
+        else n_accept = tgt.n_accept_draws[0];
+    } else {
+        draws.assign(n_keep * n_pop * d, 0.0);
+        value_callback_ctx ctx{&target_log_kernel, target_data, d};
+        ok = mi_mcmc_de_run_callback(initial_vals.data(), d, &value_callback_trampoline, &ctx, &m, &de, draws.data(), &n_accept) == MI_OK;
+        if (!ok) mi355x::last_error() = mi_mcmc_last_error();
+    }
+    if (!ok) return false;
+    draws_out.setZero(n_pop, d * C, n_keep);                          // draws_out.setZero(n_pop, n_vals, n_keep_draws), de.cpp:150
+    for (size_t k = 0; k < n_keep; ++k)
+        for (size_t i = 0; i < n_pop; ++i)
+            for (size_t j = 0; j < d; ++j)
+                for (size_t c = 0; c < C; ++c) draws_out.mat(k)(i, c * d + j) = draws[((k * n_pop + i) * d + j) * C + c];
+    if (settings_inp) settings_inp->de_settings.n_accept_draws = size_t(n_accept);         // de.cpp:226-228
+    return true;
+}
+
 struct tensor_callback_ctx { const tensor_fn_t* fn; void* user; size_t d; };
 
 // tensor_fn(vals_inp, tensor_deriv_out, tensor_data) -> d*d row-major tensor and, when asked for, the d matrices dG/dvals_i
@@ -612,6 +670,14 @@ inline bool rwmh(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_
 inline bool rwmh(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
                  Mat_t& draws_out, void* target_data, algo_settings_t& settings)
 { return internal::rwmh_impl(initial_vals, target_log_kernel, draws_out, target_data, &settings); }
+
+// mcmc::de (ref: include/mcmc/de.hpp): differential-evolution MCMC over a population of settings.de_settings.n_pop members
+inline bool de(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
+               Cube_t& draws_out, void* target_data)
+{ return internal::de_impl(initial_vals, target_log_kernel, draws_out, target_data, nullptr); }
+inline bool de(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
+               Cube_t& draws_out, void* target_data, algo_settings_t& settings)
+{ return internal::de_impl(initial_vals, target_log_kernel, draws_out, target_data, &settings); }
 
 // NOT in the reference: mcmc::hmc on the device route with the DIAGONAL mass matrix adapted during burn-in -- pooled over the chains
 // (one matrix for all, estimated from their spread; mass_out: d values) or per chain (each chain from its own draws, Stan's scheme;

@@ -91,7 +91,8 @@ typedef enum mi_kernel_hint {
                                             * cannot honour): the default kernel runs */
     MI_KERNEL_LITERAL = 12,                /* nuts (and hmc with bounds / a diagonal precond_mat; hmc, mala and nuts with a DENSE precond_mat) on the logistic target
                                             * (d <= 512) and on dense Gaussians with 128 < d <= 512: the literal kernel (one workgroup per chain) instead of the tiled kernel on the
-                                            * LDS-streamed evaluation -- same bits, for A/B timing */
+                                            * LDS-streamed evaluation -- same bits, for A/B timing.  mi_mcmc_de_run: de_literal_kernel (one workgroup per
+                                            * population) instead of de_gauss_mfma_kernel on the Gaussians with d <= 128 -- same bits */
     MI_KERNEL_NUTS_DYN = 13,               /* RETIRED (round 5), valid and ignored: round 4's register-carried tick with dynamic chain hand-out */
     MI_KERNEL_NUTS_MEMO = 14,              /* nuts, same case: every doubling on a MEMOISED trajectory (nuts_memo.hpp) -- the 2^j leaves of a doubling visit only
                                             * 1 + j (j + 1) / 2 distinct states (the reference's crossed edge plumbing, nuts.ipp:195,207), each is computed
@@ -300,6 +301,61 @@ typedef void (*mi_tensor_cb)(const double* vals_inp, double* tensor_out, double*
 int mi_mcmc_rmhmc_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
                                mi_tensor_cb tensor_fn, void* tensor_data, const mi_settings* settings, double* draws_out,
                                uint64_t* n_accept_draws);
+
+/* ---- mcmc::de (ref: include/mcmc/de.hpp, src/de.cpp:28-232): differential-evolution MCMC, MANY populations per call.
+ *
+ * Each population is one call of mcmc::de: n_pop members of d values.  The initial population is lb + (ub - lb) * u per member
+ * (lb / ub: de.initial_lb / initial_ub, or initial_vals -/+ 0.5; with vals_bound clamped to the hard bounds), used as it is in the
+ * SAMPLER's space as the reference does (the target sees inv_transform of it).  gamma = 2.38 / sqrt(2 d) (the reference ignores
+ * par_gamma); with jumps, generation g (global, burn-in included) uses par_gamma_jump when (g + 1) % 10 == 0.  A generation sweeps the
+ * members i = 0 .. n_pop-1 IN ORDER and IN PLACE: X_prop = (X_i + (X_c1 - X_c2) gamma) + r, r_k = -b + (b + b) u_k; accept iff
+ * prop - tv_i > log(z) (a NaN difference rejects); later members read the updated rows.  This is the reference run with
+ * omp_n_threads = 1, its only deterministic reading.  settings: rng_seed_value, vals_bound / bounds, n_burnin_draws / n_keep_draws
+ * (de_settings_t's counts); nothing else of mi_settings is read.
+ *
+ * RNG contract (counter-based Philox; the reference's per-thread std:: engines are not reproducible): rng_block(seed, pop, gen, slot,
+ * tag) with pop the GLOBAL population (population0 + p), gen the GLOBAL generation (draw0 + local), slot = member * B + blk,
+ * B = 1 + ceil(d / 2), tag 4 (tag 3 with gen = 0 for the initial population).  Block 0 (w0..w3) of a generation:
+ *   c1 = (w0 * (n_pop - 1)) >> 32, c1 += (c1 >= i);
+ *   c2 = (w1 * (n_pop - 2)) >> 32, c2 += (c2 >= min(i, c1)), then c2 += (c2 >= max(i, c1));
+ *   z  = u01(w2, w3)     (u01(lo, hi) = (2 k + 1) 2^-53, k = the top 52 bits of hi:lo)
+ * Blocks 1 .. ceil(d/2): dimension 2 (blk - 1) from u01(w0, w1), dimension 2 (blk - 1) + 1 from u01(w2, w3) -- the u of r above, and of
+ * the initial population (tag 3).  n_pop * B must stay below 2^32 (MI_ERR_UNSUPPORTED). */
+typedef struct mi_de_settings {
+    uint32_t struct_size;
+    int32_t  jumps;               /* de_settings_t::jumps, default false */
+    uint64_t n_pop;               /* default 100; >= 3 (the reference loops forever below) */
+    double   par_b;               /* default 1e-4 */
+    double   par_gamma_jump;      /* default 2.0 */
+    double   par_gamma;           /* default 1.0: carried, not read (the reference computes 2.38 / sqrt(2 d), src/de.cpp:61-62) */
+    const double* initial_lb;     /* d host values or NULL (initial_vals - 0.5) */
+    const double* initial_ub;     /* d host values or NULL (initial_vals + 0.5) */
+} mi_de_settings;
+
+/* P populations; all pointers in `mem`.  Layouts population-index contiguous, like mi_chains. */
+typedef struct mi_populations {
+    uint32_t  struct_size;
+    int32_t   mem;
+    uint64_t  n_populations;      /* P */
+    uint64_t  population0;        /* global id of local population 0 (the Philox counter uses it: sharding does not change the bits) */
+    const double* initial_vals;   /* [d][P]; read when draw0 == 0 and no initial box is given (may be NULL otherwise) */
+    double*   population;         /* [n_pop][d][P] out: the last population in the sampler's (transformed) space; IN when draw0 > 0 */
+    double*   draws;              /* [n_keep][n_pop][d][P] out (inverse-transformed when bounded), may be NULL */
+    uint64_t* n_accept;           /* [P] out: accepts of the kept generations, summed over the members, may be NULL */
+    uint64_t  draw0;              /* global index of this call's first generation: 0 for a fresh run; the generations of the calls
+                                   * before to CONTINUE from `population` -- the concatenation is bit-identical to one long run */
+} mi_populations;
+
+void mi_de_settings_default(mi_de_settings* s);
+/* Dispatch: iso / diag / dense Gaussians with d <= 128 (with or without bounds) on de_gauss_mfma_kernel (16 populations per wave, one
+ * per column of the MFMA tile); every other kind target_eval knows (dense d > 128, logistic) on de_literal_kernel (one workgroup per
+ * population), which MI_KERNEL_LITERAL also selects -- same bits.  MI_TARGET_NORMAL_MODEL: MI_ERR_UNSUPPORTED. */
+int mi_mcmc_de_run(const mi_target* target, const mi_settings* settings, const mi_de_settings* de, mi_populations* pops, void* stream);
+/* The reference's own contract, one population: target_log_kernel asked for the value only (grad_out NULL) once per member at setup and
+ * once per proposal, served on the calling thread while de_literal_kernel runs (see mi_mcmc_rmhmc_run_callback).  initial_vals: d
+ * values; draws_out: [n_keep][n_pop][d], may be NULL when n_keep == 0; n_accept: may be NULL.  Blocking. */
+int mi_mcmc_de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
+                            const mi_settings* settings, const mi_de_settings* de, double* draws_out, uint64_t* n_accept);
 
 /* ---- the BaseMatrixOps shim's INV and CHOL_LOWER as the engine computes them for a dense precond_mat (ref: src/hmc.cpp:58-59,
  * src/mala.cpp:58, include/stats/dmvnorm.hpp:36-41 through include/mcmc/mala.ipp:63-64): Gauss-Jordan with partial pivoting (first largest

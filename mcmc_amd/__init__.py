@@ -52,6 +52,17 @@ class mi_chains(C.Structure):
                 ("n_leapfrogs_executed", C.c_void_p)]
 
 
+class mi_de_settings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("jumps", C.c_int32), ("n_pop", C.c_uint64), ("par_b", C.c_double),
+                ("par_gamma_jump", C.c_double), ("par_gamma", C.c_double), ("initial_lb", C.c_void_p), ("initial_ub", C.c_void_p)]
+
+
+class mi_populations(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mem", C.c_int32), ("n_populations", C.c_uint64), ("population0", C.c_uint64),
+                ("initial_vals", C.c_void_p), ("population", C.c_void_p), ("draws", C.c_void_p), ("n_accept", C.c_void_p),
+                ("draw0", C.c_uint64)]
+
+
 class MiMcmcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mi_mcmc status {code}: {msg}")
@@ -63,6 +74,7 @@ _lib = None
 EXPORTS = [
     "mi_settings_default", "mi_mcmc_last_error", "mi_mcmc_last_kernel", "mi_mcmc_version", "mi_mcmc_device_count", "mi_mcmc_release_workspace", "mi_mcmc_run_user_target", "mi_mcmc_run_user_target_v", "mi_mcmc_run_tile_target",
     "mi_mcmc_hmc_run", "mi_mcmc_mala_run", "mi_mcmc_nuts_run", "mi_mcmc_rwmh_run", "mi_mcmc_rmhmc_run", "mi_mcmc_hmc_run_mass_adapted", "mi_mcmc_hmc_run_mass_adapted_per_chain", "mi_mcmc_hmc_run_callback", "mi_mcmc_mala_run_callback", "mi_mcmc_nuts_run_callback", "mi_mcmc_rwmh_run_callback", "mi_mcmc_rmhmc_run_callback",
+    "mi_de_settings_default", "mi_mcmc_de_run", "mi_mcmc_de_run_callback",
     "mi_mcmc_draws_to_chain_major", "mi_mcmc_draws_to_chain_major_device", "mi_mcmc_shard_bounds", "mi_mcmc_allgather_draws", "mi_mcmc_allgather_draws_ragged", "mi_mcmc_merge_shards", "mi_mcmc_draw_stats",
     "mi_mcmc_allgather_draws_rank_major", "mi_mcmc_rank_major_index", "mi_mcmc_allgather_draws_begin", "mi_mcmc_allgather_draws_wait",
     "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
@@ -369,6 +381,69 @@ def nuts_callback(initial_vals, callback, settings, target_data=None):
 def rwmh_callback(initial_vals, callback, settings, target_data=None):
     """settings.step_size carries par_scale; the callback is asked for the value only"""
     return hmc_callback(initial_vals, callback, settings, target_data, algo="rwmh")
+
+
+def de_settings(**kw):
+    """de_settings_t with the reference defaults (jumps false, n_pop 100, par_b 1e-4, par_gamma_jump 2), then keyword overrides;
+    initial_lb / initial_ub: d values (the initial box of every population) or None."""
+    s = mi_de_settings()
+    lib().mi_de_settings_default(C.byref(s))
+    keep = []
+    for k, v in kw.items():
+        if k in ("initial_lb", "initial_ub"):
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=np.float64)
+                keep.append(v)
+                v = v.ctypes.data
+        setattr(s, k, v)
+    s._keep = keep
+    return s
+
+
+def de(kind, init, settings, de_settings=None, n_pop=None, prec=None, X=None, y=None, population0=0, draw0=0, population=None,
+       want_draws=True, kernel_hint=KERNEL_AUTO):
+    """mcmc::de for P populations at once (mi_mcmc_de_run), host buffers.  init: [P, d] (initial_vals of every population);
+    settings: rng_seed_value, bounds, n_burnin_draws / n_keep_draws; de_settings: mi_de_settings (n_pop overrides its n_pop).
+    population: [n_pop, d, P] to continue a run (draw0 > 0).  Returns draws [n_keep, n_pop, d, P] (or None) and a dict with the
+    final population [n_pop, d, P] (transformed space) and n_accept [P]."""
+    ds = de_settings if de_settings is not None else globals()["de_settings"]()
+    if n_pop is not None:
+        ds.n_pop = int(n_pop)
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    P, d = init.shape
+    iv = np.ascontiguousarray(init.T)                                    # [d][P]
+    npop, n_keep = int(ds.n_pop), int(settings.n_keep_draws)
+    pop = np.zeros((npop, d, P)) if population is None else np.array(population, dtype=np.float64, order="C", copy=True)
+    draws = np.zeros((n_keep, npop, d, P)) if want_draws else None
+    n_accept = np.zeros(P, dtype=np.uint64)
+    t = make_target(kind, d, prec=prec, X=X, y=y, kernel_hint=kernel_hint)
+    p = mi_populations()
+    p.struct_size = C.sizeof(mi_populations)
+    p.mem, p.n_populations, p.population0, p.draw0 = MEM_HOST, P, int(population0), int(draw0)
+    p.initial_vals, p.population, p.draws, p.n_accept = _ptr(iv), _ptr(pop), _ptr(draws), _ptr(n_accept)
+    _check(lib().mi_mcmc_de_run(C.byref(t), C.byref(settings), C.byref(ds), C.byref(p), C.c_void_p(0)))
+    return draws, dict(population=pop, n_accept=n_accept)
+
+
+def de_callback(initial_vals, callback, settings, de_settings=None, n_pop=None, target_data=None):
+    """mcmc::de with a host callback for one population (mi_mcmc_de_run_callback).  callback: a ctypes mi_log_kernel_cb or a
+    Python callable f(vals: np.ndarray) -> value.  Returns draws [n_keep, n_pop, d] and n_accept."""
+    ds = de_settings if de_settings is not None else globals()["de_settings"]()
+    if n_pop is not None:
+        ds.n_pop = int(n_pop)
+    x0 = np.ascontiguousarray(initial_vals, dtype=np.float64)
+    d = x0.size
+    draws = np.zeros((int(settings.n_keep_draws), int(ds.n_pop), d))
+    n_acc = C.c_uint64(0)
+    if callable(callback) and not isinstance(callback, C._CFuncPtr):
+        def _tramp(vals, _grad, _user):
+            return float(callback(np.ctypeslib.as_array(vals, shape=(d,)).copy()))
+        cb = LOG_KERNEL_CB(_tramp)
+    else:
+        cb = callback
+    _check(lib().mi_mcmc_de_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
+                                         C.byref(settings), C.byref(ds), C.c_void_p(draws.ctypes.data), C.byref(n_acc)))
+    return draws, int(n_acc.value)
 
 
 # ---------------------------------------------------------------- diagnostics (GPU tests)

@@ -14,6 +14,7 @@ struct MalaParams;
 struct NutsParams;
 struct RwmhParams;
 struct SmallParams;
+struct DeParams;
 namespace lit { struct LitParams; }
 
 // nt = ceil(d / 16) in {1, 2, 3..4, 5..8}; general: bounds and / or diagonal precond; dense_m: dense precond (nt <= 4)
@@ -57,5 +58,10 @@ int launch_small_logistic(int algo, int d, const SmallParams& prm, const double*
 
 // literal.hpp: replay of flagged chains, or (prm.flag == nullptr) the run itself; algo 0 hmc, 1 mala, 2 nuts, 3 rwmh; n_wg workgroups of 256 threads
 int launch_literal(int algo, const lit::LitParams& prm, unsigned n_wg, hipStream_t st);
+
+// de.hpp (de_launch.hip): mcmc::de on iso / diag / dense Gaussians with d <= 128 (general: settings.vals_bound), 64 populations per
+// workgroup; and on the literal kernel, one workgroup of 256 threads per population (n_wg workgroups, every target kind)
+int launch_de_gauss(const DeParams& prm, int nt, bool general, hipStream_t st);
+int launch_de_literal(const DeParams& prm, unsigned n_wg, hipStream_t st);
 
 }  // namespace mi

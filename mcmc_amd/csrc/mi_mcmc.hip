@@ -29,6 +29,8 @@
 #include "nuts_async.hpp"
 #include "mala_dense.hpp"
 #include "rwmh_dense.hpp"
+#define MI_DE_PARAMS_ONLY
+#include "de.hpp"
 #include "hmc_diag.hpp"
 #include "logistic_launch.hpp"
 #include "launchers.hpp"
@@ -623,6 +625,50 @@ void lit_set_chain_mass(mi::lit::LitParams& lp, const double* mass_dev, const Ch
     lp.precond = 1; lp.m = mass_dev; lp.m_sqrt = t.ms.as<double>(); lp.m_inv = t.mi.as<double>(); lp.m_chain_stride = C;
 }
 
+// the target of a literal kernel (literal.hpp: LitTarget) in device memory: a host-memory target is staged into a / b, a matrix the literal
+// kernels read transposed into t_t.  The buffers must outlive the launch.
+int lit_stage_target(const char* who, const mi_target* target, mi::lit::LitTarget& t, DevBuf& t_a, DevBuf& t_b, DevBuf& t_t, hipStream_t st)
+{
+    const uint64_t d = target->d;
+    t.d = (uint32_t)d;
+    auto up = [&](DevBuf& b, const double* src, size_t n_doubles, const double** out) -> int {
+        if (target->mem == MI_MEM_DEVICE) { *out = src; return MI_OK; }
+        HIP_TRY(b.alloc(n_doubles * 8));
+        HIP_TRY(hipMemcpy(b.p, src, n_doubles * 8, hipMemcpyHostToDevice));
+        *out = b.as<double>();
+        return MI_OK;
+    };
+    int rc;
+    switch (target->kind) {
+    case MI_TARGET_GAUSS_ISO: t.kind = mi::lit::LIT_ISO; break;
+    case MI_TARGET_GAUSS_DIAG:
+        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DIAG needs prec (d)");
+        t.kind = mi::lit::LIT_DIAG; t.prec_stride = 1;
+        if ((rc = up(t_a, target->prec, d, &t.prec))) return rc;
+        break;
+    case MI_TARGET_GAUSS_DENSE:
+        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DENSE needs prec (d*d)");
+        t.kind = mi::lit::LIT_DENSE;
+        if ((rc = up(t_a, target->prec, d * d, &t.prec))) return rc;
+        HIP_TRY(t_t.alloc(d * d * 8));                     // ... read transposed by the literal kernels
+        if ((rc = transpose_on_device(t.prec, t_t.as<double>(), (uint32_t)d, (uint32_t)d, st))) return rc;
+        t.prec = t_t.as<double>();
+        break;
+    case MI_TARGET_LOGISTIC:
+        if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
+        t.kind = mi::lit::LIT_LOGISTIC; t.n_rows = (uint32_t)target->n_rows;
+        if ((rc = up(t_a, target->X, target->n_rows * d, &t.X))) return rc;
+        if ((rc = up(t_b, target->y, target->n_rows, &t.y))) return rc;
+        HIP_TRY(t_t.alloc(target->n_rows * d * 8));
+        if ((rc = transpose_on_device(t.X, t_t.as<double>(), (uint32_t)target->n_rows, (uint32_t)d, st))) return rc;
+        t.Xt = t_t.as<double>();
+        break;
+    default: return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d not implemented", who, target->kind);
+    }
+    mi::lit::lit_orders(t);
+    return MI_OK;
+}
+
 int run_literal(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
 {
     const uint64_t d = target->d, C = chains->n_chains;
@@ -634,42 +680,8 @@ int run_literal(const char* who, int algo, const mi_target* target, const mi_set
         return fail(MI_ERR_UNSUPPORTED, "nuts: max_tree_depth > %d not implemented (2^%d leapfrog steps per draw)", (int)mi::lit::LIT_NUTS_MAX_DEPTH, (int)mi::lit::LIT_NUTS_MAX_DEPTH);
     mi::lit::LitParams lp{};
     DevBuf t_a, t_b, t_t;                                // staged target (and its transposed matrix)
-    lp.t.d = (uint32_t)d;
-    auto up = [&](DevBuf& b, const double* src, size_t n_doubles, const double** out) -> int {
-        if (target->mem == MI_MEM_DEVICE) { *out = src; return MI_OK; }
-        HIP_TRY(b.alloc(n_doubles * 8));
-        HIP_TRY(hipMemcpy(b.p, src, n_doubles * 8, hipMemcpyHostToDevice));
-        *out = b.as<double>();
-        return MI_OK;
-    };
-    int rc;
-    switch (target->kind) {
-    case MI_TARGET_GAUSS_ISO: lp.t.kind = mi::lit::LIT_ISO; break;
-    case MI_TARGET_GAUSS_DIAG:
-        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DIAG needs prec (d)");
-        lp.t.kind = mi::lit::LIT_DIAG; lp.t.prec_stride = 1;
-        if ((rc = up(t_a, target->prec, d, &lp.t.prec))) return rc;
-        break;
-    case MI_TARGET_GAUSS_DENSE:
-        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DENSE needs prec (d*d)");
-        lp.t.kind = mi::lit::LIT_DENSE;
-        if ((rc = up(t_a, target->prec, d * d, &lp.t.prec))) return rc;
-        HIP_TRY(t_t.alloc(d * d * 8));                     // ... read transposed by the literal kernels
-        if ((rc = transpose_on_device(lp.t.prec, t_t.as<double>(), (uint32_t)d, (uint32_t)d, st))) return rc;
-        lp.t.prec = t_t.as<double>();
-        break;
-    case MI_TARGET_LOGISTIC:
-        if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-        lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.n_rows = (uint32_t)target->n_rows;
-        if ((rc = up(t_a, target->X, target->n_rows * d, &lp.t.X))) return rc;
-        if ((rc = up(t_b, target->y, target->n_rows, &lp.t.y))) return rc;
-        HIP_TRY(t_t.alloc(target->n_rows * d * 8));
-        if ((rc = transpose_on_device(lp.t.X, t_t.as<double>(), (uint32_t)target->n_rows, (uint32_t)d, st))) return rc;
-        lp.t.Xt = t_t.as<double>();
-        break;
-    default: return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d not implemented", who, target->kind);
-    }
-    mi::lit::lit_orders(lp.t);
+    int rc = lit_stage_target(who, target, lp.t, t_a, t_b, t_t, st);
+    if (rc) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
@@ -1255,6 +1267,167 @@ int literal_run_callback(const char* who, int algo, const double* initial_vals, 
         for (uint64_t j = 0; j < d; ++j) draws_out[i + j * n_keep] = rows[i * d + j];       // column-major n_keep x d, as Eigen's Mat_t stores draws_out
     if (n_accept_draws) HIP_TRY(hipMemcpy(n_accept_draws, nacc.p, 8, hipMemcpyDeviceToHost));
     if (step_size_out && algo == 2) HIP_TRY(hipMemcpy(step_size_out, step.p, 8, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+
+// ---- mcmc::de (src/de.cpp:28-232) for many populations: de.hpp.  Arguments are checked before anything touches the device.
+int de_check(const char* who, uint64_t d, const mi_settings* s, const mi_de_settings* de, uint64_t draw0)
+{
+    if (!s || !de) return fail(MI_ERR_BAD_ARG, "%s: null settings / de_settings", who);
+    if (s->struct_size != sizeof(mi_settings) || de->struct_size != sizeof(mi_de_settings))
+        return fail(MI_ERR_BAD_ARG, "struct_size mismatch (header / library version skew)");
+    if (d == 0 || d > 0x7fffffffULL) return fail(MI_ERR_BAD_ARG, "%s: d out of range", who);
+    if (de->n_pop < 3) return fail(MI_ERR_BAD_ARG, "%s: n_pop = %llu; differential evolution needs n_pop >= 3 (the reference loops forever below)", who,
+                                   (unsigned long long)de->n_pop);
+    if (de->n_pop * (uint64_t)mi::de_blocks((uint32_t)d) >= (1ull << 32))
+        return fail(MI_ERR_UNSUPPORTED, "%s: n_pop * (1 + ceil(d / 2)) >= 2^32 overflows the Philox slot counter", who);
+    if (draw0 + s->n_burnin_draws + s->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: draw0 + generations exceeds the 32-bit counter", who);
+    if (s->vals_bound && (!s->lower_bounds || !s->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
+    return MI_OK;
+}
+
+// the host-side half of DeParams: bounds (lit_prepare's tables), the initial box, gamma, counters
+struct DeTables { mi::lit::LitPrep prep; LitDev ldev; DevBuf box_lb, box_ub; };
+int de_tables(uint64_t d, const mi_settings* s, const mi_de_settings* de, DeTables& t, mi::DeParams& prm)
+{
+    int rc = mi::lit::lit_prepare(0, (uint32_t)d, 1.0, s->vals_bound ? 1 : 0, s->lower_bounds, s->upper_bounds, nullptr, t.prep);
+    if (rc) return rc;
+    if ((rc = lit_upload(t.prep, (uint32_t)d, s->vals_bound != 0, t.ldev, prm.lit))) return rc;
+    if (de->initial_lb) {
+        HIP_TRY(t.box_lb.alloc(d * 8)); HIP_TRY(hipMemcpy(t.box_lb.p, de->initial_lb, d * 8, hipMemcpyHostToDevice));
+        prm.box_lb = t.box_lb.as<double>();
+    }
+    if (de->initial_ub) {
+        HIP_TRY(t.box_ub.alloc(d * 8)); HIP_TRY(hipMemcpy(t.box_ub.p, de->initial_ub, d * 8, hipMemcpyHostToDevice));
+        prm.box_ub = t.box_ub.as<double>();
+    }
+    prm.d = (uint32_t)d; prm.n_pop = (uint32_t)de->n_pop;
+    prm.seed = s->rng_seed_value;
+    prm.n_burnin = (uint32_t)s->n_burnin_draws; prm.n_keep = (uint32_t)s->n_keep_draws;
+    prm.gamma = 2.38 / std::sqrt(2.0 * (double)d);         // de.cpp:61-62: par_gamma is not read
+    prm.gamma_jump = de->par_gamma_jump; prm.b = de->par_b; prm.jumps = de->jumps ? 1 : 0;
+    return MI_OK;
+}
+
+int de_run(const mi_target* target, const mi_settings* settings, const mi_de_settings* de, mi_populations* pops, hipStream_t st)
+{
+    if (!target || !pops) return fail(MI_ERR_BAD_ARG, "de: null target / populations");
+    if (target->struct_size != sizeof(mi_target) || pops->struct_size != sizeof(mi_populations))
+        return fail(MI_ERR_BAD_ARG, "struct_size mismatch (header / library version skew)");
+    const uint64_t d = target->d, NP = pops->n_populations;
+    int rc = de_check("de", d, settings, de, pops->draw0);
+    if (rc) return rc;
+    if (NP == 0) return fail(MI_ERR_BAD_ARG, "de: n_populations must be positive");
+    if (!pops->population) return fail(MI_ERR_BAD_ARG, "de: populations.population is required");
+    if (pops->draw0 == 0 && (!de->initial_lb || !de->initial_ub) && !pops->initial_vals)
+        return fail(MI_ERR_BAD_ARG, "de: populations.initial_vals is required (a fresh run without de.initial_lb / initial_ub)");
+    if (target->kind == MI_TARGET_NORMAL_MODEL)
+        return fail(MI_ERR_UNSUPPORTED, "de: MI_TARGET_NORMAL_MODEL has no literal (one workgroup per population) evaluation, which the de kernels are built on");
+    if (target->kind < MI_TARGET_GAUSS_ISO || target->kind > MI_TARGET_LOGISTIC) return fail(MI_ERR_UNSUPPORTED, "de: target kind %d not implemented", target->kind);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+
+    const uint64_t n_pop = de->n_pop, n_keep = settings->n_keep_draws;
+    const size_t pop_doubles = (size_t)n_pop * d * NP;
+    mi::DeParams prm{};
+    DeTables tb;
+    if ((rc = de_tables(d, settings, de, tb, prm))) return rc;
+    prm.NP = NP; prm.pop0 = pops->population0; prm.draw0 = (uint32_t)pops->draw0;
+    // populations in host memory are staged
+    const bool host = pops->mem == MI_MEM_HOST;
+    DevBuf s_init, s_pop, s_draws, s_acc;
+    prm.init_vals = pops->initial_vals; prm.X = pops->population; prm.draws = pops->draws; prm.n_accept = pops->n_accept;
+    if (host) {
+        if (pops->initial_vals && pops->draw0 == 0) {
+            HIP_TRY(s_init.alloc(d * NP * 8));
+            HIP_TRY(hipMemcpyAsync(s_init.p, pops->initial_vals, d * NP * 8, hipMemcpyHostToDevice, st));
+            prm.init_vals = s_init.as<double>();
+        } else prm.init_vals = nullptr;
+        HIP_TRY(s_pop.alloc(pop_doubles * 8));
+        if (pops->draw0 > 0) HIP_TRY(hipMemcpyAsync(s_pop.p, pops->population, pop_doubles * 8, hipMemcpyHostToDevice, st));
+        prm.X = s_pop.as<double>();
+        if (pops->draws) { HIP_TRY(s_draws.alloc(n_keep * pop_doubles * 8)); prm.draws = s_draws.as<double>(); }
+        if (pops->n_accept) { HIP_TRY(s_acc.alloc(NP * 8)); prm.n_accept = s_acc.as<uint64_t>(); }
+    }
+    const bool tile = (target->kind == MI_TARGET_GAUSS_ISO || target->kind == MI_TARGET_GAUSS_DIAG || target->kind == MI_TARGET_GAUSS_DENSE) &&
+                      d <= 128 && target->kernel_hint != MI_KERNEL_LITERAL;
+    DevBuf P_owned, t_a, t_b, t_t;
+    unsigned n_wg = 0;
+    size_t stride = 0;
+    if (tile) {
+        if ((rc = dense_precision_on_device(target, P_owned, &prm.P, st))) return rc;
+    } else {
+        if ((rc = lit_stage_target("de", target, prm.lit.t, t_a, t_b, t_t, st))) return rc;
+        stride = mi::lit::lit_work_doubles((uint32_t)d, prm.lit.t.n_rows, false);
+        n_wg = (unsigned)std::min<uint64_t>(NP, 1024u);
+    }
+    const size_t tv_bytes = ((size_t)n_pop * NP * 8 + 255) & ~(size_t)255;
+    WsLease ws;
+    if ((rc = ws_get(st, tv_bytes + (size_t)n_wg * stride * 8, ws))) return rc;
+    prm.tv = ws.as<double>();
+    prm.lit.work = reinterpret_cast<double*>(ws.as<char>() + tv_bytes); prm.lit.work_stride = stride;
+    if (tile) rc = launched("de", mi::launch_de_gauss(prm, (int)((d + 15) / 16), settings->vals_bound != 0, st));
+    else rc = launched("de", mi::launch_de_literal(prm, n_wg, st));
+    if (rc) return rc;
+    if (host) {
+        HIP_TRY(hipMemcpyAsync(pops->population, prm.X, pop_doubles * 8, hipMemcpyDeviceToHost, st));
+        if (pops->draws) HIP_TRY(hipMemcpyAsync(pops->draws, prm.draws, n_keep * pop_doubles * 8, hipMemcpyDeviceToHost, st));
+        if (pops->n_accept) HIP_TRY(hipMemcpyAsync(pops->n_accept, prm.n_accept, NP * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (host || P_owned.p || t_a.p || t_b.p || t_t.p || tb.ldev.any || tb.box_lb.p || tb.box_ub.p) HIP_TRY(hipStreamSynchronize(st));
+    return MI_OK;
+}
+
+// one population on de_literal_kernel with the HOST callback as target (LIT_CALLBACK): this thread serves the kernel's requests
+int de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data, const mi_settings* settings,
+                    const mi_de_settings* de, double* draws_out, uint64_t* n_accept)
+{
+    if (!initial_vals || !target_log_kernel) return fail(MI_ERR_BAD_ARG, "de (callback): null initial_vals / callback");
+    int rc = de_check("de (callback)", d, settings, de, 0);
+    if (rc) return rc;
+    const uint64_t n_pop = de->n_pop, n_keep = settings->n_keep_draws;
+    if (n_keep > 0 && !draws_out) return fail(MI_ERR_BAD_ARG, "de (callback): draws_out is required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    PinnedBuf ctl, val, xb, outb;
+    HIP_TRY(ctl.alloc(mi::lit::LIT_MB_WORDS * sizeof(uint32_t))); HIP_TRY(val.alloc(8)); HIP_TRY(xb.alloc(d * 8)); HIP_TRY(outb.alloc(d * 8));
+    std::memset(ctl.p, 0, mi::lit::LIT_MB_WORDS * sizeof(uint32_t));
+    mi::DeParams prm{};
+    prm.lit.t.kind = mi::lit::LIT_CALLBACK; prm.lit.t.d = (uint32_t)d;
+    mi::lit::lit_orders(prm.lit.t);
+    mi::lit::LitMailbox& mb = prm.lit.t.mb;
+    mb.ctl = ctl.as<uint32_t>(); mb.value = val.as<double>(); mb.x = xb.as<double>(); mb.out = outb.as<double>();
+    mb.timeout_ticks = 60ull * 100000000ull;              // 60 s of the 100 MHz wall clock per request
+    DeTables tb;
+    if ((rc = de_tables(d, settings, de, tb, prm))) return rc;
+    const size_t pop_doubles = (size_t)n_pop * d;
+    const size_t stride = mi::lit::lit_work_doubles((uint32_t)d, 0, false);
+    DevBuf init, X, tv, draws, acc, work;
+    HIP_TRY(init.alloc(d * 8)); HIP_TRY(X.alloc(pop_doubles * 8)); HIP_TRY(tv.alloc(n_pop * 8));
+    HIP_TRY(draws.alloc(n_keep * pop_doubles * 8)); HIP_TRY(acc.alloc(8)); HIP_TRY(work.alloc(stride * 8));
+    HIP_TRY(hipMemcpy(init.p, initial_vals, d * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(acc.p, 0, 8));
+    HIP_TRY(hipDeviceSynchronize());     // the kernel runs on its own NON-BLOCKING stream, which does not order itself behind the null stream's copies
+    prm.NP = 1; prm.pop0 = 0; prm.draw0 = 0;
+    prm.init_vals = init.as<double>(); prm.X = X.as<double>(); prm.tv = tv.as<double>();
+    prm.draws = n_keep ? draws.as<double>() : nullptr; prm.n_accept = acc.as<uint64_t>();
+    prm.lit.work = work.as<double>(); prm.lit.work_stride = stride;
+    hipStream_t st = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    rc = launched("de (callback)", mi::launch_de_literal(prm, 1, st));
+    if (!rc) {
+        (void)serve_callbacks(mb, (uint32_t)d, target_log_kernel, target_data, nullptr, nullptr, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MI_ERR_HIP, "de (callback): %s", hipGetErrorString(e));
+        else if (ctl.as<uint32_t>()[mi::lit::LIT_MB_ABORT] != 0u) rc = fail(MI_ERR_HIP, "de (callback): the kernel gave up waiting for a callback (60 s)");
+    }
+    (void)hipStreamDestroy(st);
+    if (rc) return rc;
+    if (n_keep) HIP_TRY(hipMemcpy(draws_out, draws.p, n_keep * pop_doubles * 8, hipMemcpyDeviceToHost));
+    if (n_accept) HIP_TRY(hipMemcpy(n_accept, acc.p, 8, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -2527,6 +2700,30 @@ int mi_mcmc_rmhmc_run(const mi_target* target, const mi_settings* settings, mi_c
     if (target->kind != MI_TARGET_NORMAL_MODEL)
         return fail(MI_ERR_UNSUPPORTED, "rmhmc: target kind %d has no built-in metric tensor on the device path (user targets: include/mi_mcmc_target.hpp)", target->kind);
     return run_small_normal_model("rmhmc", 4, target, settings, chains, static_cast<hipStream_t>(stream));
+}
+
+// mcmc::de (ref: src/de.cpp:28-232) for many populations (de.hpp)
+void mi_de_settings_default(mi_de_settings* s)
+{
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = sizeof(mi_de_settings);          // de_settings_t (mcmc_structs.hpp): jumps false, n_pop 100, par_b 1e-4, gammas 1 / 2
+    s->jumps = 0;
+    s->n_pop = 100;
+    s->par_b = 1e-4;
+    s->par_gamma_jump = 2.0;
+    s->par_gamma = 1.0;
+}
+
+int mi_mcmc_de_run(const mi_target* target, const mi_settings* settings, const mi_de_settings* de, mi_populations* pops, void* stream)
+{
+    return mi::host::de_run(target, settings, de, pops, static_cast<hipStream_t>(stream));
+}
+
+int mi_mcmc_de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
+                            const mi_settings* settings, const mi_de_settings* de, double* draws_out, uint64_t* n_accept)
+{
+    return mi::host::de_run_callback(initial_vals, d, target_log_kernel, target_data, settings, de, draws_out, n_accept);
 }
 
 }  // extern "C"
