@@ -271,6 +271,18 @@ inline target_t logistic_regression(size_t d, size_t n_rows, const double* X_row
     t.desc.n_rows = n_rows; return t;
 }
 
+// a mixture of M isotropic Gaussians (value only: mcmc::aees alone).  means: M x d row-major, variances: M, log_c: M values of
+// log(weight_i / (2 pi s2_i)^(d/2)) -- mixture_log_constants fills them.  The three arrays must outlive the run.
+inline void mixture_log_constants(size_t d, size_t M, const double* weights, const double* variances, double* log_c)
+{
+    for (size_t i = 0; i < M; ++i) log_c[i] = std::log(weights[i]) - (double(d) / 2.0) * std::log(2.0 * 3.14159265358979323846 * variances[i]);
+}
+inline target_t gaussian_mixture(size_t d, size_t M, const double* means_row_major, const double* variances, const double* log_c)
+{
+    target_t t = gaussian_iso(d); t.desc.kind = MI_TARGET_GAUSS_MIXTURE; t.desc.X = means_row_major; t.desc.prec = variances;
+    t.desc.y = log_c; t.desc.n_rows = M; return t;
+}
+
 // Tag callback: selects the device-target route. Never evaluated on the host.
 inline fp_t device_kernel(const ColVec_t&, ColVec_t*, void*) { return std::numeric_limits<fp_t>::quiet_NaN(); }
 
@@ -573,6 +585,63 @@ de_impl(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_i
     return true;
 }
 
+// mcmc::aees (ref: src/aees.cpp:28-305): draws_out (n_keep, d), the T = 1 level's draws.  The device tag (mi355x::device_value_kernel with a
+// mi355x::target_t) runs target_t::n_chains independent runs in one launch (draws_out (n_keep, d * n_chains), run c in columns c d .. c d + d - 1;
+// initial_vals d or d * n_chains values; target_t::n_accept_draws: every run's accepted MH steps at T = 1); any other callback runs one run with
+// the callback on the host (mi_mcmc_aees_run_callback).
+inline bool
+aees_impl(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel, Mat_t& draws_out,
+          void* target_data, algo_settings_t* settings_inp)
+{
+    algo_settings_t settings;
+    if (settings_inp) settings = *settings_inp;
+    const aees_settings_t& as = settings.aees_settings;
+    mi_settings m = flatten_common(settings);
+    m.n_burnin_draws = as.n_burnin_draws;
+    m.n_keep_draws = as.n_keep_draws;
+    const size_t n_init = size_t(initial_vals.size());
+    const bool device = mi355x::is_device_route(target_log_kernel);
+    const size_t d = device ? size_t(static_cast<mi355x::target_t*>(target_data)->desc.d) : n_init;
+    mi_aees_settings a; mi_aees_settings_default(&a);
+    a.n_initial_draws = as.n_initial_draws; a.par_scale = as.par_scale; a.ee_prob_par = as.ee_prob_par;
+    a.n_rings = (as.n_rings > 0xffffffffu) ? 0u : uint32_t(as.n_rings);          // beyond 32 bits: refused like n_rings = 0
+    a.cov_mat = precond_or_null(as.cov_mat, d);                                   // aees.cpp:80: only a d x d matrix counts
+    a.temper_len = uint64_t(as.temper_vec.size());
+    a.temper_vec = a.temper_len ? as.temper_vec.data() : nullptr;
+    const size_t K = size_t(a.temper_len) + 1, n_keep = as.n_keep_draws;
+    size_t C = 1;
+    std::vector<double> draws;
+    bool ok;
+    if (device) {
+        mi355x::target_t& tgt = *static_cast<mi355x::target_t*>(target_data);
+        C = tgt.n_chains ? tgt.n_chains : 1;
+        if (d == 0 || (n_init != d && n_init != d * C)) { tgt.last_error = "initial_vals must hold d or d*n_chains values"; return false; }
+        std::vector<double> init(d * C);
+        for (size_t c = 0; c < C; ++c)
+            for (size_t j = 0; j < d; ++j) init[j * C + c] = initial_vals(n_init == d ? j : c * d + j);
+        draws.assign(n_keep * d * C, 0.0);
+        std::vector<uint64_t> acc(K * C, 0);
+        mi_aees_runs r{};
+        r.struct_size = sizeof r; r.mem = MI_MEM_HOST; r.n_runs = C; r.run0 = tgt.chain0;
+        r.initial_vals = init.data(); r.draws = draws.data(); r.n_accept = acc.data();
+        tgt.desc.struct_size = sizeof(mi_target);
+        ok = mi_mcmc_aees_run(&tgt.desc, &m, &a, &r, nullptr) == MI_OK;
+        if (!ok) tgt.last_error = mi_mcmc_last_error();
+        else tgt.n_accept_draws.assign(acc.end() - C, acc.end());              // level K-1: T = 1
+    } else {
+        draws.assign(n_keep * d, 0.0);
+        value_callback_ctx ctx{&target_log_kernel, target_data, d};
+        ok = mi_mcmc_aees_run_callback(initial_vals.data(), d, &value_callback_trampoline, &ctx, &m, &a, draws.data(), nullptr, nullptr, nullptr) == MI_OK;
+        if (!ok) mi355x::last_error() = mi_mcmc_last_error();
+    }
+    if (!ok) return false;
+    draws_out.resize(n_keep, d * C);                                          // BMO_MATOPS_SET_SIZE(draws_out, n_keep_draws, n_vals), aees.cpp:266
+    for (size_t k = 0; k < n_keep; ++k)
+        for (size_t j = 0; j < d; ++j)
+            for (size_t c = 0; c < C; ++c) draws_out(k, c * d + j) = draws[(k * d + j) * C + c];
+    return true;
+}
+
 struct tensor_callback_ctx { const tensor_fn_t* fn; void* user; size_t d; };
 
 // tensor_fn(vals_inp, tensor_deriv_out, tensor_data) -> d*d row-major tensor and, when asked for, the d matrices dG/dvals_i
@@ -678,6 +747,14 @@ inline bool de(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t&
 inline bool de(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
                Cube_t& draws_out, void* target_data, algo_settings_t& settings)
 { return internal::de_impl(initial_vals, target_log_kernel, draws_out, target_data, &settings); }
+
+// mcmc::aees (ref: include/mcmc/aees.hpp): adaptive equi-energy sampling over the temperatures of settings.aees_settings.temper_vec
+inline bool aees(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
+                 Mat_t& draws_out, void* target_data)
+{ return internal::aees_impl(initial_vals, target_log_kernel, draws_out, target_data, nullptr); }
+inline bool aees(const ColVec_t& initial_vals, std::function<fp_t (const ColVec_t& vals_inp, void* target_data)> target_log_kernel,
+                 Mat_t& draws_out, void* target_data, algo_settings_t& settings)
+{ return internal::aees_impl(initial_vals, target_log_kernel, draws_out, target_data, &settings); }
 
 // NOT in the reference: mcmc::hmc on the device route with the DIAGONAL mass matrix adapted during burn-in -- pooled over the chains
 // (one matrix for all, estimated from their spread; mass_out: d values) or per chain (each chain from its own draws, Stan's scheme;

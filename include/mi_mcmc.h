@@ -58,11 +58,19 @@ typedef enum mi_target_kind {
                                  * (the remaining combinations, rwmh with a cov_mat or bounds beyond d = 8): the literal kernels -- same bits.  d > 512, hmc / mala / rwmh without
                                  * bounds / precond_mat (round 6): the state in HBM, two fp64 matrix products per gradient for all chains (gemm_samplers.hip);
                                  * the same for MI_TARGET_GAUSS_DENSE beyond d = 512 (one product per gradient) */
-    MI_TARGET_NORMAL_MODEL = 5  /* d = 2, vals = (mu, sigma), observations x_1..x_n in y[0..n_rows): the model of the reference's
+    MI_TARGET_NORMAL_MODEL = 5, /* d = 2, vals = (mu, sigma), observations x_1..x_n in y[0..n_rows): the model of the reference's
                                  * example programs (/root/reference/examples/eigen/rmhmc_normal.cpp:44-106),
                                  * log K = -n (log(2 pi)/2 + log sigma) - sum_r (x_r - mu)^2 / (2 sigma^2); its metric tensor for
                                  * rmhmc is the Fisher information diag(n / sigma^2, 2 n / sigma^2).  hmc, mala, nuts, rwmh, rmhmc (any
                                  * precond_mat / cov_mat, any bounds). */
+    MI_TARGET_GAUSS_MIXTURE = 6 /* VALUE ONLY (no gradient): a mixture of M = n_rows isotropic Gaussians, for mi_mcmc_aees_run alone (every other
+                                 * sampler returns MI_ERR_UNSUPPORTED).  X: the means, M x d row-major; prec: the variances s2_i (M values);
+                                 * y: log c_i (M values), the log of weight_i / (2 pi s2_i)^(d/2), computed by the caller.
+                                 *   dist_i = sum_j (x_j - mu_ij)^2          (j ascending, each square rounded, then added: no fma)
+                                 *   a_i    = log c_i - (0.5 dist_i) / s2_i
+                                 *   m      = max_i a_i                       (i ascending, a later a_i replaces m iff a_i > m)
+                                 *   log K  = m + log(sum_i exp(a_i - m))     (i ascending; the engine's exp / log, det_math.hpp)
+                                 * Non-finite: any a_i NaN -> NaN; m = -inf (every component underflows) -> -inf; m = +inf -> +inf. */
 } mi_target_kind;
 
 typedef enum mi_mem { MI_MEM_HOST = 0, MI_MEM_DEVICE = 1 } mi_mem;
@@ -356,6 +364,79 @@ int mi_mcmc_de_run(const mi_target* target, const mi_settings* settings, const m
  * values; draws_out: [n_keep][n_pop][d], may be NULL when n_keep == 0; n_accept: may be NULL.  Blocking. */
 int mi_mcmc_de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
                             const mi_settings* settings, const mi_de_settings* de, double* draws_out, uint64_t* n_accept);
+
+/* ---- mcmc::aees (ref: src/aees.cpp:28-305, include/mcmc/aees.ipp:30-70): adaptive equi-energy sampling, MANY independent runs per call.
+ *
+ * One run is one call of mcmc::aees.  K = temper_len + 1 levels: temper_vec with 1.0 appended, sorted DESCENDING (level 0 the hottest,
+ * level K-1 at T = 1).  S = n_initial_draws + n_burnin_draws, n_total = n_keep + K S.  For every draw n = 0 .. n_total-1 the levels run
+ * in order 0 .. K-1 (the reference with omp_n_threads = 1, its only deterministic reading):
+ *   level 0: one MH step at T_0.
+ *   level k >= 1, active iff n > k S (inactive: its state stays the zero vector, its kernel values 0): with z_eps > ee_prob_par an MH
+ *     step at T_k, kv0 = v / T_(k-1), kv1 = v / T_k; otherwise an equi-energy step: begin = (k-1) S, m = n - begin + 1,
+ *     s = floor(m / n_rings); s = 0: the level stays put.  Else W = level k-1's T = 1 log kernels of draws begin .. n in ascending
+ *     order, ring bounds b_i = (W[i s] + W[i s - 1]) / 2 (i = 1 .. n_rings-1), which_ring = the number of leading bounds with
+ *     v_k(n-1) > b_i, r = s which_ring + floor(z_tmp s), ind_mix = the window POSITION of rank r; the proposal is level k-1's state
+ *     at ABSOLUTE draw ind_mix, rejected iff z > exp(min(0.01, (new1 - kv1) + (kv0 - new0))).  v_k(n) = the level's log kernel.
+ *   MH step: X' = X + (sqrt(T) (par_scale CHOL_LOWER(cov_mat))) z, the matrix product one fma chain per row (columns ascending);
+ *     comp = std::min(0.01, (v' - v) / T) (a NaN difference gives 0.01: ACCEPT); accept iff u < exp(comp).  No clamp of non-finite
+ *     values (unlike rwmh).
+ *   kept draws: level K-1 for n >= K S, inverse-transformed when bounded.
+ * The reference's quirks, reproduced as written:
+ *   1. row 0 of kernel_vals is never written: level 1's window is all zeros, its ring bounds 0, its rank-r pick window position r;
+ *   2. ind_mix is a window position used as an absolute draw index: for k >= 2 it points at early draws of level k-1, often zero
+ *      states from before that level became active;
+ *   3. a draw-storage entry not yet written reads as zeros (ind_mix = n; every state of an inactive level);
+ *   4. the window's order, which get_sort_index leaves unspecified (and std::sort over NaN undefined), is OURS: ascending by value,
+ *      ties by window position (a stable sort), -0 equal to +0, NaN after +inf.
+ * cov_mat: d*d host values or NULL (the identity).  settings: rng_seed_value, vals_bound / bounds, n_burnin_draws / n_keep_draws (aees_settings_t's
+ * counts); nothing else of mi_settings is read.  Refused before the device is touched (MI_ERR_BAD_ARG): n_rings = 0 (the reference's
+ * n_rings - 1 wraps), a temperature <= 0 or not finite, n_total >= 2^32.  Continuing a run (a draw0 > 0) is NOT offered: it would need the
+ * whole history of every level carried across calls.
+ *
+ * RNG contract (counter-based Philox): chain id run K + k with run the GLOBAL run (run0 + r), draw n:
+ *   normals of an MH step: the engine's normal vector (rnorm_vec_inplace, literal.hpp) on stream tag 5;
+ *   uniforms: rng_block(seed, run K + k, n, slot, tag 6); slot 0: z_eps = u01(w0, w1), the accept uniform of whichever test runs
+ *   (MH or equi-energy) u01(w2, w3); slot 1: z_tmp = u01(w0, w1).  u01 as for mcmc::de.
+ * Counters: n_accept[k] the accepted MH steps of level k over all n_total draws, n_ee_accept[k] the accepted equi-energy moves (0 for
+ * level 0); a stay-put step (s = 0) counts as neither. */
+typedef struct mi_aees_settings {
+    uint32_t struct_size;
+    uint32_t n_rings;             /* default 5; >= 1 */
+    uint64_t n_initial_draws;     /* default 1000 */
+    double   par_scale;           /* default 1.0 */
+    const double* cov_mat;        /* d*d host values, row-major, or NULL = identity */
+    double   ee_prob_par;         /* default 0.10 */
+    const double* temper_vec;     /* temper_len host values (the levels above T = 1, any order), or NULL when temper_len = 0 */
+    uint64_t temper_len;          /* default 0: K = 1, a plain MH chain at T = 1 */
+} mi_aees_settings;
+
+/* P runs; all pointers in `mem`.  Layouts run-index contiguous, like mi_chains. */
+typedef struct mi_aees_runs {
+    uint32_t  struct_size;
+    int32_t   mem;
+    uint64_t  n_runs;             /* P */
+    uint64_t  run0;               /* global id of local run 0 (the Philox counter uses it: sharding does not change the bits) */
+    const double* initial_vals;   /* [d][P] */
+    double*   draws;              /* [n_keep][d][P] out (inverse-transformed when bounded), may be NULL */
+    double*   final_states;       /* [K][d][P] out: every level's last state in the sampler's (transformed) space, may be NULL */
+    uint64_t* n_accept;           /* [K][P] out, may be NULL */
+    uint64_t* n_ee_accept;        /* [K][P] out, may be NULL */
+} mi_aees_runs;
+
+void mi_aees_settings_default(mi_aees_settings* s);
+/* One workgroup per run on the literal target evaluation (literal.hpp): every kind it knows and MI_TARGET_GAUSS_MIXTURE;
+ * MI_TARGET_NORMAL_MODEL: MI_ERR_UNSUPPORTED.  The history (every level's states and T = 1 log kernels, and a sorted index per level
+ * k >= 2, merged lazily at the level's equi-energy steps) lives in a device workspace of the per-stream cache; the runs are served in
+ * batches that keep it under a budget; MI_ERR_OOM only when one run alone does not fit. */
+int mi_mcmc_aees_run(const mi_target* target, const mi_settings* settings, const mi_aees_settings* aees, mi_aees_runs* runs, void* stream);
+/* The reference's own contract, one run: target_log_kernel asked for the value only (grad_out NULL), served on the calling thread while
+ * the kernel runs.  The kernel keeps the log kernel of every level's current state (the target is deterministic), so it asks
+ * 1 (the initial state) + (K > 1 ? 1 : 0) (the zero state of the levels not yet active) + one per MH step + one per equi-energy step
+ * with s >= 1 -- the reference asks twice per MH step and once more per level and draw.  initial_vals: d values; draws_out: [n_keep][d],
+ * may be NULL when n_keep == 0; final_states [K][d], n_accept [K], n_ee_accept [K]: may be NULL.  Blocking. */
+int mi_mcmc_aees_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
+                              const mi_settings* settings, const mi_aees_settings* aees, double* draws_out, double* final_states,
+                              uint64_t* n_accept, uint64_t* n_ee_accept);
 
 /* ---- the BaseMatrixOps shim's INV and CHOL_LOWER as the engine computes them for a dense precond_mat (ref: src/hmc.cpp:58-59,
  * src/mala.cpp:58, include/stats/dmvnorm.hpp:36-41 through include/mcmc/mala.ipp:63-64): Gauss-Jordan with partial pivoting (first largest

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libmi_mcmc.so")
 
 MI_OK, MI_ERR_BAD_ARG, MI_ERR_HIP, MI_ERR_UNSUPPORTED, MI_ERR_OOM, MI_ERR_NO_DEVICE = range(6)
 TARGET_GAUSS_ISO, TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_NORMAL_MODEL = 1, 2, 3, 4, 5
+TARGET_GAUSS_MIXTURE = 6                  # value only: mcmc::aees alone (mixture_target builds one)
 MEM_HOST, MEM_DEVICE = 0, 1
 KERNEL_AUTO, KERNEL_ELEMENTWISE_1LANE, KERNEL_ELEMENTWISE_4LANE, KERNEL_NUTS_LOCKSTEP = 0, 1, 2, 3   # mi_kernel_hint
 KERNEL_HMC_TWO_WAVES_PER_SIMD, KERNEL_HMC_ONE_WAVE_PER_SIMD, KERNEL_HMC_SPLIT2, KERNEL_HMC_SPLIT4, KERNEL_HMC_SPLIT4_TWO_WAVES = 4, 5, 6, 7, 8
@@ -63,6 +64,17 @@ class mi_populations(C.Structure):
                 ("draw0", C.c_uint64)]
 
 
+class mi_aees_settings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_rings", C.c_uint32), ("n_initial_draws", C.c_uint64), ("par_scale", C.c_double),
+                ("cov_mat", C.c_void_p), ("ee_prob_par", C.c_double), ("temper_vec", C.c_void_p), ("temper_len", C.c_uint64)]
+
+
+class mi_aees_runs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mem", C.c_int32), ("n_runs", C.c_uint64), ("run0", C.c_uint64),
+                ("initial_vals", C.c_void_p), ("draws", C.c_void_p), ("final_states", C.c_void_p), ("n_accept", C.c_void_p),
+                ("n_ee_accept", C.c_void_p)]
+
+
 class MiMcmcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"mi_mcmc status {code}: {msg}")
@@ -75,6 +87,7 @@ EXPORTS = [
     "mi_settings_default", "mi_mcmc_last_error", "mi_mcmc_last_kernel", "mi_mcmc_version", "mi_mcmc_device_count", "mi_mcmc_release_workspace", "mi_mcmc_run_user_target", "mi_mcmc_run_user_target_v", "mi_mcmc_run_tile_target",
     "mi_mcmc_hmc_run", "mi_mcmc_mala_run", "mi_mcmc_nuts_run", "mi_mcmc_rwmh_run", "mi_mcmc_rmhmc_run", "mi_mcmc_hmc_run_mass_adapted", "mi_mcmc_hmc_run_mass_adapted_per_chain", "mi_mcmc_hmc_run_callback", "mi_mcmc_mala_run_callback", "mi_mcmc_nuts_run_callback", "mi_mcmc_rwmh_run_callback", "mi_mcmc_rmhmc_run_callback",
     "mi_de_settings_default", "mi_mcmc_de_run", "mi_mcmc_de_run_callback",
+    "mi_aees_settings_default", "mi_mcmc_aees_run", "mi_mcmc_aees_run_callback",
     "mi_mcmc_draws_to_chain_major", "mi_mcmc_draws_to_chain_major_device", "mi_mcmc_shard_bounds", "mi_mcmc_allgather_draws", "mi_mcmc_allgather_draws_ragged", "mi_mcmc_merge_shards", "mi_mcmc_draw_stats",
     "mi_mcmc_allgather_draws_rank_major", "mi_mcmc_rank_major_index", "mi_mcmc_allgather_draws_begin", "mi_mcmc_allgather_draws_wait",
     "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
@@ -444,6 +457,87 @@ def de_callback(initial_vals, callback, settings, de_settings=None, n_pop=None, 
     _check(lib().mi_mcmc_de_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
                                          C.byref(settings), C.byref(ds), C.c_void_p(draws.ctypes.data), C.byref(n_acc)))
     return draws, int(n_acc.value)
+
+
+def mixture_log_constants(weights, variances, d):
+    """log c_i = log w_i - (d / 2) log(2 pi s2_i): the y of a TARGET_GAUSS_MIXTURE (include/mi_mcmc.h)"""
+    w = np.asarray(weights, dtype=np.float64)
+    s2 = np.asarray(variances, dtype=np.float64)
+    return np.log(w) - (d / 2.0) * np.log(2.0 * np.pi * s2)
+
+
+def mixture_target(means, variances, weights, mem=MEM_HOST):
+    """TARGET_GAUSS_MIXTURE: means [M, d], variances [M] (isotropic per component), weights [M]"""
+    means = np.ascontiguousarray(means, dtype=np.float64)
+    M, d = means.shape
+    return make_target(TARGET_GAUSS_MIXTURE, d, prec=np.asarray(variances, dtype=np.float64).reshape(M), X=means,
+                       y=mixture_log_constants(weights, variances, d), mem=mem)
+
+
+def aees_settings(**kw):
+    """aees_settings_t with the reference defaults (n_initial_draws 1000, par_scale 1, n_rings 5, ee_prob_par 0.1, no temper_vec),
+    then keyword overrides; cov_mat: d x d or None (identity); temper_vec: the temperatures above 1 (any order) or None."""
+    s = mi_aees_settings()
+    lib().mi_aees_settings_default(C.byref(s))
+    keep = []
+    for k, v in kw.items():
+        if k in ("cov_mat", "temper_vec"):
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+                keep.append(v)
+                if k == "temper_vec":
+                    s.temper_len = v.size
+                v = v.ctypes.data
+            elif k == "temper_vec":
+                s.temper_len = 0
+        setattr(s, k, v)
+    s._keep = keep
+    return s
+
+
+def aees(target, init, settings, aees_settings=None, run0=0, want_draws=True):
+    """mcmc::aees for P independent runs at once (mi_mcmc_aees_run), host buffers.  target: a mi_target (make_target /
+    mixture_target) or a kind (then a Gaussian with no parameters, TARGET_GAUSS_ISO); init: [P, d]; settings: rng_seed_value,
+    bounds, n_burnin_draws / n_keep_draws.  Returns draws [n_keep, d, P] (or None) and a dict with final_states [K, d, P]
+    (transformed space), n_accept [K, P] and n_ee_accept [K, P]."""
+    a = aees_settings if aees_settings is not None else globals()["aees_settings"]()
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    P, d = init.shape
+    t = make_target(target, d) if isinstance(target, int) else target
+    K, n_keep = int(a.temper_len) + 1, int(settings.n_keep_draws)
+    iv = np.ascontiguousarray(init.T)                                    # [d][P]
+    draws = np.zeros((n_keep, d, P)) if want_draws else None
+    fin = np.zeros((K, d, P))
+    n_acc = np.zeros((K, P), dtype=np.uint64)
+    n_ee = np.zeros((K, P), dtype=np.uint64)
+    r = mi_aees_runs()
+    r.struct_size = C.sizeof(mi_aees_runs)
+    r.mem, r.n_runs, r.run0 = MEM_HOST, P, int(run0)
+    r.initial_vals, r.draws, r.final_states, r.n_accept, r.n_ee_accept = _ptr(iv), _ptr(draws), _ptr(fin), _ptr(n_acc), _ptr(n_ee)
+    _check(lib().mi_mcmc_aees_run(C.byref(t), C.byref(settings), C.byref(a), C.byref(r), C.c_void_p(0)))
+    return draws, dict(final_states=fin, n_accept=n_acc, n_ee_accept=n_ee)
+
+
+def aees_callback(initial_vals, callback, settings, aees_settings=None, target_data=None):
+    """mcmc::aees with a host callback for one run (mi_mcmc_aees_run_callback).  callback: a ctypes mi_log_kernel_cb or a Python
+    callable f(vals: np.ndarray) -> value.  Returns draws [n_keep, d] and a dict with final_states [K, d], n_accept [K], n_ee_accept [K]."""
+    a = aees_settings if aees_settings is not None else globals()["aees_settings"]()
+    x0 = np.ascontiguousarray(initial_vals, dtype=np.float64)
+    d, K = x0.size, int(a.temper_len) + 1
+    draws = np.zeros((int(settings.n_keep_draws), d))
+    fin = np.zeros((K, d))
+    n_acc = np.zeros(K, dtype=np.uint64)
+    n_ee = np.zeros(K, dtype=np.uint64)
+    if callable(callback) and not isinstance(callback, C._CFuncPtr):
+        def _tramp(vals, _grad, _user):
+            return float(callback(np.ctypeslib.as_array(vals, shape=(d,)).copy()))
+        cb = LOG_KERNEL_CB(_tramp)
+    else:
+        cb = callback
+    _check(lib().mi_mcmc_aees_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
+                                           C.byref(settings), C.byref(a), C.c_void_p(draws.ctypes.data), C.c_void_p(fin.ctypes.data),
+                                           C.c_void_p(n_acc.ctypes.data), C.c_void_p(n_ee.ctypes.data)))
+    return draws, dict(final_states=fin, n_accept=n_acc, n_ee_accept=n_ee)
 
 
 # ---------------------------------------------------------------- diagnostics (GPU tests)

@@ -15,6 +15,7 @@ struct NutsParams;
 struct RwmhParams;
 struct SmallParams;
 struct DeParams;
+struct AeesParams;
 namespace lit { struct LitParams; }
 
 // nt = ceil(d / 16) in {1, 2, 3..4, 5..8}; general: bounds and / or diagonal precond; dense_m: dense precond (nt <= 4)
@@ -63,5 +64,8 @@ int launch_literal(int algo, const lit::LitParams& prm, unsigned n_wg, hipStream
 // workgroup; and on the literal kernel, one workgroup of 256 threads per population (n_wg workgroups, every target kind)
 int launch_de_gauss(const DeParams& prm, int nt, bool general, hipStream_t st);
 int launch_de_literal(const DeParams& prm, unsigned n_wg, hipStream_t st);
+
+// aees.hpp (aees_launch.hip): mcmc::aees, one workgroup of 256 threads per run (n_wg workgroups, each with its own history slot)
+int launch_aees_literal(const AeesParams& prm, unsigned n_wg, hipStream_t st);
 
 }  // namespace mi

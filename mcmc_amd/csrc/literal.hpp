@@ -30,7 +30,8 @@ constexpr double LIT_EPS_DBL = 2.220446049250313e-16;    // mcmc_options.hpp:103
 constexpr double LIT_LOG_2PI = 1.83787706640934548356;   // stats/mcmc_stats.hpp:28-30
 
 enum { LIT_ISO = 0, LIT_DIAG = 1, LIT_DENSE = 2, LIT_LOGISTIC = 3,
-       LIT_CALLBACK = 4 };   // the user's HOST callbacks (the reference's std::function contract): see LitMailbox
+       LIT_CALLBACK = 4,     // the user's HOST callbacks (the reference's std::function contract): see LitMailbox
+       LIT_MIXTURE = 5 };    // MI_TARGET_GAUSS_MIXTURE, value only (mcmc::aees alone): see mixture_log_kernel
 
 // LIT_CALLBACK.  The target (and, for rmhmc, the metric tensor) is a function that can only run on the host, while the sampler's own
 // arithmetic runs here.  The kernel therefore ASKS: the workgroup writes the evaluation point into a mailbox in host-pinned, fine-grained
@@ -62,7 +63,8 @@ struct LitTarget {
                              // (a workgroup forms row i in thread i: consecutive threads then read consecutive addresses; the fma
                              // chain of a row still runs over k ascending)
     uint32_t prec_stride;    // LIT_DIAG: 1, or d + 1 when prec is the diagonal of a dense d*d matrix
-    const double* X;         // LIT_LOGISTIC: n_rows*d row-major (X^T r: thread j walks the rows)
+    const double* X;         // LIT_LOGISTIC: n_rows*d row-major (X^T r: thread j walks the rows); LIT_MIXTURE: the means, n_rows*d row-major
+                             // (prec: the n_rows variances, y: the n_rows log constants)
     const double* Xt;        // LIT_LOGISTIC: the same matrix transposed, Xt[j * n_rows + r] (eta = X beta: thread r walks the columns)
     const double* y;
     int W;                   // strided fma chains of a dot product (4: the layout of the MFMA kernels)
@@ -414,6 +416,34 @@ MI_HD bool mailbox_call(const Par& par, const LitTarget& t, const double* x, uin
 #endif
 }
 
+// MI_TARGET_GAUSS_MIXTURE (mi_mcmc.h states the operations): log sum_i exp(log c_i - 0.5 |x - mu_i|^2 / s2_i).  Every thread computes the
+// same scalar (the components in order, each distance j ascending): no reduction order to agree on.
+MI_HD double mixture_log_kernel(const LitTarget& t, const double* x)
+{
+    const uint32_t d = t.d, M = t.n_rows;
+    double m = -INF;
+    bool nan = false;
+    for (uint32_t i = 0; i < M; ++i) {
+        const double* mu = t.X + (size_t)i * d;
+        double dist = 0.0;
+        for (uint32_t j = 0; j < d; ++j) { const double df = x[j] - mu[j]; dist = dist + df * df; }
+        const double a = t.y[i] - (0.5 * dist) / t.prec[i];
+        if (a != a) nan = true;
+        if (i == 0 || a > m) m = a;
+    }
+    if (nan) return lit_nan();
+    if (m == -INF || m == INF) return m;
+    double sum = 0.0;
+    for (uint32_t i = 0; i < M; ++i) {
+        const double* mu = t.X + (size_t)i * d;
+        double dist = 0.0;
+        for (uint32_t j = 0; j < d; ++j) { const double df = x[j] - mu[j]; dist = dist + df * df; }
+        const double a = t.y[i] - (0.5 * dist) / t.prec[i];
+        sum = sum + det_exp(a - m);
+    }
+    return m + det_log(sum);
+}
+
 MI_HD double target_eval(const Par& par, const LitTarget& t, const double* x, double* grad, double* w, double* rows)
 {
     const uint32_t d = t.d;
@@ -423,6 +453,12 @@ MI_HD double target_eval(const Par& par, const LitTarget& t, const double* x, do
         if (grad) { LIT_PFOR(i, d) grad[i] = ok ? t.mb.out[i] : lit_nan(); }
         const double r = ok ? *t.mb.value : lit_nan();
         par.sync();                                         // the mailbox may be reused by the caller's next request
+        return r;
+    }
+    case LIT_MIXTURE: {                                     // value only: no sampler with a gradient is handed this kind
+        if (grad) { LIT_PFOR(i, d) grad[i] = lit_nan(); par.sync(); }
+        const double r = mixture_log_kernel(t, x);
+        par.sync();
         return r;
     }
     case LIT_ISO: {

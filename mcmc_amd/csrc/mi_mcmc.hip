@@ -31,6 +31,8 @@
 #include "rwmh_dense.hpp"
 #define MI_DE_PARAMS_ONLY
 #include "de.hpp"
+#define MI_AEES_PARAMS_ONLY
+#include "aees.hpp"
 #include "hmc_diag.hpp"
 #include "logistic_launch.hpp"
 #include "launchers.hpp"
@@ -627,7 +629,9 @@ void lit_set_chain_mass(mi::lit::LitParams& lp, const double* mass_dev, const Ch
 
 // the target of a literal kernel (literal.hpp: LitTarget) in device memory: a host-memory target is staged into a / b, a matrix the literal
 // kernels read transposed into t_t.  The buffers must outlive the launch.
-int lit_stage_target(const char* who, const mi_target* target, mi::lit::LitTarget& t, DevBuf& t_a, DevBuf& t_b, DevBuf& t_t, hipStream_t st)
+// value_only: the caller never asks for a gradient, so the value-only kinds (MI_TARGET_GAUSS_MIXTURE) are served too.
+int lit_stage_target(const char* who, const mi_target* target, mi::lit::LitTarget& t, DevBuf& t_a, DevBuf& t_b, DevBuf& t_t, hipStream_t st,
+                     bool value_only = false)
 {
     const uint64_t d = target->d;
     t.d = (uint32_t)d;
@@ -662,6 +666,15 @@ int lit_stage_target(const char* who, const mi_target* target, mi::lit::LitTarge
         HIP_TRY(t_t.alloc(target->n_rows * d * 8));
         if ((rc = transpose_on_device(t.X, t_t.as<double>(), (uint32_t)target->n_rows, (uint32_t)d, st))) return rc;
         t.Xt = t_t.as<double>();
+        break;
+    case MI_TARGET_GAUSS_MIXTURE:
+        if (!value_only) return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is value-only (mcmc::aees alone)", who);
+        if (!target->X || !target->prec || !target->y || target->n_rows == 0 || target->n_rows > 0xffffffffULL)
+            return fail(MI_ERR_BAD_ARG, "GAUSS_MIXTURE needs X (M*d means), prec (M variances), y (M log constants), n_rows = M");
+        t.kind = mi::lit::LIT_MIXTURE; t.n_rows = (uint32_t)target->n_rows;
+        if ((rc = up(t_a, target->X, target->n_rows * d, &t.X))) return rc;
+        if ((rc = up(t_b, target->prec, target->n_rows, &t.prec))) return rc;
+        if ((rc = up(t_t, target->y, target->n_rows, &t.y))) return rc;
         break;
     default: return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d not implemented", who, target->kind);
     }
@@ -1428,6 +1441,185 @@ int de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb tar
     if (rc) return rc;
     if (n_keep) HIP_TRY(hipMemcpy(draws_out, draws.p, n_keep * pop_doubles * 8, hipMemcpyDeviceToHost));
     if (n_accept) HIP_TRY(hipMemcpy(n_accept, acc.p, 8, hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+
+// ---- mcmc::aees (src/aees.cpp:28-305) for many runs: aees.hpp.  Arguments are checked before anything touches the device.
+#ifndef MI_AEES_WS_MAX_BYTES
+#define MI_AEES_WS_MAX_BYTES ((size_t)16 << 30)          // the history slots of one call: runs beyond what fits wait for a free slot
+#endif
+constexpr unsigned AEES_MAX_WG = 2048;                   // 8 workgroups of 256 threads per CU on 256 CUs
+
+int aees_check(const char* who, uint64_t d, const mi_settings* s, const mi_aees_settings* a)
+{
+    if (!s || !a) return fail(MI_ERR_BAD_ARG, "%s: null settings / aees_settings", who);
+    if (s->struct_size != sizeof(mi_settings) || a->struct_size != sizeof(mi_aees_settings))
+        return fail(MI_ERR_BAD_ARG, "struct_size mismatch (header / library version skew)");
+    if (d == 0 || d > 0x7fffffffULL) return fail(MI_ERR_BAD_ARG, "%s: d out of range", who);
+    if (a->n_rings == 0) return fail(MI_ERR_BAD_ARG, "%s: n_rings = 0 (the reference's n_rings - 1 wraps)", who);
+    if (a->temper_len > 0 && !a->temper_vec) return fail(MI_ERR_BAD_ARG, "%s: temper_len > 0 needs temper_vec", who);
+    if (a->temper_len > 0xffffULL) return fail(MI_ERR_BAD_ARG, "%s: temper_len out of range", who);
+    for (uint64_t i = 0; i < a->temper_len; ++i)
+        if (!(a->temper_vec[i] > 0.0) || !std::isfinite(a->temper_vec[i]))
+            return fail(MI_ERR_BAD_ARG, "%s: temper_vec[%llu] = %g: every temperature must be finite and > 0", who, (unsigned long long)i, a->temper_vec[i]);
+    const unsigned __int128 K = (unsigned __int128)a->temper_len + 1;
+    const unsigned __int128 n_total = (unsigned __int128)s->n_keep_draws + K * ((unsigned __int128)a->n_initial_draws + s->n_burnin_draws);
+    if (n_total >= ((unsigned __int128)1 << 32)) return fail(MI_ERR_BAD_ARG, "%s: n_keep + K (n_initial + n_burnin) must stay below 2^32", who);
+    if (s->vals_bound && (!s->lower_bounds || !s->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
+    return MI_OK;
+}
+
+// the host-side half of AeesParams: bounds, the temperatures (descending), the K scaled proposal matrices
+struct AeesTables { mi::lit::LitPrep prep; LitDev ldev; DevBuf temp, At; };
+int aees_tables(uint64_t d, const mi_settings* s, const mi_aees_settings* a, AeesTables& t, mi::AeesParams& prm)
+{
+    int rc = mi::lit::lit_prepare(0, (uint32_t)d, 1.0, s->vals_bound ? 1 : 0, s->lower_bounds, s->upper_bounds, nullptr, t.prep);
+    if (rc) return rc;
+    if ((rc = lit_upload(t.prep, (uint32_t)d, s->vals_bound != 0, t.ldev, prm.lit))) return rc;
+    const uint32_t K = (uint32_t)a->temper_len + 1;
+    std::vector<double> T(a->temper_vec, a->temper_vec + a->temper_len);
+    T.push_back(1.0);                                       // aees.cpp:62-76: 1 appended, sorted descending
+    std::sort(T.begin(), T.end(), [](double x, double y) { return x > y; });
+    std::vector<double> L((size_t)d * d, 0.0);              // CHOL_LOWER(cov_mat), or the identity (aees.cpp:82-85)
+    if (a->cov_mat) {
+        std::vector<double> Lc;
+        if ((rc = host_cholesky_lower(a->cov_mat, (size_t)d, Lc))) return rc;
+        L = Lc;
+    } else for (uint64_t i = 0; i < d; ++i) L[i * d + i] = 1.0;
+    std::vector<double> At((size_t)K * d * d);              // (sqrt(T_k) * (par_scale * L)), transposed per level
+    for (uint32_t k = 0; k < K; ++k) {
+        const double sq = std::sqrt(T[k]);
+        for (uint64_t i = 0; i < d; ++i)
+            for (uint64_t c = 0; c < d; ++c) At[((size_t)k * d + c) * d + i] = sq * (a->par_scale * L[i * d + c]);
+    }
+    HIP_TRY(t.temp.alloc(K * 8)); HIP_TRY(hipMemcpy(t.temp.p, T.data(), K * 8, hipMemcpyHostToDevice));
+    HIP_TRY(t.At.alloc(At.size() * 8)); HIP_TRY(hipMemcpy(t.At.p, At.data(), At.size() * 8, hipMemcpyHostToDevice));
+    prm.d = (uint32_t)d; prm.K = K; prm.n_rings = a->n_rings;
+    prm.S = (uint32_t)(a->n_initial_draws + s->n_burnin_draws); prm.n_keep = (uint32_t)s->n_keep_draws;
+    prm.n_total = prm.n_keep + K * prm.S;
+    prm.seed = s->rng_seed_value; prm.ee_prob = a->ee_prob_par;
+    prm.temp = t.temp.as<double>(); prm.At = t.At.as<double>();
+    return MI_OK;
+}
+
+// the workgroups of one launch and their workspace: literal scratch + one history slot each
+int aees_workspace(mi::AeesParams& prm, uint64_t n_runs, hipStream_t st, WsLease& ws, unsigned& n_wg)
+{
+    const size_t slot = mi::aees_slot_bytes(prm.d, prm.K, prm.S, prm.n_total);
+    prm.lit_stride = mi::lit::lit_work_doubles(prm.d, prm.lit.t.n_rows, false);
+    const size_t work = ((mi::aees_work_doubles(prm.lit_stride, prm.d, prm.K) * 8) + 255) & ~(size_t)255;
+    if (slot + work > MI_AEES_WS_MAX_BYTES)
+        return fail(MI_ERR_OOM, "aees: one run's history needs %zu bytes, more than the %zu-byte budget", slot + work, (size_t)MI_AEES_WS_MAX_BYTES);
+    n_wg = (unsigned)std::min<uint64_t>({n_runs, (uint64_t)AEES_MAX_WG, (uint64_t)(MI_AEES_WS_MAX_BYTES / (slot + work))});
+    int rc = ws_get(st, (size_t)n_wg * (slot + work), ws);
+    if (rc) return rc;
+    prm.lit.work = ws.as<double>(); prm.lit.work_stride = work / 8;
+    prm.hist = ws.as<char>() + (size_t)n_wg * work; prm.hist_stride = slot;
+    return MI_OK;
+}
+
+int aees_run(const mi_target* target, const mi_settings* settings, const mi_aees_settings* aees, mi_aees_runs* runs, hipStream_t st)
+{
+    if (!target || !runs) return fail(MI_ERR_BAD_ARG, "aees: null target / runs");
+    if (target->struct_size != sizeof(mi_target) || runs->struct_size != sizeof(mi_aees_runs))
+        return fail(MI_ERR_BAD_ARG, "struct_size mismatch (header / library version skew)");
+    const uint64_t d = target->d, P = runs->n_runs;
+    int rc = aees_check("aees", d, settings, aees);
+    if (rc) return rc;
+    if (P == 0) return fail(MI_ERR_BAD_ARG, "aees: n_runs must be positive");
+    if (!runs->initial_vals) return fail(MI_ERR_BAD_ARG, "aees: runs.initial_vals is required");
+    if (target->kind == MI_TARGET_NORMAL_MODEL)
+        return fail(MI_ERR_UNSUPPORTED, "aees: MI_TARGET_NORMAL_MODEL has no literal (one workgroup per run) evaluation, which the aees kernel is built on");
+    if (target->kind < MI_TARGET_GAUSS_ISO || target->kind > MI_TARGET_GAUSS_MIXTURE) return fail(MI_ERR_UNSUPPORTED, "aees: target kind %d not implemented", target->kind);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+
+    mi::AeesParams prm{};
+    AeesTables tb;
+    if ((rc = aees_tables(d, settings, aees, tb, prm))) return rc;
+    const uint64_t K = prm.K, n_keep = prm.n_keep;
+    prm.P = P; prm.run0 = runs->run0; prm.r_begin = 0; prm.r_end = P;
+    const bool host = runs->mem == MI_MEM_HOST;
+    DevBuf s_init, s_draws, s_fin, s_acc, s_ee;
+    prm.init = runs->initial_vals; prm.draws = runs->draws; prm.fin = runs->final_states; prm.n_acc = runs->n_accept; prm.n_ee = runs->n_ee_accept;
+    if (host) {                                             // runs in host memory are staged
+        HIP_TRY(s_init.alloc(d * P * 8));
+        HIP_TRY(hipMemcpyAsync(s_init.p, runs->initial_vals, d * P * 8, hipMemcpyHostToDevice, st));
+        prm.init = s_init.as<double>();
+        if (runs->draws) { HIP_TRY(s_draws.alloc(n_keep * d * P * 8)); prm.draws = s_draws.as<double>(); }
+        if (runs->final_states) { HIP_TRY(s_fin.alloc(K * d * P * 8)); prm.fin = s_fin.as<double>(); }
+        if (runs->n_accept) { HIP_TRY(s_acc.alloc(K * P * 8)); prm.n_acc = s_acc.as<uint64_t>(); }
+        if (runs->n_ee_accept) { HIP_TRY(s_ee.alloc(K * P * 8)); prm.n_ee = s_ee.as<uint64_t>(); }
+    }
+    DevBuf t_a, t_b, t_t;
+    if ((rc = lit_stage_target("aees", target, prm.lit.t, t_a, t_b, t_t, st, true))) return rc;
+    WsLease ws;
+    unsigned n_wg = 0;
+    if ((rc = aees_workspace(prm, P, st, ws, n_wg))) return rc;
+    if ((rc = launched("aees", mi::launch_aees_literal(prm, n_wg, st)))) return rc;
+    if (host) {
+        if (runs->draws) HIP_TRY(hipMemcpyAsync(runs->draws, prm.draws, n_keep * d * P * 8, hipMemcpyDeviceToHost, st));
+        if (runs->final_states) HIP_TRY(hipMemcpyAsync(runs->final_states, prm.fin, K * d * P * 8, hipMemcpyDeviceToHost, st));
+        if (runs->n_accept) HIP_TRY(hipMemcpyAsync(runs->n_accept, prm.n_acc, K * P * 8, hipMemcpyDeviceToHost, st));
+        if (runs->n_ee_accept) HIP_TRY(hipMemcpyAsync(runs->n_ee_accept, prm.n_ee, K * P * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                      // the tables above are freed on return
+    return MI_OK;
+}
+
+// one run on aees_literal_kernel with the HOST callback as target (LIT_CALLBACK): this thread serves the kernel's requests
+int aees_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data, const mi_settings* settings,
+                      const mi_aees_settings* aees, double* draws_out, double* final_states, uint64_t* n_accept, uint64_t* n_ee_accept)
+{
+    if (!initial_vals || !target_log_kernel) return fail(MI_ERR_BAD_ARG, "aees (callback): null initial_vals / callback");
+    int rc = aees_check("aees (callback)", d, settings, aees);
+    if (rc) return rc;
+    const uint64_t n_keep = settings->n_keep_draws, K = aees->temper_len + 1;
+    if (n_keep > 0 && !draws_out) return fail(MI_ERR_BAD_ARG, "aees (callback): draws_out is required");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    PinnedBuf ctl, val, xb, outb;
+    HIP_TRY(ctl.alloc(mi::lit::LIT_MB_WORDS * sizeof(uint32_t))); HIP_TRY(val.alloc(8)); HIP_TRY(xb.alloc(d * 8)); HIP_TRY(outb.alloc(d * 8));
+    std::memset(ctl.p, 0, mi::lit::LIT_MB_WORDS * sizeof(uint32_t));
+    mi::AeesParams prm{};
+    prm.lit.t.kind = mi::lit::LIT_CALLBACK; prm.lit.t.d = (uint32_t)d;
+    mi::lit::lit_orders(prm.lit.t);
+    mi::lit::LitMailbox& mb = prm.lit.t.mb;
+    mb.ctl = ctl.as<uint32_t>(); mb.value = val.as<double>(); mb.x = xb.as<double>(); mb.out = outb.as<double>();
+    mb.timeout_ticks = 60ull * 100000000ull;              // 60 s of the 100 MHz wall clock per request
+    AeesTables tb;
+    if ((rc = aees_tables(d, settings, aees, tb, prm))) return rc;
+    prm.lit_stride = mi::lit::lit_work_doubles((uint32_t)d, 0, false);
+    const size_t slot = mi::aees_slot_bytes(prm.d, prm.K, prm.S, prm.n_total);
+    const size_t work = mi::aees_work_doubles(prm.lit_stride, prm.d, prm.K);
+    DevBuf init, draws, fin, acc, ee, wk, hist;
+    HIP_TRY(init.alloc(d * 8)); HIP_TRY(draws.alloc(std::max<uint64_t>(n_keep, 1) * d * 8)); HIP_TRY(fin.alloc(K * d * 8));
+    HIP_TRY(acc.alloc(K * 8)); HIP_TRY(ee.alloc(K * 8)); HIP_TRY(wk.alloc(work * 8)); HIP_TRY(hist.alloc(std::max<size_t>(slot, 256)));
+    HIP_TRY(hipMemcpy(init.p, initial_vals, d * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());     // the kernel runs on its own NON-BLOCKING stream, which does not order itself behind the null stream's copies
+    prm.P = 1; prm.run0 = 0; prm.r_begin = 0; prm.r_end = 1;
+    prm.init = init.as<double>(); prm.draws = n_keep ? draws.as<double>() : nullptr; prm.fin = fin.as<double>();
+    prm.n_acc = acc.as<uint64_t>(); prm.n_ee = ee.as<uint64_t>();
+    prm.lit.work = wk.as<double>(); prm.lit.work_stride = work;
+    prm.hist = hist.as<char>(); prm.hist_stride = slot;
+    hipStream_t st = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    rc = launched("aees (callback)", mi::launch_aees_literal(prm, 1, st));
+    if (!rc) {
+        (void)serve_callbacks(mb, (uint32_t)d, target_log_kernel, target_data, nullptr, nullptr, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MI_ERR_HIP, "aees (callback): %s", hipGetErrorString(e));
+        else if (ctl.as<uint32_t>()[mi::lit::LIT_MB_ABORT] != 0u) rc = fail(MI_ERR_HIP, "aees (callback): the kernel gave up waiting for a callback (60 s)");
+    }
+    (void)hipStreamDestroy(st);
+    if (rc) return rc;
+    if (n_keep) HIP_TRY(hipMemcpy(draws_out, draws.p, n_keep * d * 8, hipMemcpyDeviceToHost));
+    if (final_states) HIP_TRY(hipMemcpy(final_states, fin.p, K * d * 8, hipMemcpyDeviceToHost));
+    if (n_accept) HIP_TRY(hipMemcpy(n_accept, acc.p, K * 8, hipMemcpyDeviceToHost));
+    if (n_ee_accept) HIP_TRY(hipMemcpy(n_ee_accept, ee.p, K * 8, hipMemcpyDeviceToHost));
     return MI_OK;
 }
 
@@ -2724,6 +2916,33 @@ int mi_mcmc_de_run_callback(const double* initial_vals, uint64_t d, mi_log_kerne
                             const mi_settings* settings, const mi_de_settings* de, double* draws_out, uint64_t* n_accept)
 {
     return mi::host::de_run_callback(initial_vals, d, target_log_kernel, target_data, settings, de, draws_out, n_accept);
+}
+
+// mcmc::aees (ref: src/aees.cpp:28-305) for many runs (aees.hpp)
+void mi_aees_settings_default(mi_aees_settings* s)
+{
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = sizeof(mi_aees_settings);        // aees_settings_t (mcmc_structs.hpp): n_initial 1000, par_scale 1, n_rings 5, ee_prob 0.1
+    s->n_initial_draws = 1000;
+    s->par_scale = 1.0;
+    s->cov_mat = nullptr;
+    s->n_rings = 5;
+    s->ee_prob_par = 0.10;
+    s->temper_vec = nullptr;
+    s->temper_len = 0;
+}
+
+int mi_mcmc_aees_run(const mi_target* target, const mi_settings* settings, const mi_aees_settings* aees, mi_aees_runs* runs, void* stream)
+{
+    return mi::host::aees_run(target, settings, aees, runs, static_cast<hipStream_t>(stream));
+}
+
+int mi_mcmc_aees_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb target_log_kernel, void* target_data,
+                              const mi_settings* settings, const mi_aees_settings* aees, double* draws_out, double* final_states,
+                              uint64_t* n_accept, uint64_t* n_ee_accept)
+{
+    return mi::host::aees_run_callback(initial_vals, d, target_log_kernel, target_data, settings, aees, draws_out, final_states, n_accept, n_ee_accept);
 }
 
 }  // extern "C"
