@@ -59,6 +59,9 @@ typedef enum mi_target_kind {
                                  * bounds / precond_mat (round 6): the state in HBM, two fp64 matrix products per gradient for all chains (gemm_samplers.hip);
                                  * hmc / mala there also with a diagonal or a DENSE precond_mat (dense: INV(M), CHOL_LOWER(M), M, INV(eps^2 M) as further products of the
                                  * same kernel, d <= 3840 and a workspace that fits the free device memory; otherwise the literal kernels);
+                                 * hmc (identity / diagonal precond_mat) and rwmh (no cov_mat) there also with vals_bound: the chains in the transformed space, the products at
+                                 * x = inv_transform(theta), J(theta) g in the product's epilogue (three more state vectors in the workspace; what does not fit the free device
+                                 * memory, bounds with a dense precond_mat or chains.mass_diag, bounded nuts: the literal kernels; bounded mala beyond d = 512: MI_ERR_UNSUPPORTED);
                                  * the same for MI_TARGET_GAUSS_DENSE beyond d = 512 (one product per gradient) */
     MI_TARGET_NORMAL_MODEL = 5, /* d = 2, vals = (mu, sigma), observations x_1..x_n in y[0..n_rows): the model of the reference's
                                  * example programs (/root/reference/examples/eigen/rmhmc_normal.cpp:44-106),

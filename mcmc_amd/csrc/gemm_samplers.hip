@@ -29,6 +29,15 @@
 //       MODE 7 (mala): u = Lc z; mean = x + (s2 t) / 2 (mala.cpp:123), proposal = mean + eps u (:159),
 //       MODE 8 (mala): t' = M g'; mean' = x' + (s2 t') / 2, xa = prev - mean', xb = prop - mean (dmvnorm.hpp:37 of both densities):
 //   L + 3 products per hmc draw next to the L gradients (2 L + 3 in all), 5 per mala draw next to the one.
+//   settings.vals_bound (hmc with the identity / a diagonal precond_mat, rwmh; hmc.cpp:84-95,107-122,134-136,211-218; rwmh.cpp:105-107,113,128): th / thw hold theta, the
+//   TRANSFORMED state, and the products are taken at x = inv_transform(theta), a state buffer of its own (xacc / xw[2], double-buffered like thw) that every kernel which
+//   moves theta writes next to it.  The Jacobian is diagonal, so the bounded half-kicks are epilogue modes of the gradient's product:
+//       MODE 10 (MODE 0 with bounds): p += (eps (J(theta) g)) / 2 twice (:114-122, `jacob_matrix * grad` as the fma chain it is: fma(J_ii, g_i, +0)), theta' = theta + eps (m_inv p),
+//               x' = inv_transform(theta') into the OTHER x buffer -- the next product's B operand,
+//       MODE 11 (MODE 1 with bounds): p += (eps (J(theta) g)) / 2, the RAW gradient (with respect to x) kept: log K(x) and the next draw's first kick are made of it.
+//   The tables (bounds type 1..4 of determine_bounds_type.hpp, lb, ub) are read once per 16-row block like m_inv; a block without a bounded dimension (a mask from the host)
+//   takes g as it is and x' = theta': no exp, no log.  The energies add log_jacobian(theta) (log_jacobian.hpp:25-58): the terms in parallel, the additions ONE chain over
+//   the bounded dimensions ascending.  Kept rows and the final state are the x buffer (:211-218): inv_transform of the accepted theta, the bits the product read.
 //   blockIdx -> tile: XCD-aware -- the row tiles of one chain tile run back to back on ONE XCD, so Theta's tile is read from HBM once and shared in that L2.
 //
 //   Per draw, next to the n_leap products: gemm_momentum_kernel (Philox + Box-Muller, one slot per thread, canonical slot <-> dimension map of
@@ -42,6 +51,7 @@
 
 #include "gemm_samplers.hpp"
 #include "det_math.hpp"
+#include "hmc_dense.hpp"          // box_transform, box_inv_transform, box_inv_jacobian, box_log_jacobian_term: the reference's element-wise maps, out of line
 
 #include <algorithm>
 #include <cstdio>
@@ -81,6 +91,13 @@ struct StepParams {
     const double* aux0;
     const double* aux1;
     double s2;
+    // settings.vals_bound.  MODE 10 / 11: pos = theta (the transformed state), Bm = xpos = inv_transform(theta); MODE 10: x_out = inv_transform(pos_out)
+    const double* xpos;
+    double* x_out;
+    const int* bt;           // [dK] bounds type 1..4, lower and upper bound per dimension (type 1, zeros in the padding)
+    const double* lb;
+    const double* ub;
+    const uint32_t* box_blocks;   // [dK / 16] nonzero: the 16-row block holds a bounded dimension
 };
 
 template <int MODE, int TGT>
@@ -194,6 +211,51 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void gemm_step_kernel(const 
                     prm.g_out[idx] = bv[r][ni] - mean_prop;
                     prm.pos_out[idx] = xv[r][ni] - mv[r][ni];
                 }
+        } else if constexpr (MODE == 10 || MODE == 11) {                  // a leapfrog step in the transformed space (hmc.cpp:107-122,171)
+            const bool boxed = prm.box_blocks[row0 >> 4] != 0u;            // (the same for the whole wave)
+            [[maybe_unused]] double pv[4][4], tv[4][4], xs[4][4], mi[4], lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {0.0, 0.0, 0.0, 0.0};
+            int bt[4] = {1, 1, 1, 1};
+            if constexpr (MODE == 10) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mi[r] = prm.m_inv[row0 + (size_t)(4 * r + j)];
+            }
+            if (boxed) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { const size_t i = row0 + (size_t)(4 * r + j); bt[r] = prm.bt[i]; lo[r] = prm.lb[i]; hi[r] = prm.ub[i]; }
+            }
+            // two batches of 8 elements per block (the plain modes take 16): theta rides next to the momentum and the calls below keep more alive
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int r = 2 * h; r < 2 * h + 2; ++r)
+#pragma unroll
+                    for (int ni = 0; ni < 4; ++ni) {
+                        pv[r][ni] = prm.pm[at(r, ni)]; tv[r][ni] = prm.pos[at(r, ni)];
+                        if constexpr (TGT == TGT_LOGISTIC) xs[r][ni] = prm.xpos[at(r, ni)];
+                    }
+#pragma unroll
+                for (int r = 2 * h; r < 2 * h + 2; ++r)
+#pragma unroll
+                    for (int ni = 0; ni < 4; ++ni) {
+                        const size_t idx = at(r, ni);
+                        const double v = acc[ti][ni][r];
+                        double g;
+                        if constexpr (TGT == TGT_DENSE) g = -v;            // grad log K at x: -(P x)
+                        else g = v - xs[r][ni];                            // X^T (y - sigmoid(eta)) - x
+                        double jg = g;                                     // an unbounded block: J = I
+                        if (boxed) jg = dfma(box_inv_jacobian(tv[r][ni], bt[r], lo[r], hi[r]), g, 0.0);     // :114-122
+                        double p = pv[r][ni];
+                        p = p + (eps * jg) / 2.0;                          // second half-step of this leapfrog step
+                        if constexpr (MODE == 11) { prm.pm[idx] = p; prm.g_out[idx] = g; }
+                        else {
+                            p = p + (eps * jg) / 2.0;                      // first half-step of the next one: same position, same gradient, same Jacobian
+                            prm.pm[idx] = p;
+                            const double tn = tv[r][ni] + eps * (mi[r] * p);     // :171
+                            prm.pos_out[idx] = tn;
+                            prm.x_out[idx] = boxed ? box_inv_transform(tn, bt[r], lo[r], hi[r]) : tn;       // :108 of the next step
+                        }
+                    }
+            }
         } else {
             [[maybe_unused]] double pv[4][4], xv[4][4], mi[4];
             if constexpr (MODE == 0) {
@@ -302,6 +364,16 @@ struct DrawParams {
     const double *xa, *sa, *xb, *sb;     // mala: prev - mean(prop), INV(Sigma) of it; prop - mean(prev), INV(Sigma) of it
 };
 
+// settings.vals_bound: what the bounded twins of the kernels below take next to DrawParams
+struct BoxParams {
+    const int* bt;           // [dK] bounds type 1..4 (1 in the padding)
+    const double* lb;
+    const double* ub;
+    const uint32_t* blocks;  // [dK / 16] nonzero: the 16-dimension block holds a bounded dimension
+    double* xacc;            // [dK][Cp] inv_transform of th: what the products read, the kept rows and the final state
+    double* xw;              // ... of thw
+};
+
 // theta ([d][C]) into the padded state, zeros elsewhere
 __global__ void gemm_load_kernel(const DrawParams prm)
 {
@@ -309,6 +381,20 @@ __global__ void gemm_load_kernel(const DrawParams prm)
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
         const size_t i = e / prm.Cp, c = e % prm.Cp;
         prm.th[e] = (i < prm.d && c < prm.C) ? prm.theta_in[i * prm.C + c] : 0.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *prm.draw_ctr = 0u;
+}
+
+// ... with bounds: the initial values through transform (hmc.cpp:134-136, rwmh.cpp:105-107), and the first x
+__global__ void gemm_load_box_kernel(const DrawParams prm, const BoxParams bx)
+{
+    const size_t n = (size_t)prm.dK * prm.Cp;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = e / prm.Cp, c = e % prm.Cp;
+        const bool in = i < prm.d && c < prm.C;
+        const double t = in ? box_transform(prm.theta_in[i * prm.C + c], bx.bt[i], bx.lb[i], bx.ub[i]) : 0.0;
+        prm.th[e] = t;
+        bx.xacc[e] = in ? box_inv_transform(t, bx.bt[i], bx.lb[i], bx.ub[i]) : 0.0;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *prm.draw_ctr = 0u;
 }
@@ -334,6 +420,25 @@ __global__ __launch_bounds__(256) void gemm_normals_kernel(const DrawParams prm)
         prm.thw[ia] = prm.th[ia] + prm.eps * z0;
         prm.thw[ib] = prm.th[ib] + prm.eps * z1;
     }
+}
+
+// ... rwmh with bounds: the proposal in the transformed space (rwmh.cpp:126) and x = inv_transform of it, where the target is evaluated (:128 with :84-95 of hmc.cpp)
+__global__ __launch_bounds__(256) void gemm_normals_box_kernel(const DrawParams prm, const BoxParams bx)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= prm.Cp) return;
+    const uint32_t slot = blockIdx.y;
+    const uint32_t da = 8u * (slot >> 2) + (slot & 3u), db = da + 4u;
+    const uint32_t draw = *prm.draw_ctr;
+    double z0 = 0.0, z1 = 0.0;
+    if (c < prm.C && da < prm.d) rng_normal_pair(prm.seed, prm.chain0 + c, draw + prm.draw0, slot, STREAM_NORMAL, z0, z1);
+    if (db >= prm.d) z1 = 0.0;
+    const size_t ia = (size_t)da * prm.Cp + c, ib = (size_t)db * prm.Cp + c;
+    const double ta = prm.th[ia] + prm.eps * z0, tb = prm.th[ib] + prm.eps * z1;
+    prm.thw[ia] = ta; prm.thw[ib] = tb;
+    const bool boxed = bx.blocks[da >> 4] != 0u;          // (da and db = da + 4 share a 16-dimension block)
+    bx.xw[ia] = boxed ? box_inv_transform(ta, bx.bt[da], bx.lb[da], bx.ub[da]) : ta;
+    bx.xw[ib] = boxed ? box_inv_transform(tb, bx.bt[db], bx.lb[db], bx.ub[db]) : tb;
 }
 
 // ... with a dense precond_mat: the normals as they are -- sqrt_precond_matrix z (hmc.cpp:158, mala.cpp:159) is a product.  A kernel of its own, the same slot <-> dimension
@@ -383,6 +488,28 @@ __device__ __forceinline__ double log_kernel_value(const DrawParams& prm, const 
     }
 }
 
+// log_jacobian(theta) (log_jacobian.hpp:25-58) of chain c: the terms of four dimensions at a time by the four class lanes of the chain, the additions ONE chain over the
+// bounded dimensions ascending (type-1 dimensions add nothing, not even a + 0.0), the same in all four lanes.  Every lane of the wave calls it.
+__device__ __forceinline__ double box_log_jacobian(const DrawParams& prm, const BoxParams& bx, const double* th, uint64_t c, int lane)
+{
+    const uint32_t j = (uint32_t)lane >> 4;
+    double lj = 0.0;
+    for (uint32_t b = 0; b < prm.dK / 16u; ++b) {
+        if (bx.blocks[b] == 0u) continue;
+#pragma unroll
+        for (uint32_t s = 0; s < 4u; ++s) {
+            const uint32_t i0 = 16u * b + 4u * s, i = i0 + j;
+            const double term = box_log_jacobian_term(th[(size_t)i * prm.Cp + c], bx.bt[i], bx.lb[i], bx.ub[i]);
+#pragma unroll
+            for (uint32_t g = 0; g < 4u; ++g) {
+                const double tg = __shfl(term, (lane & 15) + 16 * (int)g);
+                if (bx.bt[i0 + g] != 1) lj = lj + tg;
+            }
+        }
+    }
+    return lj;
+}
+
 // hmc: prev_K = p.p / 2 (hmc.cpp:160), the first half-step (:126) and the first drift (:171) of the draw; new_draw = prev_draw (:162)
 __global__ __launch_bounds__(256) void gemm_pre_kernel(const DrawParams prm)
 {
@@ -398,6 +525,29 @@ __global__ __launch_bounds__(256) void gemm_pre_kernel(const DrawParams prm)
         p = p + (prm.eps * prm.gacc[e]) / 2.0;
         prm.pm[e] = p;
         prm.thw[e] = prm.th[e] + prm.eps * (mi * p);         // :171
+    }
+    q = class_sum(q);
+    if (j == 0) prm.kprev[c] = q / 2.0;
+}
+
+// ... with bounds: the half-step takes J(theta) g (:114-122), the drift writes x = inv_transform(theta') next to theta'
+__global__ __launch_bounds__(256) void gemm_pre_box_kernel(const DrawParams prm, const BoxParams bx)
+{
+    const int lane = threadIdx.x & 63, j = lane >> 4;
+    const uint64_t c = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+    double q = 0.0;
+    for (uint32_t i = (uint32_t)j; i < prm.dK; i += 4u) {
+        const size_t e = (size_t)i * prm.Cp + c;
+        const bool boxed = bx.blocks[i >> 4] != 0u;
+        double p = prm.pm[e];
+        const double mi = prm.m_inv[i], t = prm.th[e], g = prm.gacc[e];
+        q = dfma(p, mi * p, q);                              // K = p . (Minv p) / 2 (:160)
+        const double jg = boxed ? dfma(box_inv_jacobian(t, bx.bt[i], bx.lb[i], bx.ub[i]), g, 0.0) : g;
+        p = p + (prm.eps * jg) / 2.0;
+        prm.pm[e] = p;
+        const double tn = t + prm.eps * (mi * p);            // :171
+        prm.thw[e] = tn;
+        bx.xw[e] = boxed ? box_inv_transform(tn, bx.bt[i], bx.lb[i], bx.ub[i]) : tn;
     }
     q = class_sum(q);
     if (j == 0) prm.kprev[c] = q / 2.0;
@@ -428,6 +578,16 @@ __global__ __launch_bounds__(256) void gemm_first_kernel(const DrawParams prm)
     const int lane = threadIdx.x & 63, j = lane >> 4;
     const uint64_t c = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
     const double first_lp = log_kernel_value<TGT>(prm, prm.th, prm.gacc, c, j);
+    if (j == 0) { prm.prevE[c] = (prm.algo == GEMM_HMC) ? -first_lp : first_lp; prm.nacc[c] = 0ull; }
+}
+// ... with bounds: box_log_kernel = log K(x) + log_jacobian(theta) (hmc.cpp:84-95)
+template <int TGT>
+__global__ __launch_bounds__(256) void gemm_first_box_kernel(const DrawParams prm, const BoxParams bx)
+{
+    const int lane = threadIdx.x & 63, j = lane >> 4;
+    const uint64_t c = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+    const double k = log_kernel_value<TGT>(prm, bx.xacc, prm.gacc, c, j);
+    const double first_lp = k + box_log_jacobian(prm, bx, prm.th, c, lane);
     if (j == 0) { prm.prevE[c] = (prm.algo == GEMM_HMC) ? -first_lp : first_lp; prm.nacc[c] = 0ull; }
 }
 
@@ -514,6 +674,63 @@ __global__ __launch_bounds__(256) void gemm_post_kernel(const DrawParams prm)
     }
 }
 
+// ... hmc (identity / diagonal precond_mat) and rwmh with bounds, a kernel of its own so that gemm_post_kernel stays as it is: the value is box_log_kernel = log K(x) +
+// log_jacobian(theta) (hmc.cpp:84-95) at the proposal's x and theta; x moves with theta, and it is x that leaves (the row through inv_transform, :211-218)
+template <int ALGO, int TGT>
+__global__ __launch_bounds__(256) void gemm_post_box_kernel(const DrawParams prm, const BoxParams bx)
+{
+    static_assert(ALGO == GEMM_HMC || ALGO == GEMM_RWMH, "bounds: hmc and rwmh");
+    const int lane = threadIdx.x & 63, j = lane >> 4;
+    const uint64_t c = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+    const bool live = c < prm.C;
+    const uint32_t draw = *prm.draw_ctr;
+    const double kv = log_kernel_value<TGT>(prm, bx.xw, prm.gprop, c, j);
+    const double lp = kv + box_log_jacobian(prm, bx, prm.thw, c, lane);
+    double qk = 0.0;
+    if constexpr (ALGO == GEMM_HMC) {
+#pragma unroll 4
+        for (uint32_t i = (uint32_t)j; i < prm.dK; i += 4u) { const double p = prm.pm[(size_t)i * prm.Cp + c]; qk = dfma(p, prm.m_inv[i] * p, qk); }      // :184
+    }
+    const double prevE = prm.prevE[c];
+    const double z = rng_uniform(prm.seed, prm.chain0 + (live ? c : 0), draw + prm.draw0, 0u);
+    bool accept, flag = false;
+    double newE;
+    if constexpr (ALGO == GEMM_HMC) {
+        qk = class_sum(qk);
+        const double prop_K = qk / 2.0;                            // :184
+        double prop_U = -lp;                                       // :178
+        const bool u_nf = !is_finite(prop_U);
+        if (u_nf) prop_U = INF;                                    // :180-182
+        flag = u_nf || !is_finite(prop_K);
+        const double x = -(prop_U + prop_K) + (prevE + prm.kprev[c]);
+        const double comp_val = (x < 0.01) ? x : 0.01;             // :188
+        accept = z < det_exp(comp_val);                            // :191
+        newE = prop_U;
+    } else {
+        double pl = lp;
+        if (!is_finite(pl)) pl = -INF;                             // rwmh.cpp:130-132
+        const double x = pl - prevE;
+        const double comp_val = (x < 0.0) ? x : 0.0;               // :136
+        accept = z < det_exp(comp_val);                            // :139
+        newE = pl;
+    }
+    const bool kept = draw >= prm.n_burnin;
+    if (j == 0) {
+        if (accept) prm.prevE[c] = newE;
+        if (accept && kept) prm.nacc[c] += 1ull;
+        if (flag && live && prm.nf_flag) { prm.nf_flag[c] = 1u; prm.nf_flag[prm.C] = 1u; }
+    }
+    double* out = (kept && prm.draws != nullptr && live) ? prm.draws + (size_t)(draw - prm.n_burnin) * prm.d * prm.C + c : nullptr;
+#pragma unroll 4
+    for (uint32_t i = (uint32_t)j; i < prm.dK; i += 4u) {
+        const size_t e = (size_t)i * prm.Cp + c;
+        double v;
+        if (accept) { v = bx.xw[e]; bx.xacc[e] = v; prm.th[e] = prm.thw[e]; prm.gacc[e] = prm.gprop[e]; }
+        else v = bx.xacc[e];
+        if (out != nullptr && i < prm.d) out[(size_t)i * prm.C] = v;
+    }
+}
+
 __global__ void gemm_advance_kernel(uint32_t* draw_ctr) { *draw_ctr += 1u; }
 
 // final state and accept counts of the chains that were not flagged (a flagged chain is replayed from theta, which must stay its initial state)
@@ -540,7 +757,8 @@ struct Layout {
     size_t n_doubles;
 };
 constexpr int DENSE_M_MATS = 3, DENSE_M_VECS = 4;     // hmc: CHOL_LOWER(M), INV(M); mala: M, CHOL_LOWER(M), INV(eps^2 M) | hmc: z, Minv p; mala: z / Sinv xa, t / Sinv xb, mean, xa (xb where hmc keeps p)
-static Layout layout_of(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass)
+constexpr int BOX_VECS = 3;                           // vals_bound: x at the accepted state and at the two proposal buffers
+static Layout layout_of(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass, bool bounded)
 {
     Layout l;
     l.dK = round_up(d, TK); l.dM = round_up(d, TM);
@@ -554,10 +772,12 @@ static Layout layout_of(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass
     l.n_doubles = l.mat + 6 * l.vec + 2 * l.rvec + 3 * l.Cp + 32;
     // ... | a dense precond_mat: its packed matrices [dK][dM] and the vectors of its products, behind everything else
     if (dense_mass) l.n_doubles += DENSE_M_MATS * (size_t)l.dK * l.dM + DENSE_M_VECS * l.vec;
+    // ... | vals_bound (never with a dense precond_mat on this route): the x buffers, in the same place
+    if (bounded) l.n_doubles += BOX_VECS * l.vec;
     return l;
 }
 uint32_t gemm_padded_d(uint32_t d) { return round_up(d, TK); }
-size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass) { return layout_of(d, n_rows, C, dense_mass).n_doubles * sizeof(double); }
+size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass, bool bounded) { return layout_of(d, n_rows, C, dense_mass, bounded).n_doubles * sizeof(double); }
 
 #define GEMM_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
@@ -579,8 +799,9 @@ template <int TGT>
 static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name)
 {
     constexpr bool LOGIT = TGT == TGT_LOGISTIC;
-    const bool dm = r.dense_mass;
-    const Layout l = layout_of(r.d, LOGIT ? r.n_rows : 0u, r.C, dm);
+    const bool dm = r.dense_mass, box = r.bounded;
+    if (box && (dm || r.algo == GEMM_MALA || !r.btype || !r.lb || !r.ub || !r.box_blocks)) return (int)hipErrorInvalidValue;     // (the caller routes these elsewhere)
+    const Layout l = layout_of(r.d, LOGIT ? r.n_rows : 0u, r.C, dm, box);
     double* base = static_cast<double*>(r.ws);
     double* A1 = base;                                        // dense: P^T; logistic: X^T [dK][nM]
     double* A2 = LOGIT ? A1 + (size_t)l.dK * l.nM : nullptr;  // logistic: X [nK][dM]
@@ -603,6 +824,9 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
         for (int i = 0; i < DENSE_M_MATS; ++i) Mm[i] = p0 + i * mmat;
         for (int i = 0; i < DENSE_M_VECS; ++i) ev[i] = p0 + DENSE_M_MATS * mmat + i * l.vec;
     }
+    double* xacc = nullptr;                                      // vals_bound: inv_transform of th / thw[0] / thw[1]
+    double* xw[2] = {nullptr, nullptr};
+    if (box) { double* p0 = kprev + 2 * l.Cp + 32; xacc = p0; xw[0] = p0 + l.vec; xw[1] = p0 + 2 * l.vec; }
     const bool hmc = r.algo == GEMM_HMC;
     const double *A_lc = hmc ? Mm[0] : Mm[1], *A_minv = Mm[1], *A_m = Mm[0], *A_sinv = Mm[2];
 
@@ -614,17 +838,22 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
     dp.eps = r.eps; dp.s2 = r.s2; dp.rs = r.rs; dp.log_det = r.log_det; dp.cons_term = r.cons_term;
     dp.dense_m = dm ? 1 : 0; dp.zb = ev[0];
     if (hmc) dp.mp = ev[1]; else { dp.xa = ev[3]; dp.sa = ev[0]; dp.xb = pm; dp.sb = ev[1]; }
+    BoxParams bp{};
+    bp.bt = r.btype; bp.lb = r.lb; bp.ub = r.ub; bp.blocks = r.box_blocks; bp.xacc = xacc; bp.xw = xw[0];
     dp.m = r.mass_tables; dp.m_sqrt = r.mass_tables + l.dK; dp.m_inv = r.mass_tables + 2 * (size_t)l.dK; dp.s_inv = r.mass_tables + 3 * (size_t)l.dK;
 
     static const int attr_rc = [] { int e = step_attr<0, TGT>(); if (!e) e = step_attr<1, TGT>(); if (!e) e = step_attr<2, TGT>(); if (!e) e = step_attr<6, TGT>();
                                      if (!e) e = step_attr<4, TGT_DENSE>(); if (!e) e = step_attr<5, TGT_DENSE>(); if (!e) e = step_attr<7, TGT_DENSE>(); if (!e) e = step_attr<8, TGT_DENSE>();
+                                     if (!e) e = step_attr<10, TGT>(); if (!e) e = step_attr<11, TGT>();
                                      if constexpr (LOGIT) { if (!e) e = step_attr<3, TGT>(); } return e; }();
     if (attr_rc) return attr_rc;
     const uint32_t n_ntiles = (uint32_t)(l.Cp / TN);
     // grad log K (and, logistic, the row terms) at `pos`; mode 0: a leapfrog step that is not the last (pos_out: the next position), 1: the last, 2: the gradient alone
-    auto evaluate = [&](const double* pos, int mode, double* pos_out, double* g_out, hipStream_t s) -> int {
+    // (vals_bound, modes 10 / 11: `pos` is x = inv_transform(theta), what the products read; theta, theta' and x' ride in th_pos / pos_out / x_out)
+    auto evaluate = [&](const double* pos, int mode, double* pos_out, double* g_out, hipStream_t s, const double* th_pos = nullptr, double* x_out = nullptr) -> int {
         StepParams sp{};
         sp.n_ntiles = n_ntiles; sp.Cp = l.Cp; sp.eps = r.eps; sp.pm = pm; sp.pos = pos; sp.pos_out = pos_out; sp.g_out = g_out; sp.m_inv = dp.m_inv;
+        if (mode >= 10) { sp.pos = th_pos; sp.xpos = pos; sp.x_out = x_out; sp.bt = r.btype; sp.lb = r.lb; sp.ub = r.ub; sp.box_blocks = r.box_blocks; }
         if constexpr (LOGIT) {
             StepParams se = sp;                               // eta = X Theta and the row terms
             se.At = A1; se.Bm = pos; se.Kp = l.dK; se.ldA = l.nM; se.M_store = l.nK; se.term_out = term;
@@ -634,6 +863,7 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
         } else {
             sp.At = A1; sp.Bm = pos; sp.Kp = l.dK; sp.ldA = l.dM; sp.M_store = l.dK;
         }
+        if (mode >= 10) return mode == 10 ? launch_step<10, TGT>(sp, s) : launch_step<11, TGT>(sp, s);
         return mode == 0 ? launch_step<0, TGT>(sp, s) : mode == 1 ? launch_step<1, TGT>(sp, s) : mode == 6 ? launch_step<6, TGT>(sp, s) : launch_step<2, TGT>(sp, s);
     };
     // a product with one of the packed mass matrices ([dK][dM], like P^T), B = `vec`; the epilogue of `mode` (4, 5, 7, 8: StepParams)
@@ -658,9 +888,15 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
         for (int i = 0; i < DENSE_M_MATS; ++i)
             if (src[i]) hipLaunchKernelGGL(gemm_pack_kernel<false>, pack_grid(mmat), dim3(256), 0, st, src[i], r.d, r.d, l.dK, l.dM, Mm[i]);
     }
-    hipLaunchKernelGGL(gemm_load_kernel, dim3(ew_grid), dim3(256), 0, st, dp);
-    if (int e = evaluate(th, 2, nullptr, gacc, st)) return e;          // the evaluation at the initial values
-    hipLaunchKernelGGL(gemm_first_kernel<TGT>, dim3(cls_grid), dim3(256), 0, st, dp);
+    if (box) {
+        hipLaunchKernelGGL(gemm_load_box_kernel, dim3(ew_grid), dim3(256), 0, st, dp, bp);
+        if (int e = evaluate(xacc, 2, nullptr, gacc, st)) return e;    // the evaluation at x = inv_transform(transform(the initial values)) (hmc.cpp:134-140)
+        hipLaunchKernelGGL(gemm_first_box_kernel<TGT>, dim3(cls_grid), dim3(256), 0, st, dp, bp);
+    } else {
+        hipLaunchKernelGGL(gemm_load_kernel, dim3(ew_grid), dim3(256), 0, st, dp);
+        if (int e = evaluate(th, 2, nullptr, gacc, st)) return e;      // the evaluation at the initial values
+        hipLaunchKernelGGL(gemm_first_kernel<TGT>, dim3(cls_grid), dim3(256), 0, st, dp);
+    }
     GEMM_TRY(hipGetLastError());
 
     const uint32_t n_total = r.n_burnin + r.n_keep;
@@ -669,9 +905,20 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
     auto enqueue_draw = [&](hipStream_t s) -> int {
         const dim3 normals_grid((unsigned)(l.Cp / 256 + (l.Cp % 256 ? 1 : 0)), l.dK / 2);
         if (dm) hipLaunchKernelGGL(gemm_normals_dense_m_kernel, normals_grid, dim3(256), 0, s, dp);
+        else if (box && !hmc) hipLaunchKernelGGL(gemm_normals_box_kernel, normals_grid, dim3(256), 0, s, dp, bp);
         else hipLaunchKernelGGL(gemm_normals_kernel, normals_grid, dim3(256), 0, s, dp);
         DrawParams pp = dp;
-        if (dm && hmc) {                                               // L + 3 products with the mass matrices next to the L gradients
+        if (box && hmc) {                                              // the same launches as the plain draw, every one the bounded twin
+            hipLaunchKernelGGL(gemm_pre_box_kernel, dim3(cls_grid), dim3(256), 0, s, dp, bp);
+            for (uint32_t k = 0; k < L; ++k)
+                if (int e = evaluate(xw[k & 1u], (k + 1 < L) ? 10 : 11, thw[(k + 1u) & 1u], gprop, s, thw[k & 1u], xw[(k + 1u) & 1u])) return e;
+            BoxParams bq = bp;
+            pp.thw = thw[(L - 1u) & 1u]; bq.xw = xw[(L - 1u) & 1u];
+            hipLaunchKernelGGL((gemm_post_box_kernel<GEMM_HMC, TGT>), dim3(cls_grid), dim3(256), 0, s, pp, bq);
+        } else if (box) {                                              // rwmh
+            if (int e = evaluate(xw[0], 2, nullptr, gprop, s)) return e;
+            hipLaunchKernelGGL((gemm_post_box_kernel<GEMM_RWMH, TGT>), dim3(cls_grid), dim3(256), 0, s, pp, bp);
+        } else if (dm && hmc) {                                               // L + 3 products with the mass matrices next to the L gradients
             if (int e = mass_product(A_lc, ev[0], 4, nullptr, nullptr, pm, nullptr, nullptr, s)) return e;            // p = Lc z (:158)
             if (int e = mass_product(A_minv, pm, 4, nullptr, nullptr, ev[1], nullptr, nullptr, s)) return e;          // Minv p (:160)
             hipLaunchKernelGGL(gemm_pre_dense_m_kernel, dim3(cls_grid), dim3(256), 0, s, dp);
@@ -732,12 +979,14 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
     if (!graphed)
         for (uint32_t t = 0; t < n_total; ++t) { if (int e = enqueue_draw(st)) return e; }
 
-    hipLaunchKernelGGL(gemm_store_kernel, dim3((unsigned)std::min<size_t>(((size_t)r.d * r.C + 255) / 256, 65535)), dim3(256), 0, st, dp);
+    DrawParams sp_out = dp;
+    if (box) sp_out.th = xacc;                                         // the final state leaves through inv_transform too: a continued call transforms it again, as the literal kernel does
+    hipLaunchKernelGGL(gemm_store_kernel, dim3((unsigned)std::min<size_t>(((size_t)r.d * r.C + 255) / 256, 65535)), dim3(256), 0, st, sp_out);
     GEMM_TRY(hipGetLastError());
     if (kernel_name) {
-        static thread_local char name[96];
-        snprintf(name, sizeof(name), "gemm_step_kernel<%d, %d> (%s%s)", r.algo == GEMM_HMC ? (L > 1 ? (dm ? 6 : 0) : 1) : 2, TGT,
-                 r.algo == GEMM_HMC ? "hmc" : r.algo == GEMM_MALA ? "mala" : "rwmh", graphed ? ", graph" : "");
+        static thread_local char name[112];
+        snprintf(name, sizeof(name), "gemm_step_kernel<%d, %d> (%s%s%s)", r.algo == GEMM_HMC ? (L > 1 ? (dm ? 6 : box ? 10 : 0) : box ? 11 : 1) : 2, TGT,
+                 r.algo == GEMM_HMC ? "hmc" : r.algo == GEMM_MALA ? "mala" : "rwmh", graphed ? ", graph" : "", box ? ", bounds" : "");
         if (r.diag_mass || dm) { const size_t n = strlen(name); snprintf(name + n - 1, sizeof(name) - n + 1, dm ? ", dense precond_mat)" : ", diagonal precond_mat)"); }
         *kernel_name = name;
     }

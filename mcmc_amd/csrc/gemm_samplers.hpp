@@ -35,12 +35,18 @@ struct GemmRun {
     // mala: M, CHOL_LOWER(M), INV(eps^2 M), with s2 / log_det / cons_term of it above; the mass tables are ones then
     bool dense_mass = false;
     const double *M_t = nullptr, *Lc_t = nullptr, *Minv_t = nullptr, *Sinv_t = nullptr;
-    void* ws = nullptr;               // gemm_ws_bytes(d, n_rows, C, dense_mass) bytes of device memory
+    // settings.vals_bound (hmc with the identity / a diagonal precond_mat, rwmh): the chains live in the transformed space, the products are taken at
+    // x = inv_transform(theta).  Device tables of gemm_padded_d(d) entries (type 1, bounds 0 in the padding) and, per 16-row block, whether it holds a bounded dimension
+    bool bounded = false;
+    const int* btype = nullptr;
+    const double *lb = nullptr, *ub = nullptr;
+    const uint32_t* box_blocks = nullptr;  // [gemm_padded_d(d) / 16]
+    void* ws = nullptr;               // gemm_ws_bytes(d, n_rows, C, dense_mass, bounded) bytes of device memory
     bool use_graph = true;            // replay the launches of one draw from a captured hipGraph (the draw index lives in device memory)
 };
 
 uint32_t gemm_padded_d(uint32_t d);
-size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass = false);      // n_rows = 0: the dense Gaussian
+size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass = false, bool bounded = false);      // n_rows = 0: the dense Gaussian
 // enqueues the whole run on `st`; returns a hipError_t as int (0 = enqueued).  *kernel_name: what ran, for mi_mcmc_last_kernel()
 int gemm_run(const GemmRun& r, hipStream_t st, const char** kernel_name);
 

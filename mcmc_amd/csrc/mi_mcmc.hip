@@ -998,7 +998,7 @@ int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_s
     return MI_OK;
 }
 
-// hmc / mala / rwmh on a dense Gaussian or the logistic-regression target BEYOND d = 512 (identity preconditioner / cov_mat, no bounds): the state of a
+// hmc / mala / rwmh on a dense Gaussian or the logistic-regression target BEYOND d = 512 (identity preconditioner / cov_mat; hmc and rwmh also with bounds): the state of a
 // 16-chain tile no longer fits a workgroup, so it lives in HBM and the gradients of ALL chains at one leapfrog step are fp64 matrix products on the matrix
 // cores -- W = P Theta, resp. eta = X Theta and X^T (y - sigmoid(eta)) -- with the half-kicks and the drift in the epilogue (gemm_samplers.hip); chains that
 // reach the non-finite regime are flagged and replayed by literal.hpp right behind it.  algo: the C ABI's numbers (0 hmc, 1 mala, 3 rwmh).
@@ -1016,10 +1016,28 @@ bool gemm_dense_mass_fits(const mi_target* target, const mi_chains* chains, hipS
     const size_t uploads = 4 * (size_t)d * d * sizeof(double) + ((size_t)1 << 20);      // the replay's transposed matrices (lit_upload) and the tables
     return rp.total_bytes + uploads <= free_b + ws_cached_bytes(st);      // (the cached workspace of this stream is given back before a larger one is taken)
 }
+// settings.vals_bound rides the route for hmc (identity / DIAGONAL precond_mat) and rwmh (no cov_mat): the chains live in the transformed space and three more state
+// vectors hold x = inv_transform(theta), what the products read.  Capacity is a routing condition here too: what does not fit stays on the literal kernel
+bool gemm_bounded_fits(const mi_target* target, const mi_chains* chains, bool replay, hipStream_t st)
+{
+    const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
+    if (d > 0x7fffffffULL || n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
+    const ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, false, true), C, (uint32_t)d, (uint32_t)(n ? n : d), false);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const size_t uploads = (size_t)d * d * sizeof(double) + ((size_t)1 << 20);      // (a host target's matrix and the tables)
+    return (replay ? rp.total_bytes : rp.own_bytes) + uploads <= free_b + ws_cached_bytes(st);
+}
 bool gemm_case(const mi_target* target, const mi_settings* settings, const mi_chains* chains, bool hmc, bool algo_has_mass = true, hipStream_t st = nullptr)
 {
-    if (!((target->kind == MI_TARGET_GAUSS_DENSE || target->kind == MI_TARGET_LOGISTIC) && target->d > 512 && !settings->vals_bound
+    if (!((target->kind == MI_TARGET_GAUSS_DENSE || target->kind == MI_TARGET_LOGISTIC) && target->d > 512
           && !chains->mass_diag && target->kernel_hint != MI_KERNEL_LITERAL && (!hmc || settings->n_leap_steps >= 1))) return false;
+    if (settings->vals_bound) {                          // hmc (identity / diagonal precond_mat) and rwmh (no cov_mat); bounded mala (its proposal covariance is J M per chain) stays literal
+        if (!hmc && algo_has_mass) return false;
+        if (settings->precond_mat && (!algo_has_mass || !precond_is_diagonal(settings, target->d))) return false;
+        if (!settings->lower_bounds || !settings->upper_bounds) return true;      // (run_gemm reports the missing arrays)
+        return gemm_bounded_fits(target, chains, hmc, st);
+    }
     if (!settings->precond_mat) return true;
     if (!algo_has_mass) return false;                    // rwmh with a cov_mat: the literal kernel
     return precond_is_diagonal(settings, target->d) || gemm_dense_mass_fits(target, chains, st);      // (hmc, mala) a DIAGONAL precond_mat, or a dense one that fits
@@ -1033,6 +1051,8 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     if (d > 0x7fffffffULL || n > 0x7fffffffULL) return fail(MI_ERR_BAD_ARG, "%s: d / n_rows out of range", who);
     if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
     if (algo == 0 && settings->n_leap_steps > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "hmc: too many leapfrog steps");
+    const bool bounded = settings->vals_bound != 0;
+    if (bounded && (!settings->lower_bounds || !settings->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
     DevBuf P_owned, Xo, yo;
     const double *P_dev = nullptr, *X_dev = nullptr, *y_dev = nullptr;
     if (logit) {
@@ -1060,9 +1080,27 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     // identity or a DIAGONAL precond_mat (hmc.cpp:57-59, mala.cpp:57-58 with mala.ipp:58-64): diag(M), CHOL_LOWER (sqrt), INV (reciprocal) and, mala, INV(eps^2 M) with
     // LOG_DET(eps^2 M) -- all from lit_prepare, in the oracle's operation order; the identity as tables of ones (1.0 * x is x bit for bit)
     mi::lit::LitPrep prep;
-    rc = mi::lit::lit_prepare(algo == 1 ? 1 : 0, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
+    rc = mi::lit::lit_prepare(algo == 1 ? 1 : 0, (uint32_t)d, settings->step_size, bounded ? 1 : 0, settings->lower_bounds, settings->upper_bounds, settings->precond_mat, prep);
     if (rc) return rc;
     const uint32_t dK = mi::gemm::gemm_padded_d((uint32_t)d);
+    // vals_bound: bounds type, lower and upper bound per dimension (determine_bounds_type.hpp:27-57, from lit_prepare) padded with type 1, and per 16-dimension block
+    // whether it holds a bounded dimension at all -- the others skip every exp / log
+    DevBuf box_dev;
+    if (bounded) {
+        const size_t off_lb = (size_t)dK * sizeof(int), off_ub = off_lb + (size_t)dK * 8, off_blk = off_ub + (size_t)dK * 8, bytes = off_blk + (size_t)(dK / 16) * sizeof(uint32_t);
+        std::vector<unsigned char> host(bytes, 0);
+        int* bt = reinterpret_cast<int*>(host.data());
+        double* lb = reinterpret_cast<double*>(host.data() + off_lb);
+        double* ub = reinterpret_cast<double*>(host.data() + off_ub);
+        uint32_t* blk = reinterpret_cast<uint32_t*>(host.data() + off_blk);
+        for (uint32_t i = 0; i < dK; ++i) bt[i] = 1;
+        for (uint64_t i = 0; i < d; ++i) { bt[i] = prep.bt[i]; lb[i] = prep.lb[i]; ub[i] = prep.ub[i]; if (bt[i] != 1) blk[i / 16] = 1u; }
+        HIP_TRY(box_dev.alloc(bytes));
+        HIP_TRY(hipMemcpy(box_dev.p, host.data(), bytes, hipMemcpyHostToDevice));
+        unsigned char* base = static_cast<unsigned char*>(box_dev.p);
+        g.bounded = true; g.btype = reinterpret_cast<const int*>(base); g.lb = reinterpret_cast<const double*>(base + off_lb);
+        g.ub = reinterpret_cast<const double*>(base + off_ub); g.box_blocks = reinterpret_cast<const uint32_t*>(base + off_blk);
+    }
     std::vector<double> tabs(4 * (size_t)dK, 1.0);
     if (algo == 1) {                                     // dmvnorm's constants for Sigma = eps^2 M, as the oracle states them
         g.s2 = settings->step_size * settings->step_size; g.rs = prep.rs; g.log_det = prep.log_det; g.cons_term = prep.cons_term;
@@ -1088,7 +1126,7 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     g.use_graph = ((double)d * (double)(logit ? 2 * n : d) + (g.dense_mass ? (algo == 0 ? 1.0 : 5.0) * (double)d * (double)d : 0.0)) * (double)C < 3.0e10;
     const bool replay = algo != 3;                       // rwmh forms no product with a vector that can be non-finite (rwmh.cpp:126)
     WsLease base;
-    ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, g.dense_mass), C, (uint32_t)d, (uint32_t)(logit ? n : d), false);
+    ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, g.dense_mass, bounded), C, (uint32_t)d, (uint32_t)(logit ? n : d), false);
     rc = ws_get(st, replay ? rp.total_bytes : rp.own_bytes, base);
     if (rc) return rc;
     if (replay) {
@@ -1109,6 +1147,7 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
         lit_common(lp, settings, &sc.dev, rp, false);
         lp.rs = g.rs; lp.log_det = g.log_det; lp.cons_term = g.cons_term;
         if (prep.precond == 1) { lp.precond = 1; lp.m = g.mass_tables; lp.m_sqrt = g.mass_tables + dK; lp.m_inv = g.mass_tables + 2 * (size_t)dK; lp.sinv_diag = g.mass_tables + 3 * (size_t)dK; }
+        if (bounded) { lp.vals_bound = 1; lp.btype = g.btype; lp.lb = g.lb; lp.ub = g.ub; }      // (the replay starts from theta, the untouched initial values: it transforms them itself)
         rc = launched("matrix-product sampler (literal replay)", mi::launch_literal(algo, lp, rp.n_wg, st));
         if (rc) return rc;
     }
@@ -2508,7 +2547,7 @@ int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_ch
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t d = target->d;
     if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("rwmh", 3, target, settings, chains, st);
-    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, false)) return run_gemm("rwmh", 3, target, settings, chains, st);    // d > 512, plain
+    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);    // d > 512, plain or with bounds
     if (target->kind == MI_TARGET_LOGISTIC) {
         if (settings->vals_bound || settings->precond_mat)
             return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("rwmh", 3, target, settings, chains, st) : run_literal("rwmh", 3, target, settings, chains, st);
@@ -2518,7 +2557,7 @@ int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_ch
         return fail(MI_ERR_UNSUPPORTED, "rwmh: target kind %d not implemented", target->kind);
     if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !settings->vals_bound && !settings->precond_mat)
         return run_dense_lds("rwmh", mi::LOGIT_RWMH, target, settings, chains, st);     // P streamed through LDS (logistic_lds.hpp)
-    if (gemm_case(target, settings, chains, false, false)) return run_gemm("rwmh", 3, target, settings, chains, st);
+    if (gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);
     if (d > 128) return run_literal("rwmh", 3, target, settings, chains, st);      // no other tiled kernel beyond d = 128: literal.hpp
 
     DevBuf P_owned;

@@ -1,0 +1,94 @@
+"""Randomised sweep of the matrix-product samplers with settings.vals_bound (mcmc_amd/csrc/gemm_samplers.hip: hmc with the identity / a diagonal precond_mat and rwmh
+beyond d = 512, dense Gaussians and the logistic target; the products at x = inv_transform(theta), J(theta) g in their epilogue) against the literal kernels of the same
+library (MI_KERNEL_LITERAL: one workgroup per chain, the reference's operations as written, pinned against the oracle by tests/test_gpu_literal_paths.py and the CPU
+suite) -- both run on the GPU: ragged d and N, ragged chain tiles, 0 .. many draws, one .. several leapfrog steps, step sizes from tiny to absurd, random bound patterns
+(none / lower / upper / both per dimension, whole 16-dimension blocks left free, bounds at +-1e300, lb = ub - tiny), chains that start in the non-finite regime or
+outside the bounds, chain0 / draw0 offsets, runs cut in two.  Bit-exact or report.
+Usage (GPU box): python tests/fuzz_gemm_bounds.py [n_cases] [seed]"""
+import os, sys
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np
+import mcmc_amd
+from mcmc_amd import synth
+
+
+def random_bounds(rng, d):
+    lo, hi = np.full(d, -np.inf), np.full(d, np.inf)
+    style = str(rng.choice(["sparse", "quarter", "all4", "none", "mixed"]))
+    p_bounded = dict(sparse=0.02, quarter=0.25, all4=1.0, none=0.0, mixed=0.6)[style]
+    t = np.where(rng.random(d) < p_bounded, 4 if style == "all4" else rng.integers(2, 5, d), 1)
+    if style in ("quarter", "mixed"):      # whole 16-dimension blocks without a bound: the epilogue skips them
+        for b in range(0, d, 16):
+            if rng.random() < 0.3: t[b:b + 16] = 1
+    lo[(t == 2) | (t == 4)] = -1.5
+    hi[(t == 3) | (t == 4)] = 2.0
+    for i in rng.choice(d, size=6, replace=False):      # odd ones
+        k = int(rng.integers(0, 4))
+        if k == 0: lo[i], hi[i] = -1e300, 1e300
+        elif k == 1: lo[i], hi[i] = -1e300, np.inf
+        elif k == 2: lo[i], hi[i] = 0.25 - 1e-9, 0.25
+        else: lo[i], hi[i] = -np.inf, 1e300
+    return style, lo, hi
+
+
+def sweep(n_cases=30, seed=1, verbose=True):
+    rng = np.random.default_rng(seed)
+    fails = 0
+    for case in range(n_cases):
+        algo = str(rng.choice(["hmc", "hmc", "rwmh"]))
+        kind = str(rng.choice(["logistic", "dense"]))
+        d = int(rng.integers(513, 1401))
+        if kind == "logistic":
+            n_rows = int(rng.choice([1, 7, 16, 17, 100, 128, 129, 300]))
+            X, y = synth.logistic_problem(d, n_rows, seed=int(rng.integers(1, 99)))
+            tk, tkw, scale = mcmc_amd.TARGET_LOGISTIC, dict(X=X, y=y), 0.1
+        else:
+            n_rows = 0
+            tk, tkw, scale = mcmc_amd.TARGET_GAUSS_DENSE, dict(prec=synth.dense_gaussian_precision(d, seed=int(rng.integers(1, 99)))), 0.5
+        C = int(rng.choice([1, 5, 16, 64, 127, 128, 129, 200, 300]))
+        burn, keep = int(rng.integers(0, 5)), int(rng.integers(0, 5))
+        if burn + keep == 0: keep = 1
+        L = int(rng.choice([1, 2, 3, 5]))
+        eps = float(rng.choice([0.002, 0.02, 0.05, 0.1, 0.3, 1.0, 1e5]))
+        style, lo, hi = random_bounds(rng, d)
+        init = synth.initial_states(C, d, seed=int(rng.integers(1, 1000))) * scale
+        if rng.random() < 0.7: init = np.clip(init, -1.0, 1.5)      # (else some start outside their bounds: log of a negative number, NaN from the first transform on)
+        wild = rng.random() < 0.3
+        if wild:      # a poisoned chain or three
+            for c in rng.choice(C, size=min(C, 3), replace=False):
+                init[c] *= float(rng.choice([1e150, 1e300]))
+                if rng.random() < 0.5: init[c, int(rng.integers(0, d))] = float(rng.choice([np.inf, -np.inf, np.nan]))
+        sd = int(rng.integers(1, 10**6))
+        chain0, draw0 = int(rng.integers(0, 5000)), int(rng.choice([0, 0, 3]))
+        M = np.diag(rng.uniform(0.5, 2.0, d)) if (algo == "hmc" and rng.random() < 0.4) else None
+        S = lambda b, k: mcmc_amd.default_settings(rng_seed_value=sd, n_burnin_draws=b, n_keep_draws=k, n_leap_steps=L, step_size=eps, precond_mat=M,
+                                                   vals_bound=1, lower_bounds=lo, upper_bounds=hi)
+        a_draws, a = mcmc_amd.sample(algo, tk, init, S(burn, keep), chain0=chain0, draw0=draw0, **tkw)
+        kernel = mcmc_amd.last_kernel()
+        b_draws, b = mcmc_amd.sample(algo, tk, init, S(burn, keep), chain0=chain0, draw0=draw0, kernel_hint=mcmc_amd.KERNEL_LITERAL, **tkw)
+        bits = lambda v: np.ascontiguousarray(v, dtype=np.float64).view(np.uint64)
+        same = lambda u, v: np.array_equal(bits(u), bits(v)) or np.array_equal(u, v, equal_nan=True)     # (NaN payloads may differ)
+        ok = (kernel.startswith("gemm_step_kernel<") and "bounds" in kernel and ("diagonal precond_mat" in kernel) == (M is not None)
+              and mcmc_amd.last_kernel().startswith("literal_kernel<")
+              and same(a_draws, b_draws) and np.array_equal(a["n_accept"], b["n_accept"]) and same(a["theta"], b["theta"]) and np.array_equal(a["n_leap"], b["n_leap"]))
+        cut = None
+        if ok and not wild and burn == 0 and keep >= 2 and draw0 == 0:       # the same run cut in two, on both kernels (the state re-enters through transform)
+            cut = int(rng.integers(1, keep))
+            p_draws, p = mcmc_amd.sample(algo, tk, init, S(0, cut), chain0=chain0, **tkw)
+            q_draws, q = mcmc_amd.sample(algo, tk, p["theta"].T.copy(), S(0, keep - cut), chain0=chain0, draw0=cut, **tkw)
+            r_draws, r = mcmc_amd.sample(algo, tk, p["theta"].T.copy(), S(0, keep - cut), chain0=chain0, draw0=cut, kernel_hint=mcmc_amd.KERNEL_LITERAL, **tkw)
+            ok = same(p_draws, a_draws[:cut]) and same(q_draws, r_draws) and np.array_equal(q["n_accept"], r["n_accept"]) and same(q["theta"], r["theta"])
+        if verbose or not ok:
+            print(("ok  " if ok else "FAIL"), dict(algo=algo, kind=kind, d=d, n_rows=n_rows, C=C, burn=burn, keep=keep, L=L, eps=eps, bounds=style, diag=M is not None, chain0=chain0,
+                                                   draw0=draw0, wild=wild, cut=cut, seed=sd, kernel=kernel, acc=int(a["n_accept"].sum())), flush=True)
+        fails += 0 if ok else 1
+    return fails
+
+
+if __name__ == "__main__":
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+    s = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+    f = sweep(n, s)
+    print("mismatching cases:", f)
+    sys.exit(1 if f else 0)
