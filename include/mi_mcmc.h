@@ -449,6 +449,10 @@ int mi_mcmc_aees_run_callback(const double* initial_vals, uint64_t d, mi_log_ker
  * it.  A, Ainv, L: HOST memory, d x d row-major; A's lower triangle is what CHOL_LOWER reads, L is zero above the diagonal.  d >= 64 runs on
  * the device (one cooperative launch: d pivot / column steps of a parallel update, mcmc_amd/csrc/linalg_device.hip), smaller matrices on the
  * calling thread; no input validation, as in the reference (a singular / non-SPD matrix gives inf / NaN entries, not an error).  Blocking.
+ * No limit on d: the device kernels stage the scaled pivot row (INV: 2 d doubles) resp. the finished column (CHOL_LOWER: d doubles) in 60 KB of
+ * LDS; a matrix beyond that -- d > 3840 for INV, d > 7680 for CHOL_LOWER -- runs the same statements on the calling thread (one host core, O(d^3):
+ * 89 ms measured at d = 512, which extrapolates to roughly 40 s at d = 4000 -- not measured) and returns the same bits, never MI_ERR_UNSUPPORTED.  For the samplers the same edge is a routing condition: hmc /
+ * mala with a dense precond_mat beyond d = 3840 run on the literal kernels (MI_TARGET_LOGISTIC above), whose preparation factorises on the host.
  * (ABI 0x000600.  Every sampler call with a dense precond_mat goes through these.) */
 int mi_mcmc_mat_inverse(const double* A, uint64_t d, double* Ainv);
 int mi_mcmc_mat_cholesky_lower(const double* A, uint64_t d, double* L);

@@ -255,6 +255,26 @@ def test_set_grid_cap(max_workgroups):
     lib().mi_mcmc_test_set_grid_cap(C.c_uint32(int(max_workgroups)))
 
 
+def test_set_linalg_stage_bytes(n_bytes):
+    """mi_mcmc_test_set_linalg_stage_bytes (TEST HOOK, mi_mcmc_probes.h): the staging budget of the device INV (2 d doubles) / CHOL_LOWER (d doubles)
+    in bytes, beyond which a matrix runs the host loops; 0 = the real budget (60 KB of LDS).  Empties the memoised factorisations."""
+    lib().mi_mcmc_test_set_linalg_stage_bytes(C.c_uint32(int(n_bytes)))
+
+
+def test_linalg_computed():
+    """mi_mcmc_test_linalg_computed (TEST HOOK, mi_mcmc_probes.h): INV / CHOL_LOWER factorisations computed so far, i.e. not answered by the memo."""
+    f = lib().mi_mcmc_test_linalg_computed
+    f.restype = C.c_uint64
+    return int(f())
+
+
+def test_linalg_computed_on_device():
+    """mi_mcmc_test_linalg_computed_on_device (TEST HOOK, mi_mcmc_probes.h): ... those of them that ran the device kernels, not the host loops."""
+    f = lib().mi_mcmc_test_linalg_computed_on_device
+    f.restype = C.c_uint64
+    return int(f())
+
+
 def last_kernel():
     """mi_mcmc_last_kernel: the kernel this thread's last run spent its time in, as rocprofv3 names it."""
     return lib().mi_mcmc_last_kernel().decode()

@@ -3,11 +3,15 @@
 // loops, and the switch to their device form (linalg_device.hip) that the product installs.
 #pragma once
 
+#include <atomic>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
 #include <utility>
 #include <vector>
+
+#include "linalg_stage.hpp"
 
 namespace {
 
@@ -53,23 +57,56 @@ inline void host_inverse_compute(const double* A, size_t d, std::vector<double>&
 // element, hence the same bits, as one cooperative launch instead of 89 ms / 40 ms of one host core at d = 512) for d >= min_d; a translation
 // unit that installs nothing (the host test shim tests/lit_host.hip) runs the loops above.  A device failure is an ERROR (the status is returned
 // and mi_mcmc_last_error says why), never a silent switch to the host loops.
+//
+// CAPACITY is a routing condition, not an error: the device kernels stage the scaled pivot row of the working copy and of the inverse (INV:
+// 2 d doubles), resp. the finished column (CHOL_LOWER: d doubles), in LDS.  A matrix whose staging exceeds the budget -- LINALG_STAGE_BYTES:
+// d > 3840 for INV, d > 7680 for CHOL_LOWER -- runs the host loops of this file: the same statements, the same bits, one host core (as every such
+// call ran before the device kernels existed).  TEST HOOK (mi_mcmc_test_set_linalg_stage_bytes, mi_mcmc_probes.h): a smaller budget for this
+// process, so that the routing runs at sizes where the oracle costs milliseconds; every change of it starts a new epoch, and a memo of
+// another epoch is emptied before it is read (a result computed under one setting never answers a call under the other).
 struct LinalgAccel {
     int (*inverse)(const double* A, size_t d, double* Ainv) = nullptr;
     int (*cholesky_lower)(const double* A, size_t d, double* L) = nullptr;
     size_t min_d = 64;           // below: the host loops (microseconds, and no launch)
+    std::atomic<size_t> stage_bytes{LINALG_STAGE_BYTES};
+    std::atomic<uint64_t> epoch{0};
+    std::atomic<uint64_t> n_computed{0};          // factorisations computed (device or host loops), i.e. not answered by the memo: what a test of the memo reads
+    std::atomic<uint64_t> n_on_device{0};         // ... those of them that ran the installed device implementation: what a test of the routing reads
 };
 inline LinalgAccel& linalg_accel() { static LinalgAccel a; return a; }
+inline void linalg_set_stage_bytes(size_t bytes)          // 0, or more than the LDS holds: the real budget
+{
+    LinalgAccel& a = linalg_accel();
+    a.stage_bytes.store(bytes == 0 || bytes > LINALG_STAGE_BYTES ? LINALG_STAGE_BYTES : bytes, std::memory_order_relaxed);
+    a.epoch.fetch_add(1, std::memory_order_relaxed);
+}
+// which: 0 INV, 1 CHOL_LOWER -- does a d x d matrix run on the installed device implementation?
+inline bool linalg_on_device(int which, size_t d)
+{
+    const LinalgAccel& a = linalg_accel();
+    if ((which == 0 ? a.inverse == nullptr : a.cholesky_lower == nullptr) || d < a.min_d) return false;
+    return (which == 0 ? 2 : 1) * d * sizeof(double) <= a.stage_bytes.load(std::memory_order_relaxed);
+}
 
 // INV behind a two-entry memo keyed by the matrix itself: one sampler call asks for the same inverse more than once (its own and the literal
 // replay's preparation; mala: INV(M) and INV(eps^2 M)), as do the calls of a run cut into pieces (checkpoint / resume) -- a deterministic function
 // of its input, so the copy has the bits of a recomputation.  Per thread; small matrices are not kept; mi_mcmc_release_workspace empties it.
 struct LinalgMemoEntry { std::vector<double> key, val; };
-struct LinalgMemo { LinalgMemoEntry e[2]; int last = 0; };
-inline LinalgMemo& linalg_memo(int which) { static thread_local LinalgMemo m[2]; return m[which]; }      // 0: INV, 1: CHOL_LOWER
+struct LinalgMemo { LinalgMemoEntry e[2]; int last = 0; uint64_t epoch = 0; };
+inline LinalgMemo& linalg_memo_raw(int which) { static thread_local LinalgMemo m[2]; return m[which]; }      // 0: INV, 1: CHOL_LOWER
 inline void linalg_memo_clear()
 {
     for (int w = 0; w < 2; ++w)
-        for (auto& e : linalg_memo(w).e) { std::vector<double>().swap(e.key); std::vector<double>().swap(e.val); }
+        for (auto& e : linalg_memo_raw(w).e) { std::vector<double>().swap(e.key); std::vector<double>().swap(e.val); }
+}
+inline LinalgMemo& linalg_memo(int which)                // ... of the current staging-budget epoch
+{
+    const uint64_t now = linalg_accel().epoch.load(std::memory_order_relaxed);
+    if (linalg_memo_raw(which).epoch != now) {
+        linalg_memo_clear();
+        linalg_memo_raw(0).epoch = linalg_memo_raw(1).epoch = now;
+    }
+    return linalg_memo_raw(which);
 }
 inline bool linalg_memo_find(int which, const double* A, size_t n, std::vector<double>& out)
 {
@@ -91,10 +128,11 @@ inline int host_inverse(const double* A, size_t d, std::vector<double>& Ainv)
 {
     const size_t n = d * d;
     if (d >= 64 && linalg_memo_find(0, A, n, Ainv)) return 0;
-    const LinalgAccel& acc = linalg_accel();
-    if (acc.inverse != nullptr && d >= acc.min_d) {
+    linalg_accel().n_computed.fetch_add(1, std::memory_order_relaxed);
+    if (linalg_on_device(0, d)) {
+        linalg_accel().n_on_device.fetch_add(1, std::memory_order_relaxed);
         Ainv.assign(n, 0.0);
-        const int rc = acc.inverse(A, d, Ainv.data());
+        const int rc = linalg_accel().inverse(A, d, Ainv.data());
         if (rc != 0) return rc;
     } else {
         host_inverse_compute(A, d, Ainv);
@@ -107,9 +145,10 @@ inline int host_cholesky_lower(const double* A, size_t d, std::vector<double>& L
 {
     if (d >= 64 && linalg_memo_find(1, A, d * d, L)) return 0;
     L.assign(d * d, 0.0);
-    const LinalgAccel& acc = linalg_accel();
-    if (acc.cholesky_lower != nullptr && d >= acc.min_d) {
-        const int rc = acc.cholesky_lower(A, d, L.data());
+    linalg_accel().n_computed.fetch_add(1, std::memory_order_relaxed);
+    if (linalg_on_device(1, d)) {
+        linalg_accel().n_on_device.fetch_add(1, std::memory_order_relaxed);
+        const int rc = linalg_accel().cholesky_lower(A, d, L.data());
         if (rc == 0) linalg_memo_keep(1, A, d * d, L);
         return rc;
     }

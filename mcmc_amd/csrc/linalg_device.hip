@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "host_common.hpp"
+#include "linalg_stage.hpp"
 
 namespace cg = cooperative_groups;
 
@@ -191,7 +192,7 @@ int inverse_impl(const double* A, size_t d, double* Ainv, uint32_t grid_cap, LaT
 {
     const size_t n = d * d, lds = 2 * d * sizeof(double);
     if (d == 0) return MI_OK;
-    if (lds > 60 * 1024) return host::fail(MI_ERR_UNSUPPORTED, "device_inverse: d = %zu is beyond the LDS-staged pivot row (d <= 3840)", d);
+    if (lds > LINALG_STAGE_BYTES) return host::fail(MI_ERR_BAD_ARG, "device_inverse: d = %zu is beyond the LDS-staged pivot row (host_inverse routes it to the host loops)", d);
     uint32_t grid = 1;
     const void* kern = reinterpret_cast<const void*>(gj_inverse_kernel<CG>);
     int rc = coop_grid(kern, lds, (uint32_t)d, grid_cap, grid); if (rc) return rc;
@@ -218,7 +219,7 @@ int cholesky_impl(const double* A, size_t d, double* L, uint32_t grid_cap, LaTim
 {
     const size_t n = d * d, lds = d * sizeof(double);
     if (d == 0) return MI_OK;
-    if (lds > 60 * 1024) return host::fail(MI_ERR_UNSUPPORTED, "device_cholesky_lower: d = %zu is beyond the LDS-staged column (d <= 7680)", d);
+    if (lds > LINALG_STAGE_BYTES) return host::fail(MI_ERR_BAD_ARG, "device_cholesky_lower: d = %zu is beyond the LDS-staged column (host_cholesky_lower routes it to the host loops)", d);
     uint32_t grid = 1;
     const void* kern = reinterpret_cast<const void*>(chol_lower_kernel<CG>);
     int rc = coop_grid(kern, lds, (uint32_t)d, grid_cap, grid); if (rc) return rc;

@@ -84,6 +84,10 @@ namespace { void snapshot_grid_cap() { t_grid_cap = g_test_grid_cap.load(std::me
 
 // test hook, declared in mi_mcmc_probes.h (not in the product header): see launch_common.hpp
 extern "C" void mi_mcmc_test_set_grid_cap(uint32_t max_workgroups) { mi::g_test_grid_cap.store(max_workgroups, std::memory_order_relaxed); }
+// test hook, declared in mi_mcmc_probes.h: the staging budget of the device INV / CHOL_LOWER (host_linalg.hpp)
+extern "C" void mi_mcmc_test_set_linalg_stage_bytes(uint32_t bytes) { linalg_set_stage_bytes(bytes); }
+extern "C" uint64_t mi_mcmc_test_linalg_computed(void) { return linalg_accel().n_computed.load(std::memory_order_relaxed); }
+extern "C" uint64_t mi_mcmc_test_linalg_computed_on_device(void) { return linalg_accel().n_on_device.load(std::memory_order_relaxed); }
 
 namespace {
 
@@ -1005,11 +1009,11 @@ int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_s
 // A DENSE precond_mat (hmc, mala) rides the same route -- products with INV(M), CHOL_LOWER(M), M, INV(eps^2 M) next to the gradient's -- where the route can hold it:
 // what it cannot (a matrix beyond the device factorisations of linalg_device.hip, a launch grid out of range, a workspace -- three more packed matrices, four more
 // state vectors -- beyond the free device memory) stays on the literal kernel, as before
-constexpr uint64_t GEMM_DENSE_M_MAX_D = 3840;            // device_inverse's LDS-staged pivot row
+constexpr uint64_t GEMM_DENSE_M_MAX_D = LINALG_STAGE_BYTES / (2 * sizeof(double));      // 3840: device_inverse's LDS-staged pivot row ...
 bool gemm_dense_mass_fits(const mi_target* target, const mi_chains* chains, hipStream_t st)
 {
     const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
-    if (d > GEMM_DENSE_M_MAX_D || n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
+    if (d > GEMM_DENSE_M_MAX_D || !linalg_on_device(0, (size_t)d) || n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
     const ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, true), C, (uint32_t)d, (uint32_t)(n ? n : d), false);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -1865,7 +1869,7 @@ int mi_mcmc_run_user_target_v(int algo, uint64_t d, mi_small_launch_fn launch, c
 int mi_mcmc_mat_inverse(const double* A, uint64_t d, double* Ainv)
 {
     if (!A || !Ainv) return fail(MI_ERR_BAD_ARG, "mat_inverse: NULL matrix");
-    if (d >= linalg_accel().min_d && mi_mcmc_device_count() < 1) return fail(MI_ERR_NO_DEVICE, "mat_inverse: no GPU visible (d >= 64 runs on the device)");
+    if (linalg_on_device(0, (size_t)d) && mi_mcmc_device_count() < 1) return fail(MI_ERR_NO_DEVICE, "mat_inverse: no GPU visible (d >= 64 runs on the device)");
     std::vector<double> out;
     const int rc = host_inverse(A, (size_t)d, out);
     if (rc) return rc;
@@ -1876,7 +1880,7 @@ int mi_mcmc_mat_inverse(const double* A, uint64_t d, double* Ainv)
 int mi_mcmc_mat_cholesky_lower(const double* A, uint64_t d, double* L)
 {
     if (!A || !L) return fail(MI_ERR_BAD_ARG, "mat_cholesky_lower: NULL matrix");
-    if (d >= linalg_accel().min_d && mi_mcmc_device_count() < 1) return fail(MI_ERR_NO_DEVICE, "mat_cholesky_lower: no GPU visible (d >= 64 runs on the device)");
+    if (linalg_on_device(1, (size_t)d) && mi_mcmc_device_count() < 1) return fail(MI_ERR_NO_DEVICE, "mat_cholesky_lower: no GPU visible (d >= 64 runs on the device)");
     std::vector<double> out;
     const int rc = host_cholesky_lower(A, (size_t)d, out);
     if (rc) return rc;

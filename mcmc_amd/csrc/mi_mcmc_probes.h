@@ -16,6 +16,18 @@ int mi_probe_mfma_cycles(int waves_per_simd, int use_lds, int iters, double* cyc
  * the NUTS kernels with dynamic chain hand-out (nuts_memo.hpp, nuts_lds.hpp) to max_workgroups (0 = no limit), so that a test with a
  * few hundred chains runs the global counter, slot re-use and retire-on-leave.  Process-wide.  Results do not depend on it. */
 void mi_mcmc_test_set_grid_cap(uint32_t max_workgroups);
+/* Defined in libmi_mcmc.so itself (a test hook like the one above): lowers the staging budget of the device INV / CHOL_LOWER of a dense precond_mat
+ * (host_linalg.hpp, linalg_device.hip: 2 d doubles for INV, d for CHOL_LOWER, 60 KB of LDS) to `bytes` (0, or more than the real budget = the real
+ * budget), so that a test at d of a few hundred runs what a matrix beyond d = 3840 / 7680 runs: the host loops instead of the device kernels,
+ * and, for hmc / mala beyond d = 512, the literal kernel instead of the matrix-product route.  Process-wide; every call empties the memoised
+ * factorisations (each thread's at its next use).  Results do not depend on it. */
+void mi_mcmc_test_set_linalg_stage_bytes(uint32_t bytes);
+/* ... and the number of INV / CHOL_LOWER factorisations this process has COMPUTED so far (on the device or in the host loops), i.e. those the two-entry
+ * memo did not answer: what a test of the memo's hits, evictions and emptying reads.  Process-wide, monotonic. */
+uint64_t mi_mcmc_test_linalg_computed(void);
+/* ... and how many of those ran the device kernels (the others: the host loops -- d < 64, or beyond the staging budget).  The two paths return the same
+ * bits, so this count is the only thing that tells a test of the capacity edge which one it ran. */
+uint64_t mi_mcmc_test_linalg_computed_on_device(void);
 #ifdef __cplusplus
 }
 #endif
