@@ -332,7 +332,8 @@ inline mi_settings flatten_common(const algo_settings_t& s)
 inline const double* precond_or_null(const Mat_t& M, size_t d) { return (size_t(M.size()) == d * d && d > 0) ? M.data() : nullptr; }
 
 // many chains through mi_mcmc_<algo>_run; fills draws_out as n_keep x (d * C).  algo 10 / 11: hmc with the diagonal mass adapted during
-// burn-in, pooled over the chains / per chain (NOT reference modes; mi_mcmc.h: mi_mcmc_hmc_run_mass_adapted[_per_chain])
+// burn-in, pooled over the chains / per chain (NOT reference modes; mi_mcmc.h: mi_mcmc_hmc_run_mass_adapted[_per_chain]); algo 12 / 13: hmc / mala
+// with the DENSE pooled mass (mi_mcmc_{hmc,mala}_run_mass_adapted_dense; mass_out: the d x d matrix, row-major)
 inline bool run_device(int algo, const ColVec_t& initial_vals, mi355x::target_t& tgt, Mat_t& draws_out, mi_settings& m,
                        unsigned n_windows = 0, double first_step_size = 0.0, std::vector<double>* mass_out = nullptr)
 {
@@ -349,8 +350,10 @@ inline bool run_device(int algo, const ColVec_t& initial_vals, mi355x::target_t&
     ch.theta = theta.data(); ch.draws = draws.data(); ch.n_accept = tgt.n_accept_draws.data();
     ch.step_size = tgt.step_size.data();
     tgt.desc.struct_size = sizeof(mi_target);
-    if (mass_out) mass_out->assign(algo == 11 ? d * C : d, 0.0);
-    const int rc = (algo == 10) ? mi_mcmc_hmc_run_mass_adapted(&tgt.desc, &m, &ch, n_windows, mass_out ? mass_out->data() : nullptr, nullptr)
+    if (mass_out) mass_out->assign(algo == 11 ? d * C : (algo == 12 || algo == 13) ? d * d : d, 0.0);
+    const int rc = (algo == 12) ? mi_mcmc_hmc_run_mass_adapted_dense(&tgt.desc, &m, &ch, n_windows, mass_out ? mass_out->data() : nullptr, nullptr)
+                 : (algo == 13) ? mi_mcmc_mala_run_mass_adapted_dense(&tgt.desc, &m, &ch, n_windows, mass_out ? mass_out->data() : nullptr, nullptr)
+                 : (algo == 10) ? mi_mcmc_hmc_run_mass_adapted(&tgt.desc, &m, &ch, n_windows, mass_out ? mass_out->data() : nullptr, nullptr)
                  : (algo == 11) ? mi_mcmc_hmc_run_mass_adapted_per_chain(&tgt.desc, &m, &ch, n_windows, first_step_size,
                                                                          mass_out ? mass_out->data() : nullptr, nullptr)
                  : (algo == 0) ? mi_mcmc_hmc_run(&tgt.desc, &m, &ch, nullptr)
@@ -771,6 +774,32 @@ inline bool hmc_mass_adapted(const ColVec_t& initial_vals, target_t& tgt, Mat_t&
     m.step_size = settings.hmc_settings.step_size;
     const bool ok = internal::run_device(per_chain ? 11 : 10, initial_vals, tgt, draws_out, m, n_windows, first_step_size, mass_out);
     if (ok) settings.hmc_settings.n_accept_draws = size_t(tgt.n_accept_draws[0]);
+    return ok;
+}
+// NOT in the reference either: mcmc::hmc / mcmc::mala with the DENSE mass matrix pooled over the chains (the covariance of their current states,
+// shrunk and inverted: mi_mcmc_{hmc,mala}_run_mass_adapted_dense in include/mi_mcmc.h states the estimate).  What a correlated target needs -- a
+// diagonal mass cannot whiten a rotation.  precond_out: the d x d matrix (row-major) the kept draws ran with; precond_mat left empty.
+inline bool hmc_mass_adapted_dense(const ColVec_t& initial_vals, target_t& tgt, Mat_t& draws_out, algo_settings_t& settings, unsigned n_windows,
+                                   std::vector<double>* precond_out = nullptr)
+{
+    mi_settings m = internal::flatten_common(settings);
+    m.n_burnin_draws = settings.hmc_settings.n_burnin_draws;
+    m.n_keep_draws = settings.hmc_settings.n_keep_draws;
+    m.n_leap_steps = settings.hmc_settings.n_leap_steps;
+    m.step_size = settings.hmc_settings.step_size;
+    const bool ok = internal::run_device(12, initial_vals, tgt, draws_out, m, n_windows, 0.0, precond_out);
+    if (ok) settings.hmc_settings.n_accept_draws = size_t(tgt.n_accept_draws[0]);
+    return ok;
+}
+inline bool mala_mass_adapted_dense(const ColVec_t& initial_vals, target_t& tgt, Mat_t& draws_out, algo_settings_t& settings, unsigned n_windows,
+                                    std::vector<double>* precond_out = nullptr)
+{
+    mi_settings m = internal::flatten_common(settings);
+    m.n_burnin_draws = settings.mala_settings.n_burnin_draws;
+    m.n_keep_draws = settings.mala_settings.n_keep_draws;
+    m.step_size = settings.mala_settings.step_size;
+    const bool ok = internal::run_device(13, initial_vals, tgt, draws_out, m, n_windows, 0.0, precond_out);
+    if (ok) settings.mala_settings.n_accept_draws = size_t(tgt.n_accept_draws[0]);
     return ok;
 }
 }  // namespace mi355x

@@ -256,6 +256,27 @@ int mi_mcmc_rmhmc_run(const mi_target* target, const mi_settings* settings, mi_c
  * must be NULL; a dimension whose pooled variance is 0 or not finite keeps mass 1. */
 int mi_mcmc_hmc_run_mass_adapted(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
                                  double* mass_diag_out, void* stream);
+/* mcmc::hmc / mcmc::mala with a DENSE mass matrix adapted during burn-in -- NOT a reference mode either.  A diagonal mass cannot whiten a
+ * CORRELATED target (a rotated Gaussian defeats it entirely); with many chains the pooled covariance of the chains' current states is a good
+ * estimate of the target's and costs one matrix product (mi_mcmc_draws_covariance below).  Schedule, draw0 chaining, n_leapfrogs totals (mala:
+ * 0) and argument checks are those of mi_mcmc_hmc_run_mass_adapted: an estimate from initial_vals, then again after each of `n_windows` equal
+ * parts of the burn-in; n_windows <= n_burnin_draws; n_chains >= 2; settings->precond_mat and chains->mass_diag must be NULL (all four are
+ * MI_ERR_BAD_ARG before any device call).  Each part is an ordinary mi_mcmc_hmc_run / mi_mcmc_mala_run with the dense precond_mat M, so it runs
+ * wherever such a call runs today, and given M it has that call's bits.  ISO, DIAG, DENSE Gaussians and LOGISTIC, any d.
+ * THE ESTIMATE, element-wise on the host in this order (C = n_chains; every operation rounded once, nothing contracted):
+ *   1. S   = cov of mi_mcmc_draws_covariance(chains->theta, n_keep = 1)
+ *   2. a   = C / (C + 5.0),  b = 1e-3 * (5.0 / (C + 5.0))                 (Stan's shrinkage of a window's covariance)
+ *   3. S'_ij = a * S_ij  (i != j),   S'_ii = a * S_ii + b
+ *   4. M0  = INV(S')                                                       (mi_mcmc_mat_inverse's routine)
+ *   5. M_ij = 0.5 * (M0_ij + M0_ji)
+ * The part runs with M = I instead when S has a non-finite entry or a diagonal entry <= 0, when M has a non-finite entry, or when
+ * CHOL_LOWER(M) (mi_mcmc_mat_cholesky_lower's routine) has one: chains that share one start whose pooled variance is exactly 0 begin like
+ * the diagonal variant's "mass 1".  precond_out [d*d] (host, row-major, may be NULL) receives the matrix the kept draws ran with.
+ * step_size is in the preconditioned metric. */
+int mi_mcmc_hmc_run_mass_adapted_dense(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
+                                       double* precond_out, void* stream);
+int mi_mcmc_mala_run_mass_adapted_dense(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
+                                        double* precond_out, void* stream);
 /* The per-chain form SURVEY 8 f-2 words ("per-chain diagonal mass adaptation"; what Stan does for each of its chains): every chain
  * estimates ITS OWN diagonal mass from ITS OWN draws.  The burn-in is cut into n_windows + 1 equal parts; part 0 runs with M = I;
  * the draws of part k are kept in a scratch slab and give, per chain and dimension, the variance over the part's draws (two passes,
@@ -523,6 +544,29 @@ int mi_mcmc_draws_to_chain_major_device(const double* draws_kdc_dev, uint64_t n_
  * lags.  Blocking. */
 int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
                        double* mean, double* acov, double* rhat, double* ess, void* stream);
+
+/* Pooled mean and covariance of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: the samples are the K = n_keep * C
+ * columns, ordered k = t * C + c.  The chains' current state mi_chains.theta ([d][C]) is the case n_keep = 1.  Outputs are HOST arrays, one
+ * of them may be NULL: mean [d], cov [d*d] row-major.  K < 2, d = 0, a NULL slab or both outputs NULL: MI_ERR_BAD_ARG, before any HIP call
+ * (as are n_keep or n_chains beyond 32 bits and d > 65 536).  Blocking.  Workspace: the stream's cached one (mi_mcmc_release_workspace).
+ * DEFINITION (fp64, every operation rounded once; the product sums run on v_mfma_f64_16x16x4_f64, an fma chain per element):
+ *   mu_i   = (sum_k x_ik) / K
+ *   e_ik   = x_ik - mu_i
+ *   cov_ij = (sum_k e_ik * e_jk) / (K - 1)
+ * Every reduction order is a function of (n_keep, d, C) alone -- not of the CU count, the grid, timing or atomics:
+ *   mean   G = min(max(1, 4096 / d), ceil(K / 4096)) groups (integer division), seg = 256 * ceil(ceil(K / G) / 256) samples each, then
+ *          G = ceil(K / seg); in group g, s = 0 .. 255 adds the samples g * seg + s + 256 m, m ascending, from +0; the 256 sums are added by
+ *          the halving tree (r[s] += r[s + h], h = 128, 64, .., 1); the group sums are added in ascending g from +0; one division by K.
+ *   cov    CHUNKING RULE: T = ceil(d / 128) tile rows, P = T (T + 1) / 2 tiles with tj <= ti, n = max(1, 1024 / P) (integer division),
+ *          KC = max(512, 16 * ceil(ceil(K / n) / 16)); chunk q holds the samples [q * KC, min(K, (q + 1) * KC)).  Inside a chunk an element
+ *          is ONE fma chain over k ascending from +0; the chunk partials of an element are added in ascending q from +0; one division by
+ *          K - 1.  Only elements with tile tj <= ti (inside a diagonal tile: j <= i) are computed; (j, i) is a copy of (i, j), so cov is
+ *          symmetric bit for bit.
+ * A non-finite sample propagates by the IEEE rules into the mean of its dimension and into that dimension's row and column of cov, and
+ * nowhere else; nothing is flagged. */
+int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                             double* mean /* [d] host, may be NULL */, double* cov /* [d*d] host, row-major, may be NULL */,
+                             void* stream);
 
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */

@@ -91,6 +91,7 @@ EXPORTS = [
     "mi_mcmc_draws_to_chain_major", "mi_mcmc_draws_to_chain_major_device", "mi_mcmc_shard_bounds", "mi_mcmc_allgather_draws", "mi_mcmc_allgather_draws_ragged", "mi_mcmc_merge_shards", "mi_mcmc_draw_stats",
     "mi_mcmc_allgather_draws_rank_major", "mi_mcmc_rank_major_index", "mi_mcmc_allgather_draws_begin", "mi_mcmc_allgather_draws_wait",
     "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
+    "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -223,6 +224,24 @@ def hmc_mass_adapted(target, settings, chains, n_windows=3, stream=None):
     _check(lib().mi_mcmc_hmc_run_mass_adapted(C.byref(target), C.byref(settings), C.byref(chains), C.c_uint32(n_windows),
                                               C.c_void_p(mass.ctypes.data), C.c_void_p(stream or 0)))
     return mass
+
+
+def _mass_adapted_dense(fn, target, settings, chains, n_windows, stream):
+    d = int(target.d)
+    M = np.zeros((d, d))
+    _check(fn(C.byref(target), C.byref(settings), C.byref(chains), C.c_uint32(n_windows), C.c_void_p(M.ctypes.data), C.c_void_p(stream or 0)))
+    return M
+
+
+def hmc_mass_adapted_dense(target, settings, chains, n_windows=3, stream=None):
+    """mi_mcmc_hmc_run_mass_adapted_dense (NOT a reference mode): hmc with a DENSE mass matrix -- the shrunk, inverted pooled covariance of
+    the chains' current states -- re-estimated after each of n_windows parts of the burn-in.  Returns the final matrix [d, d]."""
+    return _mass_adapted_dense(lib().mi_mcmc_hmc_run_mass_adapted_dense, target, settings, chains, n_windows, stream)
+
+
+def mala_mass_adapted_dense(target, settings, chains, n_windows=3, stream=None):
+    """mi_mcmc_mala_run_mass_adapted_dense: the same for mala."""
+    return _mass_adapted_dense(lib().mi_mcmc_mala_run_mass_adapted_dense, target, settings, chains, n_windows, stream)
 
 
 def hmc_mass_adapted_per_chain(target, settings, chains, n_windows=3, mass_out=None, first_step_size=0.0, stream=None):
@@ -637,6 +656,22 @@ def draw_stats(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=N
                                     C.c_void_p(mean.ctypes.data), C.c_void_p(acov.ctypes.data if want_acov else 0), C.c_void_p(rhat.ctypes.data),
                                     C.c_void_p(ess.ctypes.data), C.c_void_p(stream or 0)))
     return dict(mean=mean, acov=acov, rhat=rhat, ess=ess)
+
+
+def draws_covariance(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_mean=True, want_cov=True):
+    """mi_mcmc_draws_covariance: pooled mean [d] and covariance [d, d] of the n_keep * C columns of a slab [n_keep, d, C] (numpy array -- a
+    2-D [d, C] array is the case n_keep = 1, the chains' state --, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape).
+    Returns (mean, cov); an output that is not wanted is None."""
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d, n_chains = draws.shape
+    mean = np.zeros(d) if want_mean else None
+    cov = np.zeros((d, d)) if want_cov else None
+    _check(lib().mi_mcmc_draws_covariance(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
+                                          C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(stream or 0)))
+    return mean, cov
 
 
 def draws_to_chain_major_device(draws, n_keep, d, n_chains, out, stream=None):

@@ -37,6 +37,7 @@
 #include "logistic_launch.hpp"
 #include "launchers.hpp"
 #include "gemm_samplers.hpp"
+#include "draws_cov.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
 #include "tile_samplers.hpp"
@@ -2201,6 +2202,50 @@ __global__ __launch_bounds__(256) void pooled_variance_kernel(const double* __re
 }
 }  // namespace
 
+// The schedule the pooled mass adaptations share (diagonal: mi_mcmc_hmc_run_mass_adapted; dense: mi_mcmc_{hmc,mala}_run_mass_adapted_dense): estimate() fills
+// the d x d host matrix M from the chains' current states -- first from initial_vals, then after each of n_windows equal parts of the burn-in --, and every
+// part is an ordinary run() with precond_mat = M chained through draw0; the kept draws ride the last part.  leap_total: what n_leapfrogs reports for the run.
+namespace {
+int run_mass_adapted_parts(int (*run)(const mi_target*, const mi_settings*, mi_chains*, void*), const mi_target* target, const mi_settings* settings,
+                           mi_chains* chains, uint32_t n_windows, const double* M, uint64_t leap_total, void* stream, const std::function<int()>& estimate)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t C = chains->n_chains, n_burnin = settings->n_burnin_draws;
+    const uint64_t n_parts = (uint64_t)n_windows + 1;
+    uint64_t done = 0;
+    int rc = estimate();                                 // from the spread of initial_vals
+    if (rc) return rc;
+    for (uint64_t part = 0; part < n_parts; ++part) {
+        const bool last = part + 1 == n_parts;
+        const uint64_t upto = last ? n_burnin : (n_burnin * (part + 1)) / n_parts;
+        mi_settings s_ = *settings;
+        s_.precond_mat = M;
+        s_.n_burnin_draws = upto - done;
+        s_.n_keep_draws = last ? settings->n_keep_draws : 0;
+        mi_chains c_ = *chains;
+        c_.draw0 = chains->draw0 + done;
+        if (!last) { c_.draws = nullptr; c_.n_accept = nullptr; }
+        if (s_.n_burnin_draws + s_.n_keep_draws > 0) {
+            rc = run(target, &s_, &c_, stream);
+            if (rc) return rc;
+            HIP_TRY(hipStreamSynchronize(st));           // M (host) is read during the call's staging; the next estimate reads theta
+        }
+        done = upto;
+        if (!last) { rc = estimate(); if (rc) return rc; }
+    }
+    if (chains->n_leapfrogs) {                           // every part's call reported its own count: the run's total is what the caller gets
+        const uint64_t total = leap_total;
+        if (chains->mem == MI_MEM_DEVICE) { rc = fill_n_leap(chains->n_leapfrogs, C, total, st); if (rc) return rc; }
+        else for (uint64_t c = 0; c < C; ++c) chains->n_leapfrogs[c] = total;
+        if (chains->n_leapfrogs_executed) {              // hmc executes what it counts: the same total (the header's "equal to n_leapfrogs")
+            if (chains->mem == MI_MEM_DEVICE) { rc = fill_n_leap(chains->n_leapfrogs_executed, C, total, st); if (rc) return rc; }
+            else for (uint64_t c = 0; c < C; ++c) chains->n_leapfrogs_executed[c] = total;
+        }
+    }
+    return MI_OK;
+}
+}  // namespace
+
 int mi_mcmc_hmc_run_mass_adapted(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
                                  double* mass_diag_out, void* stream)
 {
@@ -2234,42 +2279,108 @@ int mi_mcmc_hmc_run_mass_adapted(const mi_target* target, const mi_settings* set
         }
         return MI_OK;
     };
-    const uint64_t n_burnin = settings->n_burnin_draws;
     if ((uint64_t)n_windows > settings->n_burnin_draws)
         return fail(MI_ERR_BAD_ARG, "hmc (mass adapted): n_windows = %u exceeds n_burnin_draws = %llu (each re-estimation window needs a draw)", n_windows, (unsigned long long)settings->n_burnin_draws);
-    const uint64_t n_parts = (uint64_t)n_windows + 1;
-    uint64_t done = 0;
-    rc = estimate();                                     // from the spread of initial_vals
+    rc = run_mass_adapted_parts(mi_mcmc_hmc_run, target, settings, chains, n_windows, M.data(),
+                                (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps, stream, estimate);
     if (rc) return rc;
-    for (uint64_t part = 0; part < n_parts; ++part) {
-        const bool last = part + 1 == n_parts;
-        const uint64_t upto = last ? n_burnin : (n_burnin * (part + 1)) / n_parts;
-        mi_settings s_ = *settings;
-        s_.precond_mat = M.data();
-        s_.n_burnin_draws = upto - done;
-        s_.n_keep_draws = last ? settings->n_keep_draws : 0;
-        mi_chains c_ = *chains;
-        c_.draw0 = chains->draw0 + done;
-        if (!last) { c_.draws = nullptr; c_.n_accept = nullptr; }
-        if (s_.n_burnin_draws + s_.n_keep_draws > 0) {
-            rc = mi_mcmc_hmc_run(target, &s_, &c_, stream);
-            if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(st));           // M (host) is read during the call's staging; the next estimate reads theta
-        }
-        done = upto;
-        if (!last) { rc = estimate(); if (rc) return rc; }
-    }
-    if (chains->n_leapfrogs) {                           // every part's call reported its own count: the run's total is what the caller gets
-        const uint64_t total = (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps;
-        if (chains->mem == MI_MEM_DEVICE) { rc = fill_n_leap(chains->n_leapfrogs, C, total, st); if (rc) return rc; }
-        else for (uint64_t c = 0; c < C; ++c) chains->n_leapfrogs[c] = total;
-        if (chains->n_leapfrogs_executed) {              // hmc executes what it counts: the same total (the header's "equal to n_leapfrogs")
-            if (chains->mem == MI_MEM_DEVICE) { rc = fill_n_leap(chains->n_leapfrogs_executed, C, total, st); if (rc) return rc; }
-            else for (uint64_t c = 0; c < C; ++c) chains->n_leapfrogs_executed[c] = total;
-        }
-    }
     if (mass_diag_out) std::memcpy(mass_diag_out, mass.data(), d * 8);
     return MI_OK;
+}
+
+// Pooled mean and covariance of the K = n_keep * C columns of a slab [n_keep][d][C] (draws_cov.hip; the arithmetic: include/mi_mcmc.h)
+int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* mean, double* cov, void* stream)
+{
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "draws_covariance: null slab");
+    if (d == 0) return fail(MI_ERR_BAD_ARG, "draws_covariance: d must be positive");
+    if (!mean && !cov) return fail(MI_ERR_BAD_ARG, "draws_covariance: mean and cov are both NULL, nothing is asked for");
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "draws_covariance: n_keep / n_chains do not fit 32 bits");
+    if (n_keep * n_chains < 2) return fail(MI_ERR_BAD_ARG, "draws_covariance: K = n_keep * n_chains = %llu, at least 2 samples are needed", (unsigned long long)(n_keep * n_chains));
+    if (d > mi::dcov::COV_MAX_D) return fail(MI_ERR_BAD_ARG, "draws_covariance: d = %llu is beyond %llu", (unsigned long long)d, (unsigned long long)mi::dcov::COV_MAX_D);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DevBuf staged;
+    const double* x = draws_kdc;
+    if (mem == MI_MEM_HOST) {
+        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
+        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
+        x = staged.as<double>();
+    }
+    const mi::dcov::CovPlan plan = mi::dcov::cov_plan(n_keep, d, n_chains, cov != nullptr);
+    WsLease ws;
+    int rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    HIP_TRY((hipError_t)mi::dcov::cov_run(x, d, n_chains, plan, ws.p, cov != nullptr, st));
+    if (mean) HIP_TRY(hipMemcpyAsync(mean, ws.as<double>() + plan.o_mean, d * 8, hipMemcpyDeviceToHost, st));
+    if (cov) HIP_TRY(hipMemcpyAsync(cov, ws.as<double>() + plan.o_cov, d * d * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // blocking: the outputs are the caller's host arrays, the staged slab and the workspace are ours
+    return MI_OK;
+}
+
+namespace {
+// hmc / mala with a DENSE mass matrix pooled over the chains (include/mi_mcmc.h states the estimate, element by element)
+int run_mass_adapted_dense(const char* who, bool hmc, const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
+                           double* precond_out, void* stream)
+{
+    if (!target || !settings || !chains) return fail(MI_ERR_BAD_ARG, "null target / settings / chains");
+    // the adaptation's own conditions first: they need no device
+    if (settings->precond_mat) return fail(MI_ERR_BAD_ARG, "%s (dense mass adapted): settings.precond_mat must be NULL, the mass matrix is estimated", who);
+    if (chains->mass_diag) return fail(MI_ERR_BAD_ARG, "%s (dense mass adapted): chains.mass_diag must be NULL, the mass matrix is estimated", who);
+    if (chains->n_chains < 2) return fail(MI_ERR_BAD_ARG, "%s (dense mass adapted): the mass is pooled over the chains, at least 2 are needed", who);
+    if ((uint64_t)n_windows > settings->n_burnin_draws)
+        return fail(MI_ERR_BAD_ARG, "%s (dense mass adapted): n_windows = %u exceeds n_burnin_draws = %llu (each re-estimation window needs a draw)", who, n_windows, (unsigned long long)settings->n_burnin_draws);
+    int rc = check_common(target, settings, chains);
+    if (rc) return rc;
+    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE &&
+        target->kind != MI_TARGET_LOGISTIC)
+        return fail(MI_ERR_UNSUPPORTED, "%s (dense mass adapted): implemented for the Gaussian and the logistic-regression targets", who);
+    const uint64_t d = target->d, C = chains->n_chains;
+    std::vector<double> S(d * d), Sp(d * d), M0, M(d * d), L;
+    auto all_finite = [](const std::vector<double>& v) { for (double e : v) if (!std::isfinite(e)) return false; return true; };
+    auto estimate = [&]() -> int {
+        int rc_ = mi_mcmc_draws_covariance(chains->theta, chains->mem, 1, d, C, nullptr, S.data(), stream);
+        if (rc_) return rc_;
+        bool ok = all_finite(S);
+        for (uint64_t i = 0; ok && i < d; ++i) ok = S[i * d + i] > 0.0;
+        if (ok) {
+            const double a = (double)C / ((double)C + 5.0), b = 1e-3 * (5.0 / ((double)C + 5.0));      // Stan's shrinkage of a window's covariance
+            for (uint64_t e = 0; e < d * d; ++e) Sp[e] = a * S[e];
+            for (uint64_t i = 0; i < d; ++i) Sp[i * d + i] = a * S[i * d + i] + b;
+            if ((rc_ = host_inverse(Sp.data(), d, M0))) return rc_;
+            for (uint64_t i = 0; i < d; ++i)
+                for (uint64_t j = 0; j < d; ++j) M[i * d + j] = 0.5 * (M0[i * d + j] + M0[j * d + i]);
+            ok = all_finite(M);
+            if (ok) {                                    // (memoised for d >= 64: the part's own factorisation is this one)
+                if ((rc_ = host_cholesky_lower(M.data(), d, L))) return rc_;
+                ok = all_finite(L);
+            }
+        }
+        if (!ok) {                                       // degenerate or non-finite spread: this part runs with M = I
+            std::fill(M.begin(), M.end(), 0.0);
+            for (uint64_t i = 0; i < d; ++i) M[i * d + i] = 1.0;
+        }
+        return MI_OK;
+    };
+    rc = run_mass_adapted_parts(hmc ? mi_mcmc_hmc_run : mi_mcmc_mala_run, target, settings, chains, n_windows, M.data(),
+                                hmc ? (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps : 0, stream, estimate);
+    if (rc) return rc;
+    if (precond_out) std::memcpy(precond_out, M.data(), d * d * 8);
+    return MI_OK;
+}
+}  // namespace
+
+int mi_mcmc_hmc_run_mass_adapted_dense(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
+                                       double* precond_out, void* stream)
+{
+    return run_mass_adapted_dense("hmc", true, target, settings, chains, n_windows, precond_out, stream);
+}
+
+int mi_mcmc_mala_run_mass_adapted_dense(const mi_target* target, const mi_settings* settings, mi_chains* chains, uint32_t n_windows,
+                                        double* precond_out, void* stream)
+{
+    return run_mass_adapted_dense("mala", false, target, settings, chains, n_windows, precond_out, stream);
 }
 
 // per chain and dimension: variance of the chain's own draws of one burn-in part (slab [n][d][C]; two passes, draws ascending),
