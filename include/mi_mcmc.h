@@ -62,6 +62,15 @@ typedef enum mi_target_kind {
                                  * hmc (identity / diagonal precond_mat) and rwmh (no cov_mat) there also with vals_bound: the chains in the transformed space, the products at
                                  * x = inv_transform(theta), J(theta) g in the product's epilogue (three more state vectors in the workspace; what does not fit the free device
                                  * memory, bounds with a dense precond_mat or chains.mass_diag, bounded nuts: the literal kernels; bounded mala beyond d = 512: MI_ERR_UNSUPPORTED);
+                                 * nuts there without bounds, with the identity or a DIAGONAL precond_mat and 1 <= max_tree_depth <= 10: per-chain memoised trees, every chain
+                                 * at its own point of its own doubling of its own draw, the gradients of all chains as the products of one TICK (gemm_nuts.hpp); the host
+                                 * polls a device counter of running chains -- nothing waits on the device -- up to a tick ceiling computed from the settings
+                                 * (beyond it: MI_ERR_HIP).  Capacity rule: a chain holds 11 + 2 (1 + (D - 1) D / 2) vectors of d (padded to 16) doubles, D = max_tree_depth,
+                                 * the logistic target two more of n_rows (padded to 16), and 5.9 KB of scalars (0.85 MB at d = 1024, D = 10); next to the chains the
+                                 * call needs the packed matrices, the literal replay's areas and, for chains / a target in host memory, their staged copies, which are
+                                 * counted.  Chains that do not fit the free device memory together run as consecutive ranges, in multiples of 128
+                                 * (same bits: the random numbers are counter-based on the global chain index); where not even 128 fit, and for bounded nuts, a dense
+                                 * precond_mat, max_tree_depth > 10 and mi_mcmc_nuts_run_callback: the literal kernels;
                                  * the same for MI_TARGET_GAUSS_DENSE beyond d = 512 (one product per gradient) */
     MI_TARGET_NORMAL_MODEL = 5, /* d = 2, vals = (mu, sigma), observations x_1..x_n in y[0..n_rows): the model of the reference's
                                  * example programs (/root/reference/examples/eigen/rmhmc_normal.cpp:44-106),
@@ -183,7 +192,8 @@ typedef struct mi_chains {
     uint64_t* n_leapfrogs_executed; /* out [C], may be NULL (needs n_leapfrogs next to it): the leapfrog steps the device really computed.
                                * Equal to n_leapfrogs except for nuts on the MEMOISED ticks -- the default of the plain and diagonal-mass
                                * Gaussian case, of the built-in Gaussian with vals_bound, of nuts on tile targets and (round 6) of nuts on the
-                               * LDS-streamed evaluation (logistic d <= 512, dense Gaussians 128 < d <= 512) -- which compute every
+                               * LDS-streamed evaluation (logistic d <= 512, dense Gaussians 128 < d <= 512) and on the matrix-product route (both beyond
+                               * d = 512: one per distinct point of a doubling plus the step-size search) -- which compute every
                                * distinct state of a doubling once (same draws, fewer steps).  (MI_KERNEL_NUTS_MEMO is accepted and
                                * equivalent to MI_KERNEL_AUTO: the memoised tick is what runs unless MI_KERNEL_NUTS_TICK_LOCAL or
                                * MI_KERNEL_NUTS_LOCKSTEP asks for the kernel that executes every leaf.) */

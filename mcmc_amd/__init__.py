@@ -294,6 +294,52 @@ def test_linalg_computed_on_device():
     return int(f())
 
 
+def test_set_gemm_nuts_ws_bytes(n_bytes):
+    """mi_mcmc_test_set_gemm_nuts_ws_bytes (TEST HOOK, mi_mcmc_probes.h): the workspace nuts on the matrix-product route may take for itself (the packed matrices
+    and one range of chains), as if that were all the free device memory; 0 = the real figure.  Fewer chains than the call's fit: consecutive ranges in multiples of
+    128; not even 128: the literal kernel.  Results do not depend on it."""
+    lib().mi_mcmc_test_set_gemm_nuts_ws_bytes(C.c_uint64(int(n_bytes)))
+
+
+def _u64_hook(name, *args):
+    f = getattr(lib(), name)
+    f.restype = C.c_uint64
+    return int(f(*args))
+
+
+def test_gemm_nuts_ranges():
+    """mi_mcmc_test_gemm_nuts_ranges (TEST HOOK): ranges of chains nuts on the matrix-product route has run so far in this process (monotonic)."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_ranges")
+
+
+def test_gemm_nuts_last_ticks():
+    """mi_mcmc_test_gemm_nuts_last_ticks (TEST HOOK): of the last nuts call on the matrix-product route -- ticks run, (tick, chain) slots in which the chain was
+    not idle, and all (tick, chain) slots."""
+    t, b, n = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    lib().mi_mcmc_test_gemm_nuts_last_ticks(C.byref(t), C.byref(b), C.byref(n))
+    return int(t.value), int(b.value), int(n.value)
+
+
+def test_gemm_nuts_tick_ceiling(max_tree_depth, n_draws, search=True):
+    """mi_mcmc_test_gemm_nuts_tick_ceiling (TEST HOOK; host arithmetic, no device): the ticks after which the route's host loop gives up."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_tick_ceiling", C.c_uint32(int(max_tree_depth)), C.c_uint64(int(n_draws)), C.c_int(1 if search else 0))
+
+
+def test_gemm_nuts_chain_bytes(d, n_rows, max_tree_depth):
+    """mi_mcmc_test_gemm_nuts_chain_bytes (TEST HOOK; host arithmetic): workspace bytes per chain; n_rows = 0: the dense Gaussian."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_chain_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint32(int(max_tree_depth)))
+
+
+def test_gemm_nuts_fixed_bytes(d, n_rows):
+    """mi_mcmc_test_gemm_nuts_fixed_bytes (TEST HOOK; host arithmetic): workspace bytes that do not depend on the chains (the packed matrices, the counters)."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_fixed_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)))
+
+
+def test_gemm_nuts_range_chains(n_chains, chain_bytes, fixed_bytes, budget):
+    """mi_mcmc_test_gemm_nuts_range_chains (TEST HOOK; host arithmetic): chains per range under `budget` bytes -- all of them (padded to 128) or a multiple of 128; 0: none."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_range_chains", C.c_uint64(int(n_chains)), C.c_uint64(int(chain_bytes)), C.c_uint64(int(fixed_bytes)), C.c_uint64(int(budget)))
+
+
 def last_kernel():
     """mi_mcmc_last_kernel: the kernel this thread's last run spent its time in, as rocprofv3 names it."""
     return lib().mi_mcmc_last_kernel().decode()

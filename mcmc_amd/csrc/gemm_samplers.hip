@@ -51,11 +51,13 @@
 
 #include "gemm_samplers.hpp"
 #include "det_math.hpp"
+#include "nuts_points.hpp"        // the memoised NUTS trajectory: which points a doubling visits, which tests a point closes (gemm_nuts.hpp)
 #include "hmc_dense.hpp"          // box_transform, box_inv_transform, box_inv_jacobian, box_log_jacobian_term: the reference's element-wise maps, out of line
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 
 namespace mi {
 namespace gemm {
@@ -98,6 +100,9 @@ struct StepParams {
     const double* lb;
     const double* ub;
     const uint32_t* box_blocks;   // [dK / 16] nonzero: the 16-row block holds a bounded dimension
+    // nuts (gemm_nuts.hpp).  MODE 12: every chain has its own signed step and takes a point this tick or does not
+    const double* ecol;           // [Cp] the step of the column's chain (0: an evaluation without a kick)
+    const uint32_t* colmode;      // [Cp] zero: the column's chain takes no point this tick -- its memory stays as it is
 };
 
 template <int MODE, int TGT>
@@ -210,6 +215,41 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void gemm_step_kernel(const 
                     const double mean_prop = xv[r][ni] + (prm.s2 * acc[ti][ni][r]) / 2.0;
                     prm.g_out[idx] = bv[r][ni] - mean_prop;
                     prm.pos_out[idx] = xv[r][ni] - mv[r][ni];
+                }
+        } else if constexpr (MODE == 12) {                                 // nuts: the second half-kick of a point (nuts.cpp:139-154), the step per column
+            double ec[4], pv[4][4];
+            [[maybe_unused]] double xv[4][4];
+            bool on[4];
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                const size_t col = n0 + (size_t)(64 * wn + 16 * ni + c16);
+                ec[ni] = prm.ecol[col];
+                on[ni] = prm.colmode[col] != 0u;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) {
+                    pv[r][ni] = 0.0;
+                    if constexpr (TGT == TGT_LOGISTIC) xv[r][ni] = 0.0;
+                    if (on[ni]) {
+                        pv[r][ni] = prm.pm[at(r, ni)];
+                        if constexpr (TGT == TGT_LOGISTIC) xv[r][ni] = prm.pos[at(r, ni)];
+                    }
+                }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) {
+                    const size_t idx = at(r, ni);
+                    const double v = acc[ti][ni][r];
+                    double g;
+                    if constexpr (TGT == TGT_DENSE) g = -v;                // grad log K = -(P theta)
+                    else g = v - xv[r][ni];                                // X^T (y - sigmoid(eta)) - beta
+                    if (on[ni]) {
+                        prm.pm[idx] = pv[r][ni] + (ec[ni] * g) / 2.0;     // the second half-step of the chain's leapfrog
+                        prm.g_out[idx] = g;
+                    }
                 }
         } else if constexpr (MODE == 10 || MODE == 11) {                  // a leapfrog step in the transformed space (hmc.cpp:107-122,171)
             const bool boxed = prm.box_blocks[row0 >> 4] != 0u;            // (the same for the whole wave)
@@ -997,6 +1037,8 @@ int gemm_run(const GemmRun& r, hipStream_t st, const char** kernel_name)
 {
     return r.X != nullptr ? gemm_run_t<TGT_LOGISTIC>(r, st, kernel_name) : gemm_run_t<TGT_DENSE>(r, st, kernel_name);
 }
+
+#include "gemm_nuts.hpp"          // mcmc::nuts on this route: per-chain trees, one product per tick for all chains
 
 }  // namespace gemm
 }  // namespace mi

@@ -50,5 +50,42 @@ size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass = 
 // enqueues the whole run on `st`; returns a hipError_t as int (0 = enqueued).  *kernel_name: what ran, for mi_mcmc_last_kernel()
 int gemm_run(const GemmRun& r, hipStream_t st, const char** kernel_name);
 
+// ---- mcmc::nuts on this route (gemm_nuts.hpp): identity or a DIAGONAL precond_mat, no bounds, 1 <= max_tree_depth <= 10.  One RANGE of the call's chains per run:
+// the caller's arrays are indexed by column c_off + c with the call's chain count C_total as their stride, the random numbers by chain0 + c_off + c.
+struct GemmNutsRun {
+    uint32_t d = 0;
+    uint64_t C = 0, C_total = 0, c_off = 0, chain0 = 0;
+    const double* P = nullptr;        // as GemmRun
+    const double* X = nullptr;
+    const double* y = nullptr;
+    uint32_t n_rows = 0;
+    double* theta = nullptr;          // [d][C_total] in / out (left alone for flagged chains, like every output below)
+    double* draws = nullptr;          // [n_keep][d][C_total] or nullptr
+    uint64_t* n_accept = nullptr;     // [C_total] or nullptr
+    uint64_t* n_leap = nullptr;       // the REFERENCE's leapfrog count: one per leaf walked plus the search
+    uint64_t* n_exec = nullptr;       // the leapfrogs made: one per distinct point plus the search
+    double* step = nullptr;           // in (a continuation) / out
+    uint32_t* depth = nullptr;        // [n_total][C_total] or nullptr
+    double* adapt = nullptr;          // [3][C_total] dual-averaging state, in (a continuation inside the window) / out, or nullptr
+    uint32_t* nf_flag = nullptr;      // [C_total + 1], zeroed by the caller
+    uint64_t seed = 0;
+    uint32_t n_burnin = 0, n_keep = 0, draw0 = 0, n_adapt = 0, max_depth = 0;
+    double eps_bar0 = 0.0, delta = 0.0, gamma = 0.0, t0 = 0.0, kappa = 0.0;
+    const double* mass_tables = nullptr;   // as GemmRun
+    bool diag_mass = false;
+    void* ws = nullptr;               // gemm_nuts_fixed_bytes + round_up(C, 128) * gemm_nuts_chain_bytes bytes
+    bool pack = true;                 // pack the matrices into ws (false: a later range of the same call finds them there)
+    bool use_graph = true;
+    // out
+    uint64_t ticks_run = 0, points_taken = 0, still_running = 0;      // still_running != 0: the tick ceiling was reached
+};
+uint32_t gemm_nuts_points(uint32_t max_depth);
+uint64_t gemm_nuts_tick_ceiling(uint32_t max_depth, uint64_t n_total, bool search);
+size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth);
+size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows);
+uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_bytes, size_t budget);
+// runs the range to its end (the host polls the device's counter of running chains: nothing waits on the device); returns a hipError_t as int
+int gemm_nuts_run(GemmNutsRun& r, hipStream_t st, const char** kernel_name);
+
 }  // namespace gemm
 }  // namespace mi

@@ -89,6 +89,24 @@ extern "C" void mi_mcmc_test_set_grid_cap(uint32_t max_workgroups) { mi::g_test_
 extern "C" void mi_mcmc_test_set_linalg_stage_bytes(uint32_t bytes) { linalg_set_stage_bytes(bytes); }
 extern "C" uint64_t mi_mcmc_test_linalg_computed(void) { return linalg_accel().n_computed.load(std::memory_order_relaxed); }
 extern "C" uint64_t mi_mcmc_test_linalg_computed_on_device(void) { return linalg_accel().n_on_device.load(std::memory_order_relaxed); }
+// test hooks, declared in mi_mcmc_probes.h: the workspace budget of nuts on the matrix-product route (run_gemm_nuts), the ranges it has run, and the host
+// arithmetic of its routing (plain functions: they need no device)
+namespace { std::atomic<uint64_t> g_gemm_nuts_ws_bytes{0}, g_gemm_nuts_ranges{0}, g_gemm_nuts_ticks{0}, g_gemm_nuts_points{0}, g_gemm_nuts_slots{0}; }
+extern "C" void mi_mcmc_test_set_gemm_nuts_ws_bytes(uint64_t bytes) { g_gemm_nuts_ws_bytes.store(bytes, std::memory_order_relaxed); }
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_ranges(void) { return g_gemm_nuts_ranges.load(std::memory_order_relaxed); }
+extern "C" void mi_mcmc_test_gemm_nuts_last_ticks(uint64_t* ticks, uint64_t* busy_slots, uint64_t* slots)
+{
+    if (ticks) *ticks = g_gemm_nuts_ticks.load(std::memory_order_relaxed);
+    if (busy_slots) *busy_slots = g_gemm_nuts_points.load(std::memory_order_relaxed);
+    if (slots) *slots = g_gemm_nuts_slots.load(std::memory_order_relaxed);
+}
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_tick_ceiling(uint32_t max_tree_depth, uint64_t n_draws, int search) { return mi::gemm::gemm_nuts_tick_ceiling(max_tree_depth, n_draws, search != 0); }
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth) { return mi::gemm::gemm_nuts_chain_bytes(d, n_rows, max_tree_depth); }
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows) { return mi::gemm::gemm_nuts_fixed_bytes(d, n_rows); }
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint64_t chain_bytes, uint64_t fixed_bytes, uint64_t budget)
+{
+    return mi::gemm::gemm_nuts_range_chains(n_chains, (size_t)chain_bytes, (size_t)fixed_bytes, (size_t)budget);
+}
 
 namespace {
 
@@ -2854,6 +2872,151 @@ bool lds_nuts_case(const mi_target* target, const mi_settings* settings)
 // 65 536 chains, 135 / 156 at 8 192; d = 64: 209 / 208; d = 32: 71 / 72) and within 13 % at d = 16 (37 / 33 ms) -- one tick to maintain instead of
 // four.  Their hints stay valid and are ignored.  MI_KERNEL_NUTS_TICK_LOCAL keeps the independent tick-local kernel for A/B runs.
 
+// nuts on the matrix-product route (gemm_nuts.hpp): the dense Gaussian and the logistic target BEYOND d = 512, identity or a DIAGONAL precond_mat, no bounds,
+// 1 <= max_tree_depth <= 10 -- per-chain memoised trees, one product per tick for all chains.  Capacity is a routing condition, then chunking: a chain holds
+// gemm_nuts_chain_bytes of workspace (0.85 MB at d = 1024, max_tree_depth 10), so a call whose chains do not fit the free device memory (plus this stream's cached
+// workspace) together runs them as consecutive RANGES, in multiples of 128, through the same code -- chains are independent and their random numbers are
+// counter-based on the global chain index, so the bits do not change -- and a call for which not even one range of 128 fits stays on the literal kernel.
+struct GemmNutsPlan { uint64_t range = 0; size_t own_bytes = 0; };
+bool gemm_nuts_case(const mi_target* target, const mi_settings* settings, const mi_chains* chains, hipStream_t st, GemmNutsPlan& plan)
+{
+    if (!((target->kind == MI_TARGET_GAUSS_DENSE || target->kind == MI_TARGET_LOGISTIC) && target->d > 512 && target->kernel_hint != MI_KERNEL_LITERAL)) return false;
+    if (settings->vals_bound || chains->mass_diag || settings->max_tree_depth < 1 || settings->max_tree_depth > 10) return false;
+    if (settings->precond_mat && !precond_is_diagonal(settings, target->d)) return false;
+    const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
+    if (d > 131056ULL || n > 0x7fffffffULL) return false;                                   // (grid.y of the element-wise kernel: padded d / 2)
+    const uint32_t D = (uint32_t)settings->max_tree_depth;
+    const size_t chain_b = mi::gemm::gemm_nuts_chain_bytes((uint32_t)d, (uint32_t)n, D), fixed_b = mi::gemm::gemm_nuts_fixed_bytes((uint32_t)d, (uint32_t)n);
+    size_t budget = (size_t)g_gemm_nuts_ws_bytes.load(std::memory_order_relaxed);           // (the test hook: the route's own workspace, as if this were all there is)
+    if (budget == 0) {
+        // next to the route's own: the flags and the literal replay's matrix and work areas, a host target's matrix and the tables
+        const size_t rest = (C + 1) * sizeof(uint32_t) + ((size_t)d * std::max<size_t>(d, n) + 64 + (size_t)std::min<uint64_t>(C, 512u)
+                            * mi::lit::lit_work_doubles((uint32_t)d, (uint32_t)n, false, D, true, false)) * sizeof(double) + (size_t)d * std::max<size_t>(d, n) * sizeof(double) + ((size_t)1 << 20);
+        // ... and what stage_in allocates for chains in host memory, for the whole call whatever the ranges: theta, draws, nuts_depth, the per-chain arrays; the labels of a host target
+        size_t staged = 0;
+        if (chains->mem == MI_MEM_HOST) {
+            const size_t n_tot = (size_t)(settings->n_burnin_draws + settings->n_keep_draws);
+            staged = (size_t)d * C * sizeof(double) + (chains->draws ? (size_t)settings->n_keep_draws * d * C * sizeof(double) : 0)
+                     + (chains->nuts_depth ? n_tot * C * sizeof(uint32_t) : 0)
+                     + 8 * C * sizeof(double);           // stage_in's per-chain arrays: n_accept, step_size, n_leapfrogs, n_leapfrogs_executed, nuts_adapt_state [3] (7 C words; one spare)
+        }
+        if (target->mem == MI_MEM_HOST) staged += (size_t)n * sizeof(double);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+        const size_t have = free_b + ws_cached_bytes(st);      // (the cached workspace of this stream is given back before a larger one is taken)
+        budget = have > rest + staged ? have - rest - staged : 0;
+    }
+    uint64_t range = mi::gemm::gemm_nuts_range_chains(C, chain_b, fixed_b, budget);
+    range = std::min<uint64_t>(range, (uint64_t)65535 * 64 / 128 * 128);                     // (grid.x of the class-wise kernel: padded chains / 64)
+    if (range < 128) return false;
+    plan.range = range;
+    plan.own_bytes = fixed_b + (size_t)range * chain_b;
+    return true;
+}
+int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st, const GemmNutsPlan& plan)
+{
+    int rc;
+    const uint64_t d = target->d, C = chains->n_chains;
+    const bool logit = target->kind == MI_TARGET_LOGISTIC;
+    const uint64_t n = logit ? target->n_rows : 0;
+    const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
+    if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    DevBuf P_owned, Xo, yo;
+    const double *P_dev = nullptr, *X_dev = nullptr, *y_dev = nullptr;
+    if (logit) {
+        if (!target->X || !target->y || n == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
+        X_dev = target->X; y_dev = target->y;
+        if (target->mem == MI_MEM_HOST) {
+            HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
+            HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
+            X_dev = Xo.as<double>(); y_dev = yo.as<double>();
+        }
+    } else {
+        rc = dense_precision_on_device(target, P_owned, &P_dev, st);
+        if (rc) return rc;
+    }
+    StagedChains sc;
+    rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
+    if (rc) return rc;
+    mi::gemm::GemmNutsRun g;
+    g.d = (uint32_t)d; g.C_total = C; g.chain0 = chains->chain0; g.P = P_dev; g.X = X_dev; g.y = y_dev; g.n_rows = (uint32_t)n;
+    g.theta = sc.dev.theta; g.draws = sc.dev.draws; g.n_accept = sc.dev.n_accept; g.n_leap = sc.dev.n_leapfrogs; g.n_exec = sc.dev.n_leapfrogs_executed;
+    g.step = sc.dev.step_size; g.depth = sc.dev.nuts_depth; g.adapt = sc.dev.nuts_adapt_state;
+    sc.exec_written = g.n_exec != nullptr;               // (every doubling on a memoised trajectory)
+    g.seed = settings->rng_seed_value;
+    g.n_burnin = (uint32_t)settings->n_burnin_draws; g.n_keep = (uint32_t)settings->n_keep_draws; g.draw0 = (uint32_t)chains->draw0;
+    if ((rc = nuts_continuation(settings, chains, &g.n_adapt))) return rc;
+    g.max_depth = (uint32_t)settings->max_tree_depth;
+    g.eps_bar0 = settings->step_size; g.delta = settings->target_accept_rate; g.gamma = settings->gamma_val; g.t0 = settings->t0_val; g.kappa = settings->kappa_val;
+    // identity or a DIAGONAL precond_mat: diag(M), CHOL_LOWER (sqrt), INV (reciprocal) from lit_prepare, in the oracle's operation order; the identity as tables of ones
+    mi::lit::LitPrep prep;
+    rc = mi::lit::lit_prepare(0, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
+    if (rc) return rc;
+    const uint32_t dK = mi::gemm::gemm_padded_d((uint32_t)d);
+    std::vector<double> tabs(3 * (size_t)dK, 1.0);
+    if (prep.precond == 1)
+        for (uint64_t i = 0; i < d; ++i) { tabs[i] = prep.m[i]; tabs[dK + i] = prep.m_sqrt[i]; tabs[2 * (size_t)dK + i] = prep.m_inv[i]; }
+    DevBuf tabs_dev;
+    HIP_TRY(tabs_dev.alloc(tabs.size() * 8));
+    HIP_TRY(hipMemcpy(tabs_dev.p, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice));
+    g.mass_tables = tabs_dev.as<double>(); g.diag_mass = prep.precond == 1;
+    // workspace: the route's own (the packed matrices, one range of chains) | non-finite flags | the matrix transposed and the work areas of the literal replay
+    ReplayWs rp;
+    rp.t_doubles = ((size_t)d * std::max<size_t>(d, n) + 31) & ~(size_t)31;
+    rp.own_bytes = (plan.own_bytes + 255) & ~(size_t)255;
+    rp.stride = mi::lit::lit_work_doubles((uint32_t)d, (uint32_t)n, false, g.max_depth, true, false);
+    rp.n_wg = (unsigned)std::min<uint64_t>(C, 512u);
+    const size_t flag_bytes = ((C + 1) * sizeof(uint32_t) + 255) & ~(size_t)255;
+    rp.total_bytes = rp.own_bytes + flag_bytes + (rp.t_doubles + (size_t)rp.n_wg * rp.stride) * sizeof(double);
+    WsLease base;
+    rc = ws_get(st, rp.total_bytes, base);
+    if (rc) return rc;
+    rc = replay_bind(rp, base.p, C, st);
+    if (rc) return rc;
+    g.nf_flag = rp.flag;
+    g.ws = base.p;
+    const char* kname = nullptr;
+    uint64_t ticks = 0, points = 0, slots = 0;
+    for (uint64_t c_off = 0; c_off < C; c_off += plan.range) {           // the chains as consecutive ranges: the same code, the global chain index
+        g.c_off = c_off; g.C = std::min<uint64_t>(plan.range, C - c_off); g.pack = c_off == 0;
+        // a tick is a handful of short launches while the chains are few: replayed from a captured (linear) graph; at full size the queue runs ahead anyway
+        // (the threshold is run_gemm's, taken over and not varied here: at d = 1024 the measured tick is far longer than a launch on both sides of it -- DESIGN 4.22)
+        g.use_graph = (double)d * (double)(logit ? 2 * n : d) * (double)g.C < 3.0e10;
+        const int e = mi::gemm::gemm_nuts_run(g, st, &kname);
+        if (e != 0) return fail(MI_ERR_HIP, "nuts: matrix-product sampler: %s", hipGetErrorString((hipError_t)e));
+        if (g.still_running != 0)
+            return fail(MI_ERR_HIP, "nuts: matrix-product sampler: %llu chains still running after the ceiling of %llu ticks", (unsigned long long)g.still_running, (unsigned long long)g.ticks_run);
+        g_gemm_nuts_ranges.fetch_add(1, std::memory_order_relaxed);
+        ticks += g.ticks_run; points += g.points_taken; slots += g.ticks_run * g.C;
+    }
+    g_gemm_nuts_ticks.store(ticks, std::memory_order_relaxed); g_gemm_nuts_points.store(points, std::memory_order_relaxed); g_gemm_nuts_slots.store(slots, std::memory_order_relaxed);
+    {   // chains that reached the non-finite regime (or ran past the search's allowance): replayed literally (literal.hpp)
+        mi::lit::LitParams lp{};
+        rc = transpose_on_device(logit ? X_dev : P_dev, rp.tbuf, (uint32_t)(logit ? n : d), (uint32_t)d, st);
+        if (rc) return rc;
+        if (logit) { lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.d = (uint32_t)d; lp.t.n_rows = (uint32_t)n; lp.t.X = X_dev; lp.t.y = y_dev; lp.t.Xt = rp.tbuf; }
+        else { lp.t.kind = mi::lit::LIT_DENSE; lp.t.d = (uint32_t)d; lp.t.prec = rp.tbuf; }
+        mi::lit::lit_orders(lp.t);
+        lit_common(lp, settings, &sc.dev, rp, false);
+        lp.n_adapt = g.n_adapt; lp.max_depth = g.max_depth;
+        lp.delta = g.delta; lp.gamma = g.gamma; lp.t0 = g.t0; lp.kappa = g.kappa;
+        lp.step_out = sc.dev.step_size; lp.depth_trace = sc.dev.nuts_depth; lp.adapt_state = sc.dev.nuts_adapt_state;
+        if (prep.precond == 1) { lp.precond = 1; lp.m = g.mass_tables; lp.m_sqrt = g.mass_tables + dK; lp.m_inv = g.mass_tables + 2 * (size_t)dK; }
+        rc = launched("matrix-product nuts (literal replay)", mi::launch_literal(2, lp, rp.n_wg, st));
+        if (rc) return rc;
+        if (g.n_exec) {                                  // a replayed chain executed every leapfrog it counts
+            hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, rp.flag, g.n_leap, g.n_exec, C);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    mi::note_kernel("%s", kname);
+    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));                  // (the mass tables are ours)
+    return MI_OK;
+}
+
 int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
 {
     int rc = check_common(target, settings, chains);
@@ -2864,6 +3027,8 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
     if (target->kind == MI_TARGET_LOGISTIC) {
         if (d <= (uint64_t)mi::SMALL_MAX_D && settings->max_tree_depth <= 10) return run_small_logistic("nuts", 2, target, settings, chains, st);
         if (d <= 512 && lds_nuts_case(target, settings)) return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC);
+        GemmNutsPlan plan;
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, two matrix products per tick
         return run_literal("nuts", 2, target, settings, chains, st);
     }
     if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
@@ -2871,6 +3036,10 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
     // the tiled kernels: d <= 128, max_tree_depth <= 10 (per-level records and scalars are sized for that); beyond, literal.hpp
     if (target->kind == MI_TARGET_GAUSS_DENSE && d > 128 && d <= 512 && lds_nuts_case(target, settings))
         return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (nuts_lds.hpp)
+    {
+        GemmNutsPlan plan;
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, one matrix product per tick (gemm_nuts.hpp)
+    }
     if (d > 128 || settings->max_tree_depth > (uint64_t)mi::NUTS_MAX_DEPTH) return run_literal("nuts", 2, target, settings, chains, st);
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
     if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");

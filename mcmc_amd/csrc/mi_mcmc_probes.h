@@ -28,6 +28,21 @@ uint64_t mi_mcmc_test_linalg_computed(void);
 /* ... and how many of those ran the device kernels (the others: the host loops -- d < 64, or beyond the staging budget).  The two paths return the same
  * bits, so this count is the only thing that tells a test of the capacity edge which one it ran. */
 uint64_t mi_mcmc_test_linalg_computed_on_device(void);
+/* Defined in libmi_mcmc.so itself (test hooks like the ones above), for mi_mcmc_nuts_run beyond d = 512 on the matrix-product route (gemm_nuts.hpp):
+ * the workspace the route may take for ITSELF -- the packed matrices and one range of chains -- in bytes, as if that were all the free device memory (0 = the real
+ * figure), so that a test with a few hundred chains runs what a call beyond the device's memory runs: consecutive ranges of chains in multiples of 128, and,
+ * where not even 128 chains fit, the literal kernel.  Process-wide.  Results do not depend on it. */
+void mi_mcmc_test_set_gemm_nuts_ws_bytes(uint64_t bytes);
+/* ... the ranges of chains the route has run so far (process-wide, monotonic), and of its last call: the ticks run, the (tick, chain) slots in which the
+ * chain was not idle, and all (tick, chain) slots. */
+uint64_t mi_mcmc_test_gemm_nuts_ranges(void);
+void mi_mcmc_test_gemm_nuts_last_ticks(uint64_t* ticks, uint64_t* busy_slots, uint64_t* slots);
+/* ... and the host arithmetic of its routing, which needs no device: the tick ceiling of the host loop (search: a fresh run, with the step-size search's
+ * allowance), the workspace bytes per chain and independent of the chains (n_rows = 0: the dense Gaussian), the chains per range under a budget. */
+uint64_t mi_mcmc_test_gemm_nuts_tick_ceiling(uint32_t max_tree_depth, uint64_t n_draws, int search);
+uint64_t mi_mcmc_test_gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth);
+uint64_t mi_mcmc_test_gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows);
+uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint64_t chain_bytes, uint64_t fixed_bytes, uint64_t budget);
 #ifdef __cplusplus
 }
 #endif
