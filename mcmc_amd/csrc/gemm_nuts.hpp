@@ -17,9 +17,9 @@
 //                         origin of a doubling, with the chain's signed step (nuts.cpp:139-154, the roundings of nuts_lds.hpp's DIAGM tick and of literal.hpp);
 //                         the draw's Philox normals for the chain's own draw index and p = sqrt(m) z (:200-202); the initial values and z_init (:160-168).
 //                         It writes the position buffer the product reads.
-//   the product(s)        gemm_step_kernel<12, TGT>: the second half-kick with the step read per column, the gradient stored; a column whose chain takes no point
+//   the product(s)        gemm_step_kernel<EP_NUTS = 12, TGT> (gradient_product): the second half-kick with the step read per column, the gradient stored; a column whose chain takes no point
 //                         this tick leaves memory untouched.
-//   nuts_point_kernel     one thread per (chain, dimension class j of 4), the layout of gemm_pre_kernel: U and K of the new point in the engine's order beyond d = 512
+//   nuts_point_kernel     one thread per (chain, dimension class j of 4), the layout of gemm_pre_kernel (class_lane): U and K of the new point in the engine's order beyond d = 512
 //                         (four strided fma chains, (q0 + q2) + (q1 + q3), one block), the U-turn tests this point closes against the (theta, p) records of
 //                         earlier points, the record store; then on the chain's scalars (each of the chain's four lanes keeps a private copy and computes the same):
 //                         the walk through the leaves the point unblocks (nuts.ipp:212-239: the same merges, the same uniform per merge from the same Philox slot,
@@ -94,7 +94,7 @@ __global__ void nuts_init_kernel(const TickParams prm)
     if (blockIdx.x == 0 && threadIdx.x == 0) { *prm.running = (uint32_t)prm.C; *prm.points = 0ull; }
 }
 
-// one Philox slot -- two dimensions, the canonical slot <-> dimension map of gemm_normals_kernel -- per thread
+// one Philox slot -- two dimensions (slot_dims) -- per thread
 __global__ __launch_bounds__(256) void nuts_prepare_kernel(const TickParams prm)
 {
     using namespace nuts;
@@ -103,15 +103,13 @@ __global__ __launch_bounds__(256) void nuts_prepare_kernel(const TickParams prm)
     const uint32_t mode = prm.colmode[c];
     if (mode == CM_IDLE) return;
     const uint32_t slot = blockIdx.y;
-    const uint32_t dim[2] = {8u * (slot >> 2) + (slot & 3u), 8u * (slot >> 2) + (slot & 3u) + 4u};
+    uint32_t dim[2];
+    slot_dims(slot, dim[0], dim[1]);
     const double ec = prm.ecol[c];
     const double* prev = prm.pbsel[c] ? prm.prev1 : prm.prev0;
     double z[2] = {0.0, 0.0};
-    if (mode == CM_DRAW || mode == CM_INIT) {
-        if (dim[0] < prm.d)
-            rng_normal_pair(prm.seed, prm.chain0 + prm.c_off + c, mode == CM_DRAW ? prm.didx[c] + prm.draw0 : 0u, slot, mode == CM_DRAW ? STREAM_NORMAL : STREAM_INIT, z[0], z[1]);
-        if (dim[1] >= prm.d) z[1] = 0.0;
-    }
+    if (mode == CM_DRAW || mode == CM_INIT)
+        slot_normal_pair(prm.seed, prm.chain0 + prm.c_off + c, mode == CM_DRAW ? prm.didx[c] + prm.draw0 : 0u, slot, mode == CM_DRAW ? STREAM_NORMAL : STREAM_INIT, true, prm.d, z[0], z[1]);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const uint32_t i = dim[h];
@@ -146,8 +144,9 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
 {
     using namespace nuts;
     using mi::lds_nuts::npt_of_dev;
-    const int lane = threadIdx.x & 63, j = lane >> 4;
-    const uint64_t c = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+    const ClassLane cl = class_lane();
+    const int lane = cl.lane, j = cl.j;
+    const uint64_t c = cl.c;
     const uint64_t Cp = prm.Cp;
     const size_t S = 4 * (size_t)Cp;
     double* const sc = prm.sc + ((size_t)j * Cp + c);
@@ -474,24 +473,47 @@ uint64_t gemm_nuts_tick_ceiling(uint32_t max_depth, uint64_t n_total, bool searc
     for (uint64_t j = 0; j < max_depth; ++j) pts += 1 + j * (j + 1) / 2;
     return 1 + (search ? (uint64_t)NUTS_SEARCH_TICKS + 1 : 0) + n_total * (1 + (uint64_t)(max_depth - 1) + pts);
 }
-// bytes of workspace per chain (column): the fixed vectors and 2 (theta, p) x gemm_nuts_points record vectors of gemm_padded_d(d) doubles, the two row-term
-// vectors of the logistic target, the scalars of the chain's four lanes, the column words
+// The workspace of a range of Cp columns (gemm_samplers.hip: Carve): first what does not depend on the chains -- the packed matrices, the counters --, then per chain the
+// fixed vectors and 2 (theta, p) x gemm_nuts_points record vectors of gemm_padded_d(d) doubles, the logistic target's two row-term vectors, the scalars, the column words
+struct NutsWs : TargetWs {
+    double* ctr;               // 32 doubles: the two counters
+    double* fix[nuts::NFIX];   // X, pm, G | prev_draw x 2, its gradient | mntm_vec | the four edge vectors
+    double* rec;
+    double *sc, *ecol;
+    uint32_t *colmode, *pbsel, *didx;
+    size_t fixed, n_doubles;   // doubles that do not depend on the chains, and all of them
+};
+static NutsWs gemm_nuts_carve(uint32_t d, uint32_t n_rows, uint32_t max_depth, uint64_t Cp, double* base)
+{
+    NutsWs w{};
+    w.l = layout_of(d, n_rows, Cp);
+    const Layout& l = w.l;
+    Carve cv{base};
+    take_matrices(cv, w);
+    w.ctr = cv.take(32);
+    w.fixed = cv.n;
+    for (double*& v : w.fix) v = cv.take(l.vec);
+    w.rec = cv.take(2 * (size_t)gemm_nuts_points(max_depth) * l.vec);
+    take_row_terms(cv, w);
+    w.sc = cv.take(4 * (size_t)nuts::SC_N * l.Cp);
+    w.ecol = cv.take(l.Cp);
+    w.colmode = reinterpret_cast<uint32_t*>(cv.take(2 * l.Cp));              // 3 Cp words in 2 Cp doubles
+    w.pbsel = w.colmode + l.Cp; w.didx = w.pbsel + l.Cp;
+    w.n_doubles = cv.n;
+    return w;
+}
+// bytes per chain (every region behind the fixed ones is a multiple of the columns: one column counts them), and of what does not depend on the chains
 size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth)
 {
-    const size_t dK = round_up(d, TK), nK = n_rows ? round_up(n_rows, TK) : 0;
-    return (((size_t)nuts::NFIX + 2 * (size_t)gemm_nuts_points(max_depth)) * dK + 2 * nK + 4 * (size_t)nuts::SC_N + 3) * sizeof(double);
+    const NutsWs w = gemm_nuts_carve(d, n_rows, max_depth, 1, nullptr);
+    return (w.n_doubles - w.fixed) * sizeof(double);
 }
-// ... and what does not depend on the chains: the packed matrices and the counters
-size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows)
-{
-    const Layout l = layout_of(d, n_rows, TN, false, false);
-    return (l.mat + 32) * sizeof(double);
-}
+size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows) { return gemm_nuts_carve(d, n_rows, 1, 1, nullptr).fixed * sizeof(double); }
 // chains per range when `budget` bytes are there for the route's own workspace: all of them (rounded up to the chain tile) if they fit, else the largest multiple
 // of 128 that does; 0: not even one tile -- the call stays on the literal kernel
 uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_bytes, size_t budget)
 {
-    const uint64_t Cp = (C + TN - 1) / TN * TN;
+    const uint64_t Cp = padded_chains(C);
     if (budget < fixed_bytes || chain_bytes == 0) return 0;
     const uint64_t fit = (budget - fixed_bytes) / chain_bytes / TN * TN;
     return fit < Cp ? fit : Cp;
@@ -500,29 +522,18 @@ uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_byt
 template <int TGT>
 static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_name)
 {
-    constexpr bool LOGIT = TGT == TGT_LOGISTIC;
     if (r.max_depth < 1 || r.max_depth > (uint32_t)nuts::MAX_DEPTH || r.C == 0) return (int)hipErrorInvalidValue;      // (the caller routes these elsewhere)
-    const Layout l = layout_of(r.d, LOGIT ? r.n_rows : 0u, r.C, false, false);
-    const uint32_t n_rec = gemm_nuts_points(r.max_depth);
-    double* base = static_cast<double*>(r.ws);
-    double* A1 = base;                                        // dense: P^T; logistic: X^T [dK][nM]
-    double* A2 = LOGIT ? A1 + (size_t)l.dK * l.nM : nullptr;  // logistic: X [nK][dM]
-    double* ctr = base + l.mat;                               // 32 doubles: the two counters
-    double* v0 = ctr + 32;
+    const uint32_t n_rows = TGT == TGT_LOGISTIC ? r.n_rows : 0u;
+    const NutsWs w = gemm_nuts_carve(r.d, n_rows, r.max_depth, padded_chains(r.C), static_cast<double*>(r.ws));
+    const Layout& l = w.l;
     TickParams tp{};
-    tp.d = r.d; tp.dK = l.dK; tp.n_rec = n_rec; tp.C = r.C; tp.Cp = l.Cp; tp.Ct = r.C_total; tp.c_off = r.c_off; tp.chain0 = r.chain0; tp.vec = l.vec;
-    tp.X = v0; tp.pm = v0 + l.vec; tp.G = v0 + 2 * l.vec; tp.prev0 = v0 + 3 * l.vec; tp.prev1 = v0 + 4 * l.vec; tp.gprev = v0 + 5 * l.vec; tp.mntm = v0 + 6 * l.vec;
-    tp.tpos_t = v0 + 7 * l.vec; tp.tpos_p = v0 + 8 * l.vec; tp.tneg_t = v0 + 9 * l.vec; tp.tneg_p = v0 + 10 * l.vec;
-    tp.rec = v0 + (size_t)nuts::NFIX * l.vec;
-    double* res = tp.rec + 2 * (size_t)n_rec * l.vec;
-    double* term = res + l.rvec;
-    tp.sc = term + l.rvec;
-    tp.ecol = tp.sc + 4 * (size_t)nuts::SC_N * l.Cp;
-    tp.colmode = reinterpret_cast<uint32_t*>(tp.ecol + l.Cp);
-    tp.pbsel = tp.colmode + l.Cp; tp.didx = tp.pbsel + l.Cp;                  // (3 Cp words in 2 Cp doubles)
-    tp.running = reinterpret_cast<uint32_t*>(ctr);
-    tp.points = reinterpret_cast<unsigned long long*>(ctr + 1);
-    tp.lk.dK = l.dK; tp.lk.nK = l.nK; tp.lk.Cp = l.Cp; tp.lk.C = r.C; tp.lk.d = r.d; tp.lk.term = term;
+    tp.d = r.d; tp.dK = l.dK; tp.n_rec = gemm_nuts_points(r.max_depth); tp.C = r.C; tp.Cp = l.Cp; tp.Ct = r.C_total; tp.c_off = r.c_off; tp.chain0 = r.chain0; tp.vec = l.vec;
+    tp.X = w.fix[0]; tp.pm = w.fix[1]; tp.G = w.fix[2]; tp.prev0 = w.fix[3]; tp.prev1 = w.fix[4]; tp.gprev = w.fix[5]; tp.mntm = w.fix[6];
+    tp.tpos_t = w.fix[7]; tp.tpos_p = w.fix[8]; tp.tneg_t = w.fix[9]; tp.tneg_p = w.fix[10];
+    tp.rec = w.rec; tp.sc = w.sc; tp.ecol = w.ecol; tp.colmode = w.colmode; tp.pbsel = w.pbsel; tp.didx = w.didx;
+    tp.running = reinterpret_cast<uint32_t*>(w.ctr);
+    tp.points = reinterpret_cast<unsigned long long*>(w.ctr + 1);
+    tp.lk.dK = l.dK; tp.lk.nK = l.nK; tp.lk.Cp = l.Cp; tp.lk.C = r.C; tp.lk.d = r.d; tp.lk.term = w.term;
     tp.m_sqrt = r.mass_tables + l.dK; tp.m_inv = r.mass_tables + 2 * (size_t)l.dK;
     tp.theta = r.theta; tp.draws = r.draws; tp.n_accept = r.n_accept; tp.n_leap_out = r.n_leap; tp.n_exec_out = r.n_exec; tp.step = r.step; tp.depth = r.depth;
     tp.adapt = r.adapt; tp.nf_flag = r.nf_flag;
@@ -530,17 +541,8 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
     tp.search_allowance = NUTS_SEARCH_TICKS;
     tp.eps_bar0 = r.eps_bar0; tp.delta = r.delta; tp.gamma = r.gamma; tp.t0 = r.t0; tp.kappa = r.kappa;
 
-    static const int attr_rc = [] { int e = step_attr<12, TGT>(); if constexpr (LOGIT) { if (!e) e = step_attr<3, TGT>(); } return e; }();
-    if (attr_rc) return attr_rc;
-    auto pack_grid = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)); };
-    if (r.pack) {                                              // (the matrices are the same for every range of a call)
-        if constexpr (LOGIT) {
-            hipLaunchKernelGGL(gemm_pack_kernel<true>, pack_grid((size_t)l.dK * l.nM), dim3(256), 0, st, r.X, r.n_rows, r.d, l.dK, l.nM, A1);
-            hipLaunchKernelGGL(gemm_pack_kernel<false>, pack_grid((size_t)l.nK * l.dM), dim3(256), 0, st, r.X, r.n_rows, r.d, l.nK, l.dM, A2);
-        } else {
-            hipLaunchKernelGGL(gemm_pack_kernel<true>, pack_grid((size_t)l.dK * l.dM), dim3(256), 0, st, r.P, r.d, r.d, l.dK, l.dM, A1);
-        }
-    }
+    if (int e = step_attrs<TGT>()) return e;
+    if (r.pack) pack_target<TGT>(w, r.P, r.X, r.n_rows, r.d, st);      // (the matrices are the same for every range of a call)
     hipLaunchKernelGGL(nuts_init_kernel, dim3((unsigned)std::min<size_t>((4 * l.Cp + 255) / 256, 65535)), dim3(256), 0, st, tp);
     GEMM_TRY(hipGetLastError());
 
@@ -552,16 +554,7 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
         hipLaunchKernelGGL(nuts_prepare_kernel, prep_grid, dim3(256), 0, s, tp);
         StepParams sp{};
         sp.n_ntiles = n_ntiles; sp.Cp = l.Cp; sp.pm = tp.pm; sp.pos = tp.X; sp.g_out = tp.G; sp.ecol = tp.ecol; sp.colmode = tp.colmode;
-        if constexpr (LOGIT) {
-            StepParams se = sp;                               // eta = X Theta and the row terms
-            se.At = A1; se.Bm = tp.X; se.Kp = l.dK; se.ldA = l.nM; se.M_store = l.nK; se.term_out = term;
-            if (int e = launch_step<3, TGT>(se, s)) return e;
-            hipLaunchKernelGGL(gemm_rowterm_kernel, dim3((unsigned)std::min<size_t>((l.rvec + 255) / 256, 1u << 20)), dim3(256), 0, s, r.y, r.n_rows, l.nK, l.Cp, res, term);
-            sp.At = A2; sp.Bm = res; sp.Kp = l.nK; sp.ldA = l.dM; sp.M_store = l.dK;       // X^T (y - sigmoid(eta)), rows ascending
-        } else {
-            sp.At = A1; sp.Bm = tp.X; sp.Kp = l.dK; sp.ldA = l.dM; sp.M_store = l.dK;
-        }
-        if (int e = launch_step<12, TGT>(sp, s)) return e;
+        if (int e = gradient_product<TGT>(w, r.y, r.n_rows, tp.X, EP_NUTS, sp, s)) return e;
         hipLaunchKernelGGL(nuts_point_kernel<TGT>, dim3(cls_grid), dim3(256), 0, s, tp);
         return (int)hipGetLastError();
     };
@@ -569,23 +562,7 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
     // one tick captured once (a linear graph), replayed; the host polls the counter of running chains every NUTS_POLL_TICKS ticks, up to the ceiling
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    bool graphed = false;
-    if (r.use_graph) {
-        static hipStream_t cap_st = [] { hipStream_t s = nullptr; if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr; return s; }();
-        static std::mutex cap_mu;                          // (one capture stream for the process: two host threads must not capture on it at once)
-        std::lock_guard<std::mutex> cap_lk(cap_mu);
-        if (cap_st != nullptr && hipStreamBeginCapture(cap_st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int e = enqueue_tick(cap_st);
-            const hipError_t ec = hipStreamEndCapture(cap_st, &graph);
-            if (e == 0 && ec == hipSuccess && graph != nullptr && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) graphed = true;
-            else {
-                if (exec) (void)hipGraphExecDestroy(exec);
-                if (graph) (void)hipGraphDestroy(graph);
-                exec = nullptr; graph = nullptr;
-                (void)hipGetLastError();
-            }
-        } else (void)hipGetLastError();
-    }
+    const bool graphed = r.use_graph && capture_and_instantiate(enqueue_tick, &graph, &exec);
     const uint64_t ceiling = gemm_nuts_tick_ceiling(r.max_depth, (uint64_t)r.n_burnin + r.n_keep, r.draw0 == 0);
     uint64_t ticks = 0;
     uint32_t running = (uint32_t)r.C;
@@ -599,12 +576,12 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
     }
     unsigned long long points = 0;
     if (rc == 0) rc = (int)hipMemcpy(&points, tp.points, sizeof(points), hipMemcpyDeviceToHost);
-    if (graphed) { (void)hipStreamSynchronize(st); (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); }
+    if (graphed) { const int e = release_graph(st, graph, exec); if (rc == 0) rc = e; }
     if (rc) return rc;
     r.ticks_run = ticks; r.points_taken = points; r.still_running = running;
     if (kernel_name) {
         static thread_local char name[112];
-        snprintf(name, sizeof(name), "gemm_step_kernel<12, %d> (nuts, memoised%s%s)", TGT, graphed ? ", graph" : "", r.diag_mass ? ", diagonal precond_mat" : "");
+        snprintf(name, sizeof(name), "gemm_step_kernel<%d, %d> (nuts, memoised%s%s)", (int)EP_NUTS, TGT, graphed ? ", graph" : "", r.diag_mass ? ", diagonal precond_mat" : "");
         *kernel_name = name;
     }
     return 0;
