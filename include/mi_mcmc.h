@@ -578,6 +578,36 @@ int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_ke
                              double* mean /* [d] host, may be NULL */, double* cov /* [d*d] host, row-major, may be NULL */,
                              void* stream);
 
+/* Exact pooled order statistics and quantiles of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: the samples of
+ * dimension i are the K = n_keep * C values x[t][i][c], pooled over draws and chains.  Outputs are HOST arrays.  Blocking.  Workspace: the
+ * stream's cached one (mi_mcmc_release_workspace).  No CPU path: no device is MI_ERR_NO_DEVICE.  MI_ERR_BAD_ARG, before any HIP call: a NULL
+ * slab, ranks, probs or out; d = 0; K = 0; n_keep or n_chains beyond 32 bits; d > 65 536; n_ranks = 0 or > MI_ORDER_STATS_MAX_RANKS; n_probs = 0
+ * or > 16; a rank >= K; a probability outside [0, 1] or NaN.
+ * ORDER.  Values are ordered by a 64-bit key; with u the bits of x:
+ *   key(x) = 0xFFFFFFFFFFFFFFFF   for any NaN, of either sign and any payload
+ *          = ~u                   if the sign bit of u is set
+ *          = u | 2^63             otherwise
+ * that is -inf < negatives < -0.0 < +0.0 < positives < +inf < NaN: numpy's sort order with the sign of zero made definite.
+ * ORDER STATISTIC.  out[a][i] is the value whose key is the ranks[a]-th smallest (0-based) of dimension i's K keys -- exact, by a radix
+ * selection on the keys (mcmc_amd/csrc/draws_select.hip) whose counts are integers: the result depends on no grid, timing or atomic order.  A
+ * NaN comes back as the canonical quiet NaN 0x7FF8000000000000.  ranks may be unsorted and may repeat.
+ * QUANTILE (Hyndman-Fan type 7, numpy's method="linear"), on the host from two order statistics per probability, fp64, every operation
+ * rounded once, nothing contracted:
+ *   h  = p * (double)(K - 1)
+ *   lo = floor(h)                 (and at most K - 1: p = 1 with a K - 1 that the conversion rounded up)
+ *   g  = h - (double)lo
+ *   hi = min(lo + 1, K - 1)
+ *   q  = (g == 0) ? x_lo : x_lo + g * (x_hi - x_lo)
+ * Non-finite samples propagate by the IEEE rules through that one expression and nowhere else (g == 0 gives x_lo whatever x_hi is).
+ * The numpy statement of all of this is mcmc_amd/quantiles.py. */
+#define MI_ORDER_STATS_MAX_RANKS 32
+int mi_mcmc_draws_order_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                              const uint64_t* ranks /* host, n_ranks values, each < K */, uint32_t n_ranks,
+                              double* out /* host, [n_ranks][d] */, void* stream);
+int mi_mcmc_draws_quantiles(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                            const double* probs /* host, n_probs values in [0, 1] */, uint32_t n_probs /* <= 16 */,
+                            double* out /* host, [n_probs][d] */, void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

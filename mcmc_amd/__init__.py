@@ -92,6 +92,7 @@ EXPORTS = [
     "mi_mcmc_allgather_draws_rank_major", "mi_mcmc_rank_major_index", "mi_mcmc_allgather_draws_begin", "mi_mcmc_allgather_draws_wait",
     "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
     "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
+    "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -718,6 +719,39 @@ def draws_covariance(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, st
     _check(lib().mi_mcmc_draws_covariance(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
                                           C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(stream or 0)))
     return mean, cov
+
+
+def _slab_shape(draws, n_keep, d, n_chains, mem):
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d, n_chains = draws.shape
+    return draws, int(n_keep), int(d), int(n_chains)
+
+
+def draws_order_stats(draws, ranks, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None):
+    """mi_mcmc_draws_order_stats: out[a, i] = the value with the ranks[a]-th smallest key (0-based) among the n_keep * C pooled samples of
+    dimension i of a slab [n_keep, d, C] (numpy array, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape) -- exact; the order
+    is that of mcmc_amd.quantiles.key.  Up to 32 ranks, unsorted or repeated.  Returns [len(ranks), d]."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    ranks = np.ascontiguousarray(ranks, dtype=np.uint64).ravel()
+    out = np.zeros((ranks.size, d))
+    _check(lib().mi_mcmc_draws_order_stats(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
+                                           C.c_void_p(ranks.ctypes.data), C.c_uint32(ranks.size), C.c_void_p(out.ctypes.data), C.c_void_p(stream or 0)))
+    return out
+
+
+def draws_quantiles(draws, probs, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None):
+    """mi_mcmc_draws_quantiles: out[a, i] = the type-7 quantile (numpy's method="linear") at probs[a] of the pooled samples of dimension i,
+    from two exact order statistics on the device (mcmc_amd.quantiles.quantiles_ref, bit for bit).  Up to 16 probabilities.  Returns
+    [len(probs), d]."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    probs = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    out = np.zeros((probs.size, d))
+    _check(lib().mi_mcmc_draws_quantiles(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
+                                         C.c_void_p(probs.ctypes.data), C.c_uint32(probs.size), C.c_void_p(out.ctypes.data), C.c_void_p(stream or 0)))
+    return out
 
 
 def draws_to_chain_major_device(draws, n_keep, d, n_chains, out, stream=None):

@@ -38,6 +38,7 @@
 #include "launchers.hpp"
 #include "gemm_samplers.hpp"
 #include "draws_cov.hpp"
+#include "draws_select.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
 #include "tile_samplers.hpp"
@@ -2334,6 +2335,103 @@ int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_ke
     if (mean) HIP_TRY(hipMemcpyAsync(mean, ws.as<double>() + plan.o_mean, d * 8, hipMemcpyDeviceToHost, st));
     if (cov) HIP_TRY(hipMemcpyAsync(cov, ws.as<double>() + plan.o_cov, d * d * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));                   // blocking: the outputs are the caller's host arrays, the staged slab and the workspace are ours
+    return MI_OK;
+}
+
+namespace {
+// The checks that mi_mcmc_draws_order_stats and mi_mcmc_draws_quantiles share: they need no device
+int order_stats_check(const char* who, const double* draws_kdc, uint64_t n_keep, uint64_t d, uint64_t n_chains, const double* out)
+{
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
+    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (n_keep * n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = 0, at least 1 sample is needed", who);
+    if (d > mi::dsel::SEL_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::dsel::SEL_MAX_D);
+    return MI_OK;
+}
+
+// out [n_ranks][d] on the host <- the order statistics of a checked call (draws_select.hip); blocking
+int order_stats_run(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const uint64_t* ranks, uint32_t n_ranks, double* out,
+                    void* stream)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DevBuf staged;
+    const double* x = draws_kdc;
+    if (mem == MI_MEM_HOST) {
+        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
+        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
+        x = staged.as<double>();
+    }
+    mi::dsel::SelRanks r{};
+    for (uint32_t a = 0; a < n_ranks; ++a) r.r[a] = ranks[a];
+    const mi::dsel::SelPlan plan = mi::dsel::sel_plan(n_keep, d, n_chains, n_ranks);
+    WsLease ws;
+    int rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    HIP_TRY((hipError_t)mi::dsel::sel_run(x, n_keep, d, n_chains, r, n_ranks, plan, ws.p, st));
+    HIP_TRY(hipMemcpyAsync(out, ws.as<char>() + plan.o_out, (size_t)n_ranks * d * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // blocking: out is the caller's host array, the staged slab and the workspace are ours
+    return MI_OK;
+}
+}  // namespace
+
+// The ranks[a]-th smallest key of every dimension of a slab [n_keep][d][C], as a value (the key, the order: include/mi_mcmc.h)
+int mi_mcmc_draws_order_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const uint64_t* ranks, uint32_t n_ranks,
+                              double* out, void* stream)
+{
+    const char* who = "draws_order_stats";
+    int rc = order_stats_check(who, draws_kdc, n_keep, d, n_chains, out);
+    if (rc) return rc;
+    if (!ranks) return fail(MI_ERR_BAD_ARG, "%s: ranks is NULL", who);
+    if (n_ranks == 0 || n_ranks > MI_ORDER_STATS_MAX_RANKS) return fail(MI_ERR_BAD_ARG, "%s: n_ranks = %u, must be 1 .. %d", who, n_ranks, MI_ORDER_STATS_MAX_RANKS);
+    const uint64_t K = n_keep * n_chains;
+    for (uint32_t a = 0; a < n_ranks; ++a)
+        if (ranks[a] >= K) return fail(MI_ERR_BAD_ARG, "%s: ranks[%u] = %llu is not below K = %llu", who, a, (unsigned long long)ranks[a], (unsigned long long)K);
+    return order_stats_run(draws_kdc, mem, n_keep, d, n_chains, ranks, n_ranks, out, stream);
+}
+
+// Type-7 quantiles from two order statistics per probability; the arithmetic below IS include/mi_mcmc.h's statement (this file is compiled with
+// -ffp-contract=off: nothing is fused)
+int mi_mcmc_draws_quantiles(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const double* probs, uint32_t n_probs,
+                            double* out, void* stream)
+{
+    const char* who = "draws_quantiles";
+    int rc = order_stats_check(who, draws_kdc, n_keep, d, n_chains, out);
+    if (rc) return rc;
+    if (!probs) return fail(MI_ERR_BAD_ARG, "%s: probs is NULL", who);
+    if (n_probs == 0 || n_probs > MI_ORDER_STATS_MAX_RANKS / 2) return fail(MI_ERR_BAD_ARG, "%s: n_probs = %u, must be 1 .. %d", who, n_probs, MI_ORDER_STATS_MAX_RANKS / 2);
+    for (uint32_t a = 0; a < n_probs; ++a)
+        if (!(probs[a] >= 0.0 && probs[a] <= 1.0)) return fail(MI_ERR_BAD_ARG, "%s: probs[%u] = %g is not in [0, 1]", who, a, probs[a]);
+    const uint64_t K = n_keep * n_chains;
+    uint64_t ranks[MI_ORDER_STATS_MAX_RANKS];
+    double g[MI_ORDER_STATS_MAX_RANKS / 2];
+    for (uint32_t a = 0; a < n_probs; ++a) {
+        const double h = probs[a] * (double)(K - 1);
+        const double fl = std::floor(h);
+        const uint64_t lo = fl >= (double)(K - 1) ? K - 1 : (uint64_t)fl;
+        g[a] = h - (double)lo;
+        ranks[2 * a] = lo;
+        ranks[2 * a + 1] = lo + 1 < K ? lo + 1 : K - 1;
+    }
+    std::vector<double> os((size_t)2 * n_probs * d);
+    rc = order_stats_run(draws_kdc, mem, n_keep, d, n_chains, ranks, 2 * n_probs, os.data(), stream);
+    if (rc) return rc;
+    for (uint32_t a = 0; a < n_probs; ++a) {
+        const double* x_lo = os.data() + (size_t)(2 * a) * d;
+        const double* x_hi = x_lo + d;
+        for (uint64_t i = 0; i < d; ++i) {
+            if (g[a] == 0.0) out[(size_t)a * d + i] = x_lo[i];
+            else {
+                const double diff = x_hi[i] - x_lo[i];
+                const double prod = g[a] * diff;
+                out[(size_t)a * d + i] = x_lo[i] + prod;
+            }
+        }
+    }
     return MI_OK;
 }
 
