@@ -10,6 +10,7 @@
 
 #include "host_common.hpp"
 #include "det_math.hpp"
+#include "settings_host.hpp"
 #include "callback_mode.hpp"
 
 using mi::host::fail;
@@ -243,10 +244,10 @@ int mi_mcmc_mala_run_callback(const double* initial_vals, uint64_t d, mi_log_ker
     if (settings->vals_bound || settings->precond_mat)     // the literal kernel with the callback as its target (literal.hpp LIT_CALLBACK)
         return mi::host::literal_run_callback("mala", 1, initial_vals, d, cb, target_data, nullptr, nullptr, settings, draws_out, n_accept_draws, nullptr);
     const uint64_t n_burnin = settings->n_burnin_draws, n_keep = settings->n_keep_draws, n_total = n_burnin + n_keep;
-    const double eps = settings->step_size, s2 = eps * eps, rs = 1.0 / s2;
-    double log_det = 0.0;                                // LOG_DET(eps^2 I) = sum_i 2 log sqrt(s2), i ascending (oracle: orc_log_det_from_chol)
-    for (uint64_t i = 0; i < d; ++i) log_det = log_det + 2.0 * mi::det_log(__builtin_sqrt(s2));
-    const double cons_term = -0.5 * (double)d * 1.83787706640934548356;
+    const double eps = settings->step_size, s2 = eps * eps;
+    mi::settings::MalaSigma sg;                          // LOG_DET(eps^2 I) = sum_i 2 log sqrt(s2), i ascending (oracle: orc_log_det_from_chol)
+    (void)mi::settings::mala_sigma(d, eps, 0, nullptr, sg);
+    const double rs = sg.rs, log_det = sg.log_det, cons_term = sg.cons_term;
     enum { PREV = 0, PROP, Z, GRAD, MEAN_PREV, MEAN_PROP, TMP0, TMP1, NVEC };
     CbMachine m;
     rc = m.init(d, NVEC, cb, target_data);

@@ -1,15 +1,16 @@
 // literal_host.hpp -- host-side preparation of a literal replay (literal.hpp): bounds types, the preconditioner in the form the
 // literal kernels read (identity / diagonal vectors / dense matrices with INV and CHOL_LOWER from the host), and, for unbounded
-// mala, INV / LOG_DET of the constant Sigma = eps^2 M -- all in the operation order the oracle states (host_linalg.hpp).
+// mala, INV / LOG_DET of the constant Sigma = eps^2 M -- composed from the derivations of settings_host.hpp.
 // Used by the C ABI (mi_mcmc.hip) and by the host test shim (tests/lit_host.hip), so that the CPU tests exercise this code too.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
-#include "host_linalg.hpp"
 #include "literal.hpp"
+#include "settings_host.hpp"
 
 namespace mi {
 namespace lit {
@@ -37,59 +38,26 @@ inline void lit_transpose(const double* in, size_t rows, size_t cols, std::vecto
 inline int lit_prepare(int algo, uint32_t d, double eps, int vals_bound, const double* lower, const double* upper,
                        const double* precond_mat, LitPrep& o)
 {
-    o.bt.assign(d, 1); o.lb.assign(d, 0.0); o.ub.assign(d, 0.0);
-    if (vals_bound)
-        for (uint32_t i = 0; i < d; ++i) {       // determine_bounds_type.hpp:27-57
-            o.lb[i] = lower[i]; o.ub[i] = upper[i];
-            const bool fl = std::isfinite(lower[i]), fu = std::isfinite(upper[i]);
-            o.bt[i] = (fl && fu) ? 4 : (fl && !fu) ? 2 : (!fl && fu) ? 3 : 1;
-        }
-    o.precond = 0;
-    if (precond_mat) {
-        o.precond = 1;
-        for (uint32_t i = 0; i < d && o.precond == 1; ++i)
-            for (uint32_t k = 0; k < d; ++k)
-                if (i != k && precond_mat[(size_t)i * d + k] != 0.0) { o.precond = 2; break; }
-        if (o.precond == 1) {
-            o.m.resize(d); o.m_sqrt.resize(d); o.m_inv.resize(d);
-            for (uint32_t i = 0; i < d; ++i) {
-                const double v = precond_mat[(size_t)i * d + i];
-                o.m[i] = v; o.m_sqrt[i] = __builtin_sqrt(v); o.m_inv[i] = 1.0 / v;
-            }
-        } else {
-            std::vector<double> Minv, Lc;
-            if (int rc = host_inverse(precond_mat, d, Minv)) return rc;
-            if (int rc = host_cholesky_lower(precond_mat, d, Lc)) return rc;
-            lit_transpose(precond_mat, d, d, o.Mfull);
-            lit_transpose(Minv.data(), d, d, o.Minv);
-            lit_transpose(Lc.data(), d, d, o.Lchol);
-        }
+    namespace S = mi::settings;
+    o.bt.resize(d); o.lb.resize(d); o.ub.resize(d);
+    S::bounds_tables(d, vals_bound, lower, upper, o.bt.data(), o.lb.data(), o.ub.data());
+    o.precond = S::precond_kind(precond_mat, d);
+    if (o.precond == 1) {
+        o.m.resize(d); o.m_sqrt.resize(d); o.m_inv.resize(d);
+        S::diag_mass(precond_mat, d, o.m.data(), o.m_sqrt.data(), o.m_inv.data());
+    } else if (o.precond == 2) {
+        std::vector<double> Minv, Lc;
+        if (int rc = S::dense_mass(precond_mat, d, &Minv, Lc)) return rc;
+        lit_transpose(precond_mat, d, d, o.Mfull);
+        lit_transpose(Minv.data(), d, d, o.Minv);
+        lit_transpose(Lc.data(), d, d, o.Lchol);
     }
     if (algo == 1) {
-        const double s2 = eps * eps;
-        o.rs = 1.0 / s2;
-        o.cons_term = -0.5 * (double)d * LIT_LOG_2PI;
-        double ld = 0.0;
-        if (o.precond == 0) {
-            const double lii = __builtin_sqrt(s2);
-            for (uint32_t i = 0; i < d; ++i) ld = ld + 2.0 * det_log(lii);
-        } else if (o.precond == 1) {
-            o.sinv_diag.resize(d);
-            for (uint32_t i = 0; i < d; ++i) {
-                const double sig = s2 * o.m[i];
-                o.sinv_diag[i] = 1.0 / sig;
-                ld = ld + 2.0 * det_log(__builtin_sqrt(sig));
-            }
-        } else {
-            std::vector<double> Sigma((size_t)d * d), Ls;
-            for (size_t i = 0; i < (size_t)d * d; ++i) Sigma[i] = s2 * precond_mat[i];
-            std::vector<double> Sinv;
-            if (int rc = host_inverse(Sigma.data(), d, Sinv)) return rc;
-            lit_transpose(Sinv.data(), d, d, o.Sinv);
-            if (int rc = host_cholesky_lower(Sigma.data(), d, Ls)) return rc;
-            for (uint32_t i = 0; i < d; ++i) ld = ld + 2.0 * det_log(Ls[(size_t)i * d + i]);
-        }
-        o.log_det = ld;
+        S::MalaSigma sg;
+        if (int rc = S::mala_sigma(d, eps, o.precond, o.precond == 1 ? o.m.data() : precond_mat, sg)) return rc;
+        o.rs = sg.rs; o.cons_term = sg.cons_term; o.log_det = sg.log_det;
+        o.sinv_diag = std::move(sg.sinv_diag);
+        if (o.precond == 2) lit_transpose(sg.Sinv.data(), d, d, o.Sinv);
     }
     return 0;
 }

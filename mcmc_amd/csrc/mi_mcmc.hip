@@ -41,6 +41,7 @@
 #include "draws_select.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
+#include "settings_host.hpp"
 #include "tile_samplers.hpp"
 
 // round time of the few-chain launch shapes of the plain HMC kernel relative to the default (two waves per SIMD), d = 128
@@ -274,6 +275,18 @@ void lit_common(mi::lit::LitParams& p, const mi_settings* s, const mi_chains* de
     p.work = r.work; p.work_stride = r.stride;
 }
 
+// One table on the device: n entries of src, padded to n_padded entries with `fill` (settings_host.hpp: pad_table).  The buffer dies with the
+// DevBuf, so a caller that uploaded anything synchronises the stream before the DevBuf goes out of scope.
+template <class T>
+int upload_padded(DevBuf& b, const T* src, size_t n, size_t n_padded, T fill)
+{
+    std::vector<T> padded;
+    if (n_padded > n) { padded.resize(n_padded); mi::settings::pad_table(src, n, n_padded, fill, padded.data()); src = padded.data(); }
+    HIP_TRY(b.alloc(n_padded * sizeof(T)));
+    HIP_TRY(hipMemcpy(b.p, src, n_padded * sizeof(T), hipMemcpyHostToDevice));
+    return MI_OK;
+}
+
 // device copies of a LitPrep (literal_host.hpp) and the LitParams pointers into them.  The buffers die with the LitDev, so a caller
 // that uploaded anything synchronises the stream before it returns.
 struct LitDev {
@@ -282,35 +295,25 @@ struct LitDev {
 };
 int lit_upload(const mi::lit::LitPrep& pr, uint32_t d, bool want_bounds, LitDev& dv, mi::lit::LitParams& p)
 {
-    auto up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-        HIP_TRY(b.alloc(bytes));
-        HIP_TRY(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-        dv.any = true;
-        return MI_OK;
+    auto up = [&](DevBuf& b, const std::vector<double>& v, const double*& out) -> int {
+        const int rc = upload_padded(b, v.data(), v.size(), v.size(), 0.0);
+        dv.any = true; out = b.as<double>();
+        return rc;
     };
     int rc;
     p.precond = pr.precond;
     p.rs = pr.rs; p.log_det = pr.log_det; p.cons_term = pr.cons_term;
     if (want_bounds) {
-        if ((rc = up(dv.bt, pr.bt.data(), d * sizeof(int)))) return rc;
-        if ((rc = up(dv.lb, pr.lb.data(), d * 8))) return rc;
-        if ((rc = up(dv.ub, pr.ub.data(), d * 8))) return rc;
-        p.vals_bound = 1; p.btype = dv.bt.as<int>(); p.lb = dv.lb.as<double>(); p.ub = dv.ub.as<double>();
+        if ((rc = upload_padded(dv.bt, pr.bt.data(), d, d, 1)) || (rc = up(dv.lb, pr.lb, p.lb)) || (rc = up(dv.ub, pr.ub, p.ub))) return rc;
+        p.vals_bound = 1; p.btype = dv.bt.as<int>();
     }
     if (pr.precond == 1) {
-        if ((rc = up(dv.m, pr.m.data(), d * 8))) return rc;
-        if ((rc = up(dv.ms, pr.m_sqrt.data(), d * 8))) return rc;
-        if ((rc = up(dv.mi, pr.m_inv.data(), d * 8))) return rc;
-        p.m = dv.m.as<double>(); p.m_sqrt = dv.ms.as<double>(); p.m_inv = dv.mi.as<double>();
+        if ((rc = up(dv.m, pr.m, p.m)) || (rc = up(dv.ms, pr.m_sqrt, p.m_sqrt)) || (rc = up(dv.mi, pr.m_inv, p.m_inv))) return rc;
     } else if (pr.precond == 2) {
-        const size_t mb = (size_t)d * d * 8;
-        if ((rc = up(dv.Mfull, pr.Mfull.data(), mb))) return rc;
-        if ((rc = up(dv.Lchol, pr.Lchol.data(), mb))) return rc;
-        if ((rc = up(dv.Minv, pr.Minv.data(), mb))) return rc;
-        p.Mfull = dv.Mfull.as<double>(); p.Lchol = dv.Lchol.as<double>(); p.Minv = dv.Minv.as<double>();
+        if ((rc = up(dv.Mfull, pr.Mfull, p.Mfull)) || (rc = up(dv.Lchol, pr.Lchol, p.Lchol)) || (rc = up(dv.Minv, pr.Minv, p.Minv))) return rc;
     }
-    if (!pr.sinv_diag.empty()) { if ((rc = up(dv.sinv_diag, pr.sinv_diag.data(), d * 8))) return rc; p.sinv_diag = dv.sinv_diag.as<double>(); }
-    if (!pr.Sinv.empty()) { if ((rc = up(dv.Sinv, pr.Sinv.data(), (size_t)d * d * 8))) return rc; p.Sinv = dv.Sinv.as<double>(); }
+    if (!pr.sinv_diag.empty() && (rc = up(dv.sinv_diag, pr.sinv_diag, p.sinv_diag))) return rc;
+    if (!pr.Sinv.empty() && (rc = up(dv.Sinv, pr.Sinv, p.Sinv))) return rc;
     return MI_OK;
 }
 
@@ -575,51 +578,35 @@ struct GeneralTables {
     bool active = false;
     bool dense = false;                       // precond_mat has off-diagonal entries: INV / CHOL_LOWER as dense matrices
     DevBuf minv_full, l_full;
-    std::vector<double> m, m_sqrt, m_inv;     // host copies (diagonal)
-    DevBuf bt, lb, ub, m_dev, ms_dev, mi_dev;
+    std::vector<double> m, m_sqrt, m_inv;     // host copies: the diagonal (of a DENSE matrix too), ones for the identity
+    std::vector<double> L;                    // host copy of CHOL_LOWER (dense), row-major
+    DevBuf bt, lb, ub, ms_dev, mi_dev;
+    DevBuf m_dev;                             // mala alone reads m on the device: upload_m()
+    int upload_m() { return upload_padded(m_dev, m.data(), m.size(), m.size(), 1.0); }
 };
 
 int general_tables(const char* who, const mi_settings* s, uint64_t d, GeneralTables& g, bool allow_dense = false, bool dense_beyond_64 = false)
 {
+    namespace S = mi::settings;
     g.active = s->vals_bound != 0 || s->precond_mat != nullptr;
     if (!g.active) return MI_OK;
     if (d > 128) return fail(MI_ERR_UNSUPPORTED, "%s: vals_bound / precond_mat with d > 128 is not implemented", who);
     if (s->vals_bound && (!s->lower_bounds || !s->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
     g.m.assign(d, 1.0); g.m_sqrt.assign(d, 1.0); g.m_inv.assign(d, 1.0);
-    if (s->precond_mat)
-        for (uint64_t i = 0; i < d; ++i)
-            for (uint64_t k = 0; k < d; ++k) {
-                const double v = s->precond_mat[i * d + k];
-                if (i != k && v != 0.0) {
-                    if (!allow_dense) return fail(MI_ERR_UNSUPPORTED, "%s: only a diagonal precond_mat is implemented on the device path", who);
-                    g.dense = true;
-                }
-                if (i == k) { g.m[i] = v; g.m_sqrt[i] = __builtin_sqrt(v); g.m_inv[i] = 1.0 / v; }
-            }
+    g.dense = S::precond_kind(s->precond_mat, d) == 2;
+    if (g.dense && !allow_dense) return fail(MI_ERR_UNSUPPORTED, "%s: only a diagonal precond_mat is implemented on the device path", who);
+    if (s->precond_mat) S::diag_mass(s->precond_mat, d, g.m.data(), g.m_sqrt.data(), g.m_inv.data());
+    int rc;
     if (g.dense) {
         if (d > 64 && !dense_beyond_64) return fail(MI_ERR_UNSUPPORTED, "%s: a dense precond_mat / cov_mat is implemented for d <= 64 (diagonal: d <= 128)", who);
-        std::vector<double> Minv, L;
-        int rcu = host_inverse(s->precond_mat, d, Minv); if (rcu) return rcu;
-        rcu = host_cholesky_lower(s->precond_mat, d, L); if (rcu) return rcu;
-        rcu = upload_matrix(Minv, d, g.minv_full); if (rcu) return rcu;
-        rcu = upload_matrix(L, d, g.l_full); if (rcu) return rcu;
+        std::vector<double> Minv;
+        if ((rc = S::dense_mass(s->precond_mat, d, &Minv, g.L)) || (rc = upload_matrix(Minv, d, g.minv_full)) || (rc = upload_matrix(g.L, d, g.l_full))) return rc;
     }
-    std::vector<int> bt(d, 1);
-    std::vector<double> lbv(d, 0.0), ubv(d, 0.0);
-    if (s->vals_bound)
-        for (uint64_t i = 0; i < d; ++i) {
-            lbv[i] = s->lower_bounds[i]; ubv[i] = s->upper_bounds[i];
-            const bool fl = std::isfinite(lbv[i]), fu = std::isfinite(ubv[i]);
-            bt[i] = (fl && fu) ? 4 : (fl && !fu) ? 2 : (!fl && fu) ? 3 : 1;
-        }
-    HIP_TRY(g.bt.alloc(d * sizeof(int))); HIP_TRY(g.lb.alloc(d * 8)); HIP_TRY(g.ub.alloc(d * 8));
-    HIP_TRY(g.m_dev.alloc(d * 8)); HIP_TRY(g.ms_dev.alloc(d * 8)); HIP_TRY(g.mi_dev.alloc(d * 8));
-    HIP_TRY(hipMemcpy(g.bt.p, bt.data(), d * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.lb.p, lbv.data(), d * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.ub.p, ubv.data(), d * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.m_dev.p, g.m.data(), d * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.ms_dev.p, g.m_sqrt.data(), d * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(g.mi_dev.p, g.m_inv.data(), d * 8, hipMemcpyHostToDevice));
+    std::vector<int> bt(d);
+    std::vector<double> lbv(d), ubv(d);
+    S::bounds_tables(d, s->vals_bound ? 1 : 0, s->lower_bounds, s->upper_bounds, bt.data(), lbv.data(), ubv.data());
+    if ((rc = upload_padded(g.bt, bt.data(), d, d, 1)) || (rc = upload_padded(g.lb, lbv.data(), d, d, 0.0)) || (rc = upload_padded(g.ub, ubv.data(), d, d, 0.0))
+        || (rc = upload_padded(g.ms_dev, g.m_sqrt.data(), d, d, 1.0)) || (rc = upload_padded(g.mi_dev, g.m_inv.data(), d, d, 1.0))) return rc;
     return MI_OK;
 }
 
@@ -802,43 +789,23 @@ uint64_t serve_callbacks(const mi::lit::LitMailbox& mb, uint32_t d, mi_log_kerne
 }
 }  // namespace
 
-// a diagonal precond_mat for the LDS-streamed hmc kernels: sqrt(m) and 1 / m on the device, padded with ones to 512 entries
-struct DiagMass { DevBuf ms, mi; };
-int diag_mass_upload(const mi_settings* settings, uint64_t d, DiagMass& t)
+// mala with a diagonal precond_mat on the LDS-streamed kernels: m, sqrt(m), INV(eps^2 M) (padded with ones to 512 entries) and LOG_DET(eps^2 M)
+// (settings_host.hpp)
+struct MalaDiagMass { DevBuf m, ms, sinv; };
+int mala_diag_tables(const mi_settings* settings, uint64_t d, MalaDiagMass& t, mi::LogitParams& q)
 {
-    std::vector<double> ms(512, 1.0), mi_(512, 1.0);
-    for (uint64_t i = 0; i < d; ++i) { const double v = settings->precond_mat[i * d + i]; ms[i] = __builtin_sqrt(v); mi_[i] = 1.0 / v; }
-    HIP_TRY(t.ms.alloc(512 * 8)); HIP_TRY(t.mi.alloc(512 * 8));
-    HIP_TRY(hipMemcpy(t.ms.p, ms.data(), 512 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t.mi.p, mi_.data(), 512 * 8, hipMemcpyHostToDevice));
-    return MI_OK;
-}
-// mala with a diagonal precond_mat on the LDS-streamed kernels: m, sqrt(m), INV(eps^2 M) (padded to 512) and LOG_DET(eps^2 M), all in the
-// oracle's operation order (literal_host.hpp: lit_prepare)
-struct MalaDiagMass { DevBuf m, ms, sinv; double log_det = 0.0; };
-int mala_diag_mass_upload(const mi_settings* settings, uint64_t d, MalaDiagMass& t, mi::LogitParams& q)
-{
-    mi::lit::LitPrep prep;
-    const int rcp = mi::lit::lit_prepare(1, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
-    if (rcp) return rcp;
-    std::vector<double> m(512, 1.0), ms(512, 1.0), si(512, 1.0);
-    for (uint64_t i = 0; i < d; ++i) { m[i] = prep.m[i]; ms[i] = prep.m_sqrt[i]; si[i] = prep.sinv_diag[i]; }
-    HIP_TRY(t.m.alloc(512 * 8)); HIP_TRY(t.ms.alloc(512 * 8)); HIP_TRY(t.sinv.alloc(512 * 8));
-    HIP_TRY(hipMemcpy(t.m.p, m.data(), 512 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t.ms.p, ms.data(), 512 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t.sinv.p, si.data(), 512 * 8, hipMemcpyHostToDevice));
+    std::vector<double> m(d), ms(d), mi_(d);
+    mi::settings::diag_mass(settings->precond_mat, d, m.data(), ms.data(), mi_.data());
+    mi::settings::MalaSigma sg;
+    int rc = mi::settings::mala_sigma(d, settings->step_size, 1, m.data(), sg);
+    if (rc) return rc;
+    if ((rc = upload_padded(t.m, m.data(), d, 512, 1.0)) || (rc = upload_padded(t.ms, ms.data(), d, 512, 1.0))
+        || (rc = upload_padded(t.sinv, sg.sinv_diag.data(), d, 512, 1.0))) return rc;
     q.m = t.m.as<double>(); q.m_sqrt = t.ms.as<double>(); q.s_inv = t.sinv.as<double>();
-    q.log_det = prep.log_det;
+    q.log_det = sg.log_det;
     return MI_OK;
 }
-bool precond_is_diagonal(const mi_settings* settings, uint64_t d)
-{
-    if (!settings->precond_mat) return false;
-    for (uint64_t i = 0; i < d; ++i)
-        for (uint64_t k = 0; k < d; ++k)
-            if (i != k && settings->precond_mat[i * d + k] != 0.0) return false;
-    return true;
-}
+bool precond_is_diagonal(const mi_settings* settings, uint64_t d) { return mi::settings::precond_kind(settings->precond_mat, d) == 1; }
 
 // settings.vals_bound and / or a DIAGONAL precond_mat for hmc / nuts on the LDS-streamed kernels (lds_box.hpp; logistic_lds.hpp DIAGM / BOUNDS):
 // determine_bounds_type (determine_bounds_type.hpp:27-57), the bounds, sqrt(m) and 1 / m -- on the device, padded to 512 entries with type 1 /
@@ -849,62 +816,41 @@ int lds_tables(const char* who, const mi_settings* settings, uint64_t d, LdsTabl
     t.bounds = settings->vals_bound != 0; t.mass = settings->precond_mat != nullptr;
     if (!t.bounds && !t.mass) return MI_OK;
     if (t.bounds && (!settings->lower_bounds || !settings->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
-    std::vector<double> m(512, 1.0), ms(512, 1.0), mi_(512, 1.0), lbv(512, 0.0), ubv(512, 0.0);
-    std::vector<int> bt(512, 1);
-    if (t.mass) for (uint64_t i = 0; i < d; ++i) { const double v = settings->precond_mat[i * d + i]; m[i] = v; ms[i] = __builtin_sqrt(v); mi_[i] = 1.0 / v; }
-    if (t.bounds)
-        for (uint64_t i = 0; i < d; ++i) {
-            lbv[i] = settings->lower_bounds[i]; ubv[i] = settings->upper_bounds[i];
-            const bool fl = std::isfinite(lbv[i]), fu = std::isfinite(ubv[i]);
-            bt[i] = (fl && fu) ? 4 : (fl && !fu) ? 2 : (!fl && fu) ? 3 : 1;
-        }
-    HIP_TRY(t.m.alloc(512 * 8)); HIP_TRY(t.ms.alloc(512 * 8)); HIP_TRY(t.mi.alloc(512 * 8));
-    HIP_TRY(hipMemcpy(t.m.p, m.data(), 512 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t.ms.p, ms.data(), 512 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t.mi.p, mi_.data(), 512 * 8, hipMemcpyHostToDevice));
+    std::vector<double> m(d, 1.0), ms(d, 1.0), mi_(d, 1.0);
+    if (t.mass) mi::settings::diag_mass(settings->precond_mat, d, m.data(), ms.data(), mi_.data());
+    int rc;
+    if ((rc = upload_padded(t.m, m.data(), d, 512, 1.0)) || (rc = upload_padded(t.ms, ms.data(), d, 512, 1.0)) || (rc = upload_padded(t.mi, mi_.data(), d, 512, 1.0))) return rc;
     q.m_sqrt = t.ms.as<double>(); q.m_inv = t.mi.as<double>();
     if (t.bounds) {
-        HIP_TRY(t.bt.alloc(512 * sizeof(int))); HIP_TRY(t.lb.alloc(512 * 8)); HIP_TRY(t.ub.alloc(512 * 8));
-        HIP_TRY(hipMemcpy(t.bt.p, bt.data(), 512 * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t.lb.p, lbv.data(), 512 * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(t.ub.p, ubv.data(), 512 * 8, hipMemcpyHostToDevice));
+        std::vector<int> bt(d);
+        std::vector<double> lbv(d), ubv(d);
+        mi::settings::bounds_tables(d, 1, settings->lower_bounds, settings->upper_bounds, bt.data(), lbv.data(), ubv.data());
+        if ((rc = upload_padded(t.bt, bt.data(), d, 512, 1)) || (rc = upload_padded(t.lb, lbv.data(), d, 512, 0.0)) || (rc = upload_padded(t.ub, ubv.data(), d, 512, 0.0))) return rc;
         q.btype = t.bt.as<int>(); q.lb = t.lb.as<double>(); q.ub = t.ub.as<double>();
     }
     return MI_OK;
 }
 // hmc with a DENSE precond_mat on the LDS-streamed kernel (logistic_lds.hpp: DENSEM): INV(M) and CHOL_LOWER(M) from the host (hmc.cpp:57-59
 // through the oracle's Gauss-Jordan / column Cholesky, as everywhere), row-major on the device
-// mala (mala.cpp:57-58; mala.ipp:58-64): M, CHOL_LOWER(M), and -- Sigma = eps^2 M is constant without bounds -- INV(Sigma) and LOG_DET(Sigma) =
-// sum_i 2 log CHOL_LOWER(Sigma)_ii, i ascending, as the d <= 128 kernel takes them (mala_gauss_dense_m_kernel)
+// mala (mala.cpp:57-58; mala.ipp:58-64): M, CHOL_LOWER(M), and -- Sigma = eps^2 M is constant without bounds -- INV(Sigma) and LOG_DET(Sigma)
+// (settings_host.hpp: mala_sigma), as the d <= 128 kernel takes them (mala_gauss_dense_m_kernel)
 struct LdsDenseM { DevBuf minv, l, m, sinv; };
 int lds_dense_m(const mi_settings* settings, uint64_t d, LdsDenseM& t, mi::LogitParams& q, int algo)
 {
-    auto up = [&](DevBuf& b, const double* src) -> int {
-        HIP_TRY(b.alloc(d * d * 8));
-        HIP_TRY(hipMemcpy(b.p, src, d * d * 8, hipMemcpyHostToDevice));
-        return MI_OK;
-    };
+    const size_t dd = (size_t)d * d;
     int rc;
-    std::vector<double> L;
-    if ((rc = host_cholesky_lower(settings->precond_mat, d, L))) return rc;
-    if ((rc = up(t.l, L.data()))) return rc;
+    const bool mala = algo == mi::LOGIT_MALA;
+    std::vector<double> Minv, L;
+    if ((rc = mi::settings::dense_mass(settings->precond_mat, d, mala ? nullptr : &Minv, L)) || (rc = upload_padded(t.l, L.data(), dd, dd, 0.0))) return rc;
     q.L_rm = t.l.as<double>();
-    if (algo == mi::LOGIT_MALA) {
-        const double s2 = settings->step_size * settings->step_size;
-        std::vector<double> Sigma(d * d), Sinv, Ls;
-        for (uint64_t i = 0; i < d * d; ++i) Sigma[i] = s2 * settings->precond_mat[i];
-        if ((rc = host_inverse(Sigma.data(), d, Sinv))) return rc;
-        if ((rc = host_cholesky_lower(Sigma.data(), d, Ls))) return rc;
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) ld = ld + 2.0 * mi::det_log(Ls[i * d + i]);
-        q.log_det = ld;
-        if ((rc = up(t.m, settings->precond_mat))) return rc;
-        if ((rc = up(t.sinv, Sinv.data()))) return rc;
+    if (mala) {
+        mi::settings::MalaSigma sg;
+        if ((rc = mi::settings::mala_sigma(d, settings->step_size, 2, settings->precond_mat, sg))) return rc;
+        q.log_det = sg.log_det;
+        if ((rc = upload_padded(t.m, settings->precond_mat, dd, dd, 0.0)) || (rc = upload_padded(t.sinv, sg.Sinv.data(), dd, dd, 0.0))) return rc;
         q.M_rm = t.m.as<double>(); q.Sinv_rm = t.sinv.as<double>();
     } else {
-        std::vector<double> Minv;
-        if ((rc = host_inverse(settings->precond_mat, d, Minv))) return rc;
-        if ((rc = up(t.minv, Minv.data()))) return rc;
+        if ((rc = upload_padded(t.minv, Minv.data(), dd, dd, 0.0))) return rc;
         q.Minv_rm = t.minv.as<double>();
     }
     return MI_OK;
@@ -998,19 +944,16 @@ int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_s
     q.eps = settings->step_size;
     q.draw0 = (uint32_t)chains->draw0;
     if (algo == mi::LOGIT_MALA) {                        // dmvnorm's constants for Sigma = eps^2 I, as the oracle states them
-        const double s2 = settings->step_size * settings->step_size;
-        double log_det = 0.0;
-        const double lii = __builtin_sqrt(s2);
-        for (uint64_t i = 0; i < d; ++i) log_det = log_det + 2.0 * mi::det_log(lii);
-        q.s2 = s2; q.rs = 1.0 / s2; q.log_det = log_det;
-        q.cons_term = -0.5 * (double)d * 1.83787706640934548356;
+        mi::settings::MalaSigma sg;
+        (void)mi::settings::mala_sigma(d, settings->step_size, 0, nullptr, sg);
+        q.s2 = settings->step_size * settings->step_size; q.rs = sg.rs; q.log_det = sg.log_det; q.cons_term = sg.cons_term;
     }
     LdsTables lt;
     LdsDenseM ldm;
     MalaDiagMass mdm;
     if ((algo == mi::LOGIT_HMC || algo == mi::LOGIT_MALA) && lds_dense_m_ok(target, settings)) { if ((rc = lds_dense_m(settings, d, ldm, q, algo))) return rc; }      // a dense precond_mat, unbounded
     else if (algo == mi::LOGIT_HMC) { if ((rc = lds_tables(who, settings, d, lt, q))) return rc; }      // (the caller routed bounds / a DIAGONAL matrix here)
-    else if (algo == mi::LOGIT_MALA && settings->precond_mat) { if ((rc = mala_diag_mass_upload(settings, d, mdm, q))) return rc; }
+    else if (algo == mi::LOGIT_MALA && settings->precond_mat) { if ((rc = mala_diag_tables(settings, d, mdm, q))) return rc; }
     rc = launch_logit(algo, q, P_dev, nullptr, st, settings, &sc.dev, mi::LOGIT_TARGET_DENSE, &lt);
     if (rc) return rc;
     rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains,
@@ -1066,6 +1009,16 @@ bool gemm_case(const mi_target* target, const mi_settings* settings, const mi_ch
     if (!algo_has_mass) return false;                    // rwmh with a cov_mat: the literal kernel
     return precond_is_diagonal(settings, target->d) || gemm_dense_mass_fits(target, chains, st);      // (hmc, mala) a DIAGONAL precond_mat, or a dense one that fits
 }
+// the mass tables of the matrix-product route: n_tables tables of dK entries in one buffer -- m | sqrt(m) | 1 / m of a diagonal precond_mat, padded with
+// ones; everything else (the identity, a dense matrix, a fourth table) ones
+void gemm_mass_tables(const mi::lit::LitPrep& prep, uint64_t d, uint32_t dK, int n_tables, std::vector<double>& tabs)
+{
+    tabs.assign((size_t)n_tables * dK, 1.0);
+    if (prep.precond != 1) return;
+    mi::settings::pad_table(prep.m.data(), d, dK, 1.0, &tabs[0]);
+    mi::settings::pad_table(prep.m_sqrt.data(), d, dK, 1.0, &tabs[dK]);
+    mi::settings::pad_table(prep.m_inv.data(), d, dK, 1.0, &tabs[2 * (size_t)dK]);
+}
 int run_gemm(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
 {
     int rc;
@@ -1113,28 +1066,25 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     if (bounded) {
         const size_t off_lb = (size_t)dK * sizeof(int), off_ub = off_lb + (size_t)dK * 8, off_blk = off_ub + (size_t)dK * 8, bytes = off_blk + (size_t)(dK / 16) * sizeof(uint32_t);
         std::vector<unsigned char> host(bytes, 0);
-        int* bt = reinterpret_cast<int*>(host.data());
-        double* lb = reinterpret_cast<double*>(host.data() + off_lb);
-        double* ub = reinterpret_cast<double*>(host.data() + off_ub);
+        mi::settings::pad_table(prep.bt.data(), d, dK, 1, reinterpret_cast<int*>(host.data()));
+        mi::settings::pad_table(prep.lb.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_lb));
+        mi::settings::pad_table(prep.ub.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_ub));
         uint32_t* blk = reinterpret_cast<uint32_t*>(host.data() + off_blk);
-        for (uint32_t i = 0; i < dK; ++i) bt[i] = 1;
-        for (uint64_t i = 0; i < d; ++i) { bt[i] = prep.bt[i]; lb[i] = prep.lb[i]; ub[i] = prep.ub[i]; if (bt[i] != 1) blk[i / 16] = 1u; }
-        HIP_TRY(box_dev.alloc(bytes));
-        HIP_TRY(hipMemcpy(box_dev.p, host.data(), bytes, hipMemcpyHostToDevice));
+        for (uint64_t i = 0; i < d; ++i) if (prep.bt[i] != 1) blk[i / 16] = 1u;
+        if ((rc = upload_padded(box_dev, host.data(), bytes, bytes, (unsigned char)0))) return rc;
         unsigned char* base = static_cast<unsigned char*>(box_dev.p);
         g.bounded = true; g.btype = reinterpret_cast<const int*>(base); g.lb = reinterpret_cast<const double*>(base + off_lb);
         g.ub = reinterpret_cast<const double*>(base + off_ub); g.box_blocks = reinterpret_cast<const uint32_t*>(base + off_blk);
     }
-    std::vector<double> tabs(4 * (size_t)dK, 1.0);
+    std::vector<double> tabs;
+    gemm_mass_tables(prep, d, dK, 4, tabs);
     if (algo == 1) {                                     // dmvnorm's constants for Sigma = eps^2 M, as the oracle states them
         g.s2 = settings->step_size * settings->step_size; g.rs = prep.rs; g.log_det = prep.log_det; g.cons_term = prep.cons_term;
-        for (uint64_t i = 0; i < d; ++i) tabs[3 * (size_t)dK + i] = prep.precond == 1 ? prep.sinv_diag[i] : prep.rs;
+        if (prep.precond == 1) mi::settings::pad_table(prep.sinv_diag.data(), d, dK, 1.0, &tabs[3 * (size_t)dK]);
+        else std::fill_n(&tabs[3 * (size_t)dK], d, prep.rs);
     }
-    if (prep.precond == 1)
-        for (uint64_t i = 0; i < d; ++i) { tabs[i] = prep.m[i]; tabs[dK + i] = prep.m_sqrt[i]; tabs[2 * (size_t)dK + i] = prep.m_inv[i]; }
     DevBuf tabs_dev;
-    HIP_TRY(tabs_dev.alloc(tabs.size() * 8));
-    HIP_TRY(hipMemcpy(tabs_dev.p, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice));
+    if ((rc = upload_padded(tabs_dev, tabs.data(), tabs.size(), tabs.size(), 1.0))) return rc;
     g.mass_tables = tabs_dev.as<double>(); g.diag_mass = prep.precond == 1;
     // a DENSE precond_mat: INV(M), CHOL_LOWER(M), M and (mala) INV(eps^2 M), transposed on the device -- the very matrices the literal kernel reads (lit_upload),
     // so the products of the route and of its replay take the oracle's matrices bit for bit
@@ -1214,19 +1164,13 @@ int run_small(const char* who, int algo, uint64_t d, const mi_settings* settings
     prm.draw0 = (uint32_t)chains->draw0;
     prm.eps = settings->step_size;
     prm.vals_bound = settings->vals_bound ? 1 : 0;
-    for (int i = 0; i < mi::SMALL_MAX_D; ++i) {
-        prm.btype[i] = 1; prm.lb[i] = 0.0; prm.ub[i] = 0.0;
+    for (int i = 0; i < mi::SMALL_MAX_D; ++i)
         for (int k = 0; k < mi::SMALL_MAX_D; ++k) prm.M[i][k] = (i == k) ? 1.0 : 0.0;
-    }
     if (settings->precond_mat && algo != 4)          // hmc.cpp:57, mala.cpp:57, rwmh.cpp:58 (rmhmc has none)
         for (uint64_t i = 0; i < d; ++i)
             for (uint64_t k = 0; k < d; ++k) prm.M[i][k] = settings->precond_mat[i * d + k];
-    if (settings->vals_bound)
-        for (uint64_t i = 0; i < d; ++i) {       // determine_bounds_type.hpp:27-57
-            prm.lb[i] = settings->lower_bounds[i]; prm.ub[i] = settings->upper_bounds[i];
-            const bool fl = std::isfinite(prm.lb[i]), fu = std::isfinite(prm.ub[i]);
-            prm.btype[i] = (fl && fu) ? 4 : (fl && !fu) ? 2 : (!fl && fu) ? 3 : 1;
-        }
+    mi::settings::bounds_tables(d, prm.vals_bound, settings->lower_bounds, settings->upper_bounds, prm.btype, prm.lb, prm.ub);
+    mi::settings::pad_table(prm.btype, d, mi::SMALL_MAX_D, 1, prm.btype);      // (prm{}: lb and ub are zeros beyond d already)
     if (algo == 2) {
         if ((rc = nuts_continuation(settings, chains, &prm.n_adapt))) return rc;
         prm.max_depth = (uint32_t)settings->max_tree_depth;
@@ -1817,25 +1761,15 @@ int mi_mcmc_run_tile_target(int algo, uint64_t d, int nt, int wpb, uint64_t lds_
     p.n_burnin = (uint32_t)settings->n_burnin_draws; p.n_keep = (uint32_t)settings->n_keep_draws;
     p.n_leap_steps = (uint32_t)settings->n_leap_steps; p.draw0 = (uint32_t)chains->draw0;
     p.eps = settings->step_size;
-    p.s2 = settings->step_size * settings->step_size; p.rs = 1.0 / p.s2;
-    p.cons_term = -0.5 * (double)d * 1.83787706640934548356;
-    {
-        const double lii = __builtin_sqrt(p.s2);
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) ld = ld + 2.0 * mi::det_log(lii);
-        p.log_det = ld;
-    }
+    // Sigma = eps^2 M is constant: INV(Sigma) = diag(1 / (eps^2 m_i)) and LOG_DET(Sigma) as the oracle's Gauss-Jordan / Cholesky give them for the identity
+    // or a diagonal matrix (settings_host.hpp: mala_sigma; the built-in general mala kernel, mala_dense.hpp, forms the same values)
+    mi::settings::MalaSigma sg;
+    (void)mi::settings::mala_sigma(d, settings->step_size, mala_diag ? 1 : 0, mala_diag ? gt.m.data() : nullptr, sg);
+    p.s2 = settings->step_size * settings->step_size; p.rs = sg.rs; p.cons_term = sg.cons_term; p.log_det = sg.log_det;
     p.lds_user_doubles = (uint32_t)(lds_user / sizeof(double));
     DevBuf sinv_dev;
     if (mala_diag) {
-        // Sigma = eps^2 M is constant: INV(Sigma) = diag(1 / (eps^2 m_i)) and LOG_DET(Sigma) = sum_i 2 log sqrt(eps^2 m_i), i ascending -- what the oracle's
-        // Gauss-Jordan / Cholesky give for a diagonal matrix (the built-in general mala kernel, mala_dense.hpp, forms the same values)
-        std::vector<double> sinv(d);
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) { const double sig = p.s2 * gt.m[i]; sinv[i] = 1.0 / sig; ld = ld + 2.0 * mi::det_log(__builtin_sqrt(sig)); }
-        p.log_det = ld;
-        HIP_TRY(sinv_dev.alloc(d * 8));
-        HIP_TRY(hipMemcpy(sinv_dev.p, sinv.data(), d * 8, hipMemcpyHostToDevice));
+        if ((rc = upload_padded(sinv_dev, sg.sinv_diag.data(), d, d, 1.0)) || (rc = gt.upload_m())) return rc;
         p.m = gt.m_dev.as<double>(); p.m_sqrt = gt.ms_dev.as<double>(); p.s_inv = sinv_dev.as<double>();
     }
     else if (gt.active) {
@@ -1944,22 +1878,18 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
     }
     if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
         return fail(MI_ERR_UNSUPPORTED, "hmc: target kind %d not implemented", target->kind);
-    // precond_mat (hmc.cpp:57-59): a DIAGONAL matrix is supported (INV and CHOL_LOWER of a diagonal matrix are the
-    // element-wise 1/m and sqrt(m), exactly what the oracle's Gauss-Jordan / Cholesky produce); dense is not yet
-    std::vector<double> m_sqrt, m_inv;
-    bool dense_m = false;
-    if (settings->precond_mat) {
-        m_sqrt.resize(d); m_inv.resize(d);
-        for (uint64_t i = 0; i < d; ++i)
-            for (uint64_t k = 0; k < d; ++k) {
-                const double v = settings->precond_mat[i * d + k];
-                if (i != k && v != 0.0) dense_m = true;
-                if (i == k) { m_sqrt[i] = __builtin_sqrt(v); m_inv[i] = 1.0 / v; }
-            }
-        // a dense matrix: INV / CHOL_LOWER on the host; three fragment sets in LDS (d <= 64), or the two extra ones read from L2
-        // in fragment order (64 < d <= 128); target must be an MFMA one
-        if (dense_m && target->kind == MI_TARGET_LOGISTIC) return fail(MI_ERR_UNSUPPORTED, "hmc: precond_mat with the logistic target is not implemented");
-    }
+    // precond_mat (hmc.cpp:57-59): INV and CHOL_LOWER of a DIAGONAL matrix are the element-wise 1/m and sqrt(m), exactly what the oracle's
+    // Gauss-Jordan / Cholesky produce; a dense matrix: three fragment sets in LDS (d <= 64), or the two extra ones read from L2 in fragment
+    // order (64 < d <= 128) -- the tables come from settings_host.hpp where a route below needs them
+    const bool dense_m = mi::settings::precond_kind(settings->precond_mat, d) == 2;
+    // sqrt(m) and 1 / m of a diagonal precond_mat alone (no bounds) on the device
+    DevBuf ms_dev, mi_dev;
+    auto upload_diag_mass = [&]() -> int {
+        std::vector<double> m(d), m_sqrt(d), m_inv(d);
+        mi::settings::diag_mass(settings->precond_mat, d, m.data(), m_sqrt.data(), m_inv.data());
+        if (int rcu = upload_padded(ms_dev, m_sqrt.data(), d, d, 1.0)) return rcu;
+        return upload_padded(mi_dev, m_inv.data(), d, d, 1.0);
+    };
     // beyond d = 128 the tiled kernels serve separable targets without bounds (identity or diagonal precond_mat: hmc_diag.hpp);
     // everything else there -- dense gradients, bounds, a dense precond_mat -- runs on the literal kernel (literal.hpp)
     if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !(dense_m && settings->vals_bound) && target->kernel_hint != MI_KERNEL_LITERAL)
@@ -2016,27 +1946,18 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
         int diag_lanes = mi::hmc_diag_pick_lanes(q.C);          // lanes per chain (hmc_diag.hpp)
         if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_1LANE) diag_lanes = 1;
         if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_4LANE) diag_lanes = 4;
-        DevBuf ms_d, mi_d;
         ChainMass cm;
         if (sc.dev.mass_diag) {                          // per-chain tables [d][C]
             if ((rc = chain_mass_tables(sc.dev.mass_diag, d, q.C, cm, st))) return rc;
             q.m_sqrt = cm.ms.as<double>(); q.m_inv = cm.mi.as<double>(); q.m_per_chain = 1;
-            mi::note_kernel("hmc_diag%d_kernel<true>", diag_lanes == 4 ? 4 : 1);
-            if (diag_lanes == 4) hipLaunchKernelGGL(mi::hmc_diag4_kernel<true>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
-            else hipLaunchKernelGGL(mi::hmc_diag1_kernel<true>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
         } else if (diag_precond_elementwise) {
-            HIP_TRY(ms_d.alloc(d * 8)); HIP_TRY(mi_d.alloc(d * 8));
-            HIP_TRY(hipMemcpy(ms_d.p, m_sqrt.data(), d * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(mi_d.p, m_inv.data(), d * 8, hipMemcpyHostToDevice));
-            q.m_sqrt = ms_d.as<double>(); q.m_inv = mi_d.as<double>();
-            mi::note_kernel("hmc_diag%d_kernel<true>", diag_lanes == 4 ? 4 : 1);
-            if (diag_lanes == 4) hipLaunchKernelGGL(mi::hmc_diag4_kernel<true>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
-            else hipLaunchKernelGGL(mi::hmc_diag1_kernel<true>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
-        } else {
-        mi::note_kernel("hmc_diag%d_kernel<false>", diag_lanes == 4 ? 4 : 1);
-        if (diag_lanes == 4) hipLaunchKernelGGL(mi::hmc_diag4_kernel<false>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(mi::hmc_diag1_kernel<false>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
+            if ((rc = upload_diag_mass())) return rc;
+            q.m_sqrt = ms_dev.as<double>(); q.m_inv = mi_dev.as<double>();
         }
+        const bool precond = q.m_sqrt != nullptr;        // the PRECOND instantiation: mass tables, per chain or shared
+        mi::note_kernel("hmc_diag%d_kernel<%s>", diag_lanes == 4 ? 4 : 1, precond ? "true" : "false");
+        if (diag_lanes == 4) hipLaunchKernelGGL(precond ? mi::hmc_diag4_kernel<true> : mi::hmc_diag4_kernel<false>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
+        else hipLaunchKernelGGL(precond ? mi::hmc_diag1_kernel<true> : mi::hmc_diag1_kernel<false>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
         HIP_TRY(hipGetLastError());
         {   // chains that reached the non-finite regime: replayed literally (literal.hpp)
             mi::lit::LitParams lp{};
@@ -2044,7 +1965,7 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
             if (rc) return rc;
             lit_common(lp, settings, &sc.dev, rp, false);
             if (sc.dev.mass_diag) lit_set_chain_mass(lp, sc.dev.mass_diag, cm, q.C);
-            else if (diag_precond_elementwise) { lp.precond = 1; lp.m_sqrt = ms_d.as<double>(); lp.m_inv = mi_d.as<double>(); }
+            else if (diag_precond_elementwise) { lp.precond = 1; lp.m_sqrt = ms_dev.as<double>(); lp.m_inv = mi_dev.as<double>(); }
             rc = launched("hmc (literal replay)", mi::launch_literal(0, lp, rp.n_wg, st));
             if (rc) return rc;
         }
@@ -2103,40 +2024,16 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
 #endif
 
     const int nt = (int)((d + 15) / 16);
-    DevBuf bt_dev, lb_dev, ub_dev;
-    if (general) {
-        // determine_bounds_type (determine_bounds_type.hpp:27-57): 1 none, 2 lower, 3 upper, 4 both
-        std::vector<int> bt(d, 1);
-        std::vector<double> lbv(d, 0.0), ubv(d, 0.0);
-        if (settings->vals_bound)
-            for (uint64_t i = 0; i < d; ++i) {
-                lbv[i] = settings->lower_bounds[i]; ubv[i] = settings->upper_bounds[i];
-                const bool fl = std::isfinite(lbv[i]), fu = std::isfinite(ubv[i]);
-                bt[i] = (fl && fu) ? 4 : (fl && !fu) ? 2 : (!fl && fu) ? 3 : 1;
-            }
-        if (m_sqrt.empty()) { m_sqrt.assign(d, 1.0); m_inv.assign(d, 1.0); }
-        DevBuf ms_dev, mi_dev;
-        HIP_TRY(bt_dev.alloc(d * sizeof(int))); HIP_TRY(lb_dev.alloc(d * 8)); HIP_TRY(ub_dev.alloc(d * 8));
-        HIP_TRY(ms_dev.alloc(d * 8)); HIP_TRY(mi_dev.alloc(d * 8));
-        HIP_TRY(hipMemcpy(bt_dev.p, bt.data(), d * sizeof(int), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(lb_dev.p, lbv.data(), d * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ub_dev.p, ubv.data(), d * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ms_dev.p, m_sqrt.data(), d * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(mi_dev.p, m_inv.data(), d * 8, hipMemcpyHostToDevice));
-        prm.btype = bt_dev.as<int>(); prm.lb = lb_dev.as<double>(); prm.ub = ub_dev.as<double>();
-        prm.m_sqrt = ms_dev.as<double>(); prm.m_inv = mi_dev.as<double>();
+    if (general) {                                      // bounds and / or a dense precond_mat: the tables of the other samplers' general variants
+        GeneralTables gt;
+        rc = general_tables("hmc", settings, d, gt, true, true);
+        if (rc) return rc;
+        prm.btype = gt.bt.as<int>(); prm.lb = gt.lb.as<double>(); prm.ub = gt.ub.as<double>();
+        prm.m_sqrt = gt.ms_dev.as<double>(); prm.m_inv = gt.mi_dev.as<double>();
         prm.vals_bound = settings->vals_bound ? 1 : 0;
-        DevBuf minv_dev, l_dev;
-        if (dense_m) {
-            std::vector<double> Minv, L;
-            rc = host_inverse(settings->precond_mat, d, Minv); if (rc) return rc;
-            rc = host_cholesky_lower(settings->precond_mat, d, L); if (rc) return rc;
-            rc = upload_matrix(Minv, d, minv_dev); if (rc) return rc;
-            rc = upload_matrix(L, d, l_dev); if (rc) return rc;
-            prm.Minv = minv_dev.as<double>(); prm.Lchol = l_dev.as<double>();
-        }
+        if (dense_m) { prm.Minv = gt.minv_full.as<double>(); prm.Lchol = gt.l_full.as<double>(); }
         rc = launched("hmc", mi::launch_hmc_gauss(prm, nt, true, dense_m, st));
-        if (!rc) HIP_TRY(hipStreamSynchronize(st));     // bounds buffers are ours
+        if (!rc) HIP_TRY(hipStreamSynchronize(st));     // the tables are ours
     }
     else {
         // launch shape of the plain kernel (64 < d <= 128): with fewer 16-chain tiles than the chip has wave slots, give a tile
@@ -2162,16 +2059,13 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
             default: break;
             }
         }
-        DevBuf ms_dev, mi_dev;
         ChainMass cm;
         if (chain_mass) {
             if ((rc = chain_mass_tables(sc.dev.mass_diag, d, chains->n_chains, cm, st))) return rc;
             prm.m_sqrt = cm.ms.as<double>(); prm.m_inv = cm.mi.as<double>(); prm.m_per_chain = 1;
             rc = launched("hmc", mi::launch_hmc_gauss_diagm(prm, nt, st));
         } else if (diag_only) {
-            HIP_TRY(ms_dev.alloc(d * 8)); HIP_TRY(mi_dev.alloc(d * 8));
-            HIP_TRY(hipMemcpy(ms_dev.p, m_sqrt.data(), d * 8, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(mi_dev.p, m_inv.data(), d * 8, hipMemcpyHostToDevice));
+            if ((rc = upload_diag_mass())) return rc;
             prm.m_sqrt = ms_dev.as<double>(); prm.m_inv = mi_dev.as<double>();
             rc = launched("hmc", mi::launch_hmc_gauss_diagm(prm, nt, st));
         } else
@@ -2608,13 +2502,10 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
         return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("mala", 1, target, settings, chains, st) : run_literal("mala", 1, target, settings, chains, st);
     if (target->kind == MI_TARGET_LOGISTIC && d > 512) return run_literal("mala", 1, target, settings, chains, st);
     // Sigma = eps^2 * I (mala.ipp:41,63): INV by Gauss-Jordan gives diag(1/s2); CHOL gives diag(sqrt(s2));
-    // LOG_DET = sum_i 2 log L_ii accumulated sequentially, exactly as the oracle states it.
+    // LOG_DET = sum_i 2 log L_ii accumulated sequentially, exactly as the oracle states it (settings_host.hpp: mala_sigma).
     const double s2_ = settings->step_size * settings->step_size;
-    double log_det_ = 0.0;
-    {
-        const double lii = __builtin_sqrt(s2_);
-        for (uint64_t i = 0; i < d; ++i) log_det_ = log_det_ + 2.0 * mi::det_log(lii);
-    }
+    mi::settings::MalaSigma sg;
+    (void)mi::settings::mala_sigma(d, settings->step_size, 0, nullptr, sg);
     if (target->kind == MI_TARGET_LOGISTIC) {
         if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
         if (d > 512) return fail(MI_ERR_UNSUPPORTED, "mala: logistic target with d = %llu > 512 not implemented", (unsigned long long)d);
@@ -2636,14 +2527,12 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
         q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept;
         q.seed = settings->rng_seed_value;
         q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
-        q.eps = settings->step_size; q.s2 = s2_; q.rs = 1.0 / s2_;
-        q.cons_term = -0.5 * (double)d * 1.83787706640934548356;
-        q.log_det = log_det_;
+        q.eps = settings->step_size; q.s2 = s2_; q.rs = sg.rs; q.cons_term = sg.cons_term; q.log_det = sg.log_det;
         q.draw0 = (uint32_t)chains->draw0;
         MalaDiagMass mdm;
         LdsDenseM ldm;
         if (lds_dense_m_ok(target, settings)) { if ((rc = lds_dense_m(settings, d, ldm, q, mi::LOGIT_MALA))) return rc; }     // dense, no bounds
-        else if (settings->precond_mat) { if ((rc = mala_diag_mass_upload(settings, d, mdm, q))) return rc; }     // (diagonal, no bounds: routed above)
+        else if (settings->precond_mat) { if ((rc = mala_diag_tables(settings, d, mdm, q))) return rc; }     // (diagonal, no bounds: routed above)
         rc = launch_logit(mi::LOGIT_MALA, q, X_dev, y_dev, st, settings, &sc.dev);
         if (rc) return rc;
         rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, 0, st);
@@ -2682,17 +2571,7 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
     prm.n_keep = (uint32_t)settings->n_keep_draws;
     prm.eps = settings->step_size;
     prm.draw0 = (uint32_t)chains->draw0;
-    // Sigma = eps^2 * I (mala.ipp:41,63): INV by Gauss-Jordan gives diag(1/s2); CHOL gives diag(sqrt(s2));
-    // LOG_DET = sum_i 2 log L_ii accumulated sequentially, exactly as the oracle states it.
-    prm.s2 = settings->step_size * settings->step_size;
-    prm.rs = 1.0 / prm.s2;
-    prm.cons_term = -0.5 * (double)d * 1.83787706640934548356;   // MCMC_LOG_2PI, stats/mcmc_stats.hpp:28-30
-    {
-        const double lii = __builtin_sqrt(prm.s2);
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) ld = ld + 2.0 * mi::det_log(lii);
-        prm.log_det = ld;
-    }
+    prm.s2 = s2_; prm.rs = sg.rs; prm.cons_term = sg.cons_term; prm.log_det = sg.log_det;      // Sigma = eps^2 I, from above
 
     const int nt = (int)((d + 15) / 16);
     GeneralTables gt;
@@ -2728,16 +2607,11 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
     }
     else if (dense_unbounded) {
         // dense precond_mat, unbounded: Sigma = eps^2 M is constant, so INV / CHOL_LOWER / LOG_DET come from the host once
-        std::vector<double> Sigma(d * d), Sinv, Ls;
-        for (uint64_t i = 0; i < d * d; ++i) Sigma[i] = prm.s2 * settings->precond_mat[i];
-        rc = host_inverse(Sigma.data(), d, Sinv); if (rc) return rc;
-        rc = host_cholesky_lower(Sigma.data(), d, Ls); if (rc) return rc;
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) ld = ld + 2.0 * mi::det_log(Ls[i * d + i]);
-        prm.log_det = ld;
+        rc = mi::settings::mala_sigma(d, settings->step_size, 2, settings->precond_mat, sg); if (rc) return rc;
+        prm.log_det = sg.log_det;
         DevBuf m_full, sinv_full;
         rc = upload_matrix(std::vector<double>(settings->precond_mat, settings->precond_mat + d * d), d, m_full); if (rc) return rc;
-        rc = upload_matrix(Sinv, d, sinv_full); if (rc) return rc;
+        rc = upload_matrix(sg.Sinv, d, sinv_full); if (rc) return rc;
         prm.Mfull = m_full.as<double>(); prm.Lchol = gt.l_full.as<double>(); prm.Sinv = sinv_full.as<double>();
         prm.sep_target = target->kind != MI_TARGET_GAUSS_DENSE;     // ISO / DIAG: the gradient is element-wise in the reference's target function
         rc = launched("mala", mi::launch_mala_gauss(prm, nt, 2, st));
@@ -2745,9 +2619,9 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
     }
     else if (gt.active) {
         // unbounded runs hoist LOG_DET(eps^2 M) = sum_i 2 log sqrt(eps^2 M_ii), i ascending (bounded runs sum it per draw)
-        double ld = 0.0;
-        for (uint64_t i = 0; i < d; ++i) ld = ld + 2.0 * mi::det_log(__builtin_sqrt(prm.s2 * gt.m[i]));
-        prm.log_det = ld;
+        (void)mi::settings::mala_sigma(d, settings->step_size, 1, gt.m.data(), sg);
+        prm.log_det = sg.log_det;
+        if ((rc = gt.upload_m())) return rc;
         prm.vals_bound = settings->vals_bound ? 1 : 0;
         prm.btype = gt.bt.as<int>(); prm.lb = gt.lb.as<double>(); prm.ub = gt.ub.as<double>();
         prm.m = gt.m_dev.as<double>(); prm.m_sqrt = gt.ms_dev.as<double>();
@@ -2822,8 +2696,7 @@ int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_ch
         prm.btype = gt.bt.as<int>(); prm.lb = gt.lb.as<double>(); prm.ub = gt.ub.as<double>();
         prm.c_diag = c_dev.as<double>();
         if (gt.dense) {
-            std::vector<double> L;
-            rc = host_cholesky_lower(settings->precond_mat, d, L); if (rc) return rc;
+            std::vector<double> L = gt.L;
             for (auto& v : L) v = prm.par_scale * v;
             rc = upload_matrix(L, d, lc_dev); if (rc) return rc;
             prm.Lc = lc_dev.as<double>();
@@ -3052,12 +2925,10 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     rc = mi::lit::lit_prepare(0, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
     if (rc) return rc;
     const uint32_t dK = mi::gemm::gemm_padded_d((uint32_t)d);
-    std::vector<double> tabs(3 * (size_t)dK, 1.0);
-    if (prep.precond == 1)
-        for (uint64_t i = 0; i < d; ++i) { tabs[i] = prep.m[i]; tabs[dK + i] = prep.m_sqrt[i]; tabs[2 * (size_t)dK + i] = prep.m_inv[i]; }
+    std::vector<double> tabs;
+    gemm_mass_tables(prep, d, dK, 3, tabs);
     DevBuf tabs_dev;
-    HIP_TRY(tabs_dev.alloc(tabs.size() * 8));
-    HIP_TRY(hipMemcpy(tabs_dev.p, tabs.data(), tabs.size() * 8, hipMemcpyHostToDevice));
+    if ((rc = upload_padded(tabs_dev, tabs.data(), tabs.size(), tabs.size(), 1.0))) return rc;
     g.mass_tables = tabs_dev.as<double>(); g.diag_mass = prep.precond == 1;
     // workspace: the route's own (the packed matrices, one range of chains) | non-finite flags | the matrix transposed and the work areas of the literal replay
     ReplayWs rp;

@@ -2,6 +2,8 @@
 // __host__ __device__ functions the GPU runs, one "thread" per chain here) behind a C entry point, so that the CPU test suite can
 // hold the product's replay logic against the oracle on non-finite cases without a GPU.  Built by tests/lit_host.py with
 //   hipcc -O2 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -shared
+#include <algorithm>
+
 #include "../mcmc_amd/csrc/literal_host.hpp"
 
 // what the extended entry point adds: per-chain diagonal masses (hmc), host callbacks as the target (kind = LIT_CALLBACK: the host
@@ -93,4 +95,29 @@ extern "C" int lit_host_run_ext(int algo, int kind, uint32_t d, uint32_t n_rows,
     return lit_host_run_impl(algo, kind, d, n_rows, prec, X, y, C, chain0, theta, draws, n_accept, n_leap, seed, n_burnin, n_keep, n_leap_steps,
                              draw0, eps, vals_bound, lower, upper, precond_mat, n_adapt, max_depth, delta, gamma, t0, kappa, step_out,
                              depth_trace, n_fp_steps, ex);
+}
+
+// the pieces of mcmc_amd/csrc/settings_host.hpp on their own (tests/test_settings_host_cpu.py): bounds types, the kind of precond_mat, its diagonal's mass
+// tables (of a dense matrix too, as the general kernel variants read them), INV / CHOL_LOWER and INV(eps^2 M) row-major when it is dense, mala's constants
+// sigma = {rs, cons_term, log_det}, and bt / m_sqrt padded to n_padded entries with type 1 / `fill`.  Returns the kind, or -1 when a factorisation failed.
+extern "C" int lit_host_settings(uint32_t d, int vals_bound, const double* lower, const double* upper, const double* precond_mat, double eps,
+                                 int* bt, double* lb, double* ub, double* m, double* m_sqrt, double* m_inv, double* Minv, double* L,
+                                 double* sigma, double* sinv_diag, double* Sinv, uint32_t n_padded, double fill, int* bt_padded, double* m_sqrt_padded)
+{
+    namespace S = mi::settings;
+    S::bounds_tables(d, vals_bound, lower, upper, bt, lb, ub);
+    const int kind = S::precond_kind(precond_mat, d);
+    if (kind != 0) S::diag_mass(precond_mat, d, m, m_sqrt, m_inv);
+    std::vector<double> inv, chol;
+    if (kind == 2) {
+        if (S::dense_mass(precond_mat, d, &inv, chol)) return -1;
+        std::copy(inv.begin(), inv.end(), Minv); std::copy(chol.begin(), chol.end(), L);
+    }
+    S::MalaSigma sg;
+    if (S::mala_sigma(d, eps, kind, kind == 1 ? m : precond_mat, sg)) return -1;
+    sigma[0] = sg.rs; sigma[1] = sg.cons_term; sigma[2] = sg.log_det;
+    std::copy(sg.sinv_diag.begin(), sg.sinv_diag.end(), sinv_diag); std::copy(sg.Sinv.begin(), sg.Sinv.end(), Sinv);
+    S::pad_table(bt, d, n_padded, 1, bt_padded);
+    if (kind != 0) S::pad_table(m_sqrt, d, n_padded, fill, m_sqrt_padded);
+    return kind;
 }

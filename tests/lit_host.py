@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 _SO = os.path.join(HERE, "_lit_host.so")
 _ENGINE_INC = os.path.join(ROOT, "include", "mi_mcmc_engine")      # the engine headers that ship with the public ones
-_SRC = ([os.path.join(HERE, "lit_host.hip")] + [os.path.join(ROOT, "mcmc_amd", "csrc", f) for f in ("literal.hpp", "literal_host.hpp", "host_linalg.hpp")]
+_SRC = ([os.path.join(HERE, "lit_host.hip")] + [os.path.join(ROOT, "mcmc_amd", "csrc", f) for f in ("literal.hpp", "literal_host.hpp", "settings_host.hpp", "host_linalg.hpp")]
         + [os.path.join(_ENGINE_INC, "det_math.hpp")])
 _dp = C.POINTER(C.c_double)
 _lib = None
@@ -68,3 +68,22 @@ def run(algo, kind, init, seed, n_burnin, n_keep, n_leap, eps, prec=None, X=None
                             C.c_void_p(tensor_data or 0), _p(adapt))
     assert rc == 0
     return draws, dict(n_accept=nacc, n_leap=nleap, theta=theta.T.copy(), eps=step, depth=depth, adapt_state=adapt)
+
+
+def settings(d, eps=1.0, lower=None, upper=None, precond=None, n_padded=None, fill=1.0):
+    """The pieces of mcmc_amd/csrc/settings_host.hpp for one set of settings.  Returns a dict: kind, bt, lb, ub, m, m_sqrt, m_inv (diagonal of any
+    precond), Minv, L, Sinv (row-major, dense), rs, cons_term, log_det, sinv_diag, bt_padded, m_sqrt_padded."""
+    lower, upper, precond = _f(lower), _f(upper), _f(precond)
+    n_padded = d if n_padded is None else n_padded
+    o = dict(bt=np.zeros(d, dtype=np.int32), bt_padded=np.zeros(n_padded, dtype=np.int32), sigma=np.zeros(3), m_sqrt_padded=np.zeros(n_padded))
+    for k in ("lb", "ub", "m", "m_sqrt", "m_inv", "sinv_diag"):
+        o[k] = np.full(d, np.nan)
+    for k in ("Minv", "L", "Sinv"):
+        o[k] = np.full((d, d), np.nan)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    o["kind"] = lib().lit_host_settings(C.c_uint32(d), C.c_int(0 if lower is None else 1), _p(lower), _p(upper), _p(precond), C.c_double(eps),
+                                        ip(o["bt"]), _p(o["lb"]), _p(o["ub"]), _p(o["m"]), _p(o["m_sqrt"]), _p(o["m_inv"]), _p(o["Minv"]), _p(o["L"]),
+                                        _p(o["sigma"]), _p(o["sinv_diag"]), _p(o["Sinv"]), C.c_uint32(n_padded), C.c_double(fill),
+                                        ip(o["bt_padded"]), _p(o["m_sqrt_padded"]))
+    o["rs"], o["cons_term"], o["log_det"] = o.pop("sigma")
+    return o
