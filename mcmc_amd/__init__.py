@@ -271,7 +271,8 @@ def rmhmc_callback(initial_vals, kernel_fn, kernel_data, tensor_fn, tensor_data,
 
 
 def test_set_grid_cap(max_workgroups):
-    """mi_mcmc_test_set_grid_cap (TEST HOOK, mi_mcmc_probes.h): cap the persistent grids of the dynamic-hand-out NUTS kernels; 0 = none."""
+    """mi_mcmc_test_set_grid_cap (TEST HOOK, mi_mcmc_probes.h): cap the persistent grids of the dynamic-hand-out NUTS kernels and the grid-stride grids of the
+    matrix-product route; 0 = none."""
     lib().mi_mcmc_test_set_grid_cap(C.c_uint32(int(max_workgroups)))
 
 
@@ -339,6 +340,27 @@ def test_gemm_nuts_fixed_bytes(d, n_rows):
 def test_gemm_nuts_range_chains(n_chains, chain_bytes, fixed_bytes, budget):
     """mi_mcmc_test_gemm_nuts_range_chains (TEST HOOK; host arithmetic): chains per range under `budget` bytes -- all of them (padded to 128) or a multiple of 128; 0: none."""
     return _u64_hook("mi_mcmc_test_gemm_nuts_range_chains", C.c_uint64(int(n_chains)), C.c_uint64(int(chain_bytes)), C.c_uint64(int(fixed_bytes)), C.c_uint64(int(budget)))
+
+
+GEMM_PLAIN, GEMM_DENSE_M, GEMM_BOUNDED = 0, 1, 2       # the variants of hmc / mala / rwmh on the matrix-product route (test_gemm_need_bytes)
+
+
+def test_set_gemm_graph(mode):
+    """mi_mcmc_test_set_gemm_graph (TEST HOOK, mi_mcmc_probes.h): 1 = the samplers of the matrix-product route never capture the launches of a draw / a tick into a
+    graph (what a call of 65 536 chains does); 0 = the rule as it is.  Results do not depend on it."""
+    lib().mi_mcmc_test_set_gemm_graph(C.c_int(int(mode)))
+
+
+def test_set_gemm_ws_bytes(n_bytes):
+    """mi_mcmc_test_set_gemm_ws_bytes (TEST HOOK, mi_mcmc_probes.h): the device memory the capacity condition of hmc / mala / rwmh on the matrix-product route sees
+    (0 = the real figure); a call that needs more stays on the literal kernel.  Results do not depend on it."""
+    lib().mi_mcmc_test_set_gemm_ws_bytes(C.c_uint64(int(n_bytes)))
+
+
+def test_gemm_need_bytes(d, n_rows, n_chains, variant=GEMM_PLAIN, replay=True):
+    """mi_mcmc_test_gemm_need_bytes (TEST HOOK; host arithmetic, no device): what that condition compares with the memory -- the workspace, with `replay` (hmc, mala)
+    the literal replay's part behind it, and the uploads.  n_rows = 0: the dense Gaussian."""
+    return _u64_hook("mi_mcmc_test_gemm_need_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint64(int(n_chains)), C.c_int(int(variant)), C.c_int(1 if replay else 0))
 
 
 def last_kernel():

@@ -543,7 +543,7 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
 
     if (int e = step_attrs<TGT>()) return e;
     if (r.pack) pack_target<TGT>(w, r.P, r.X, r.n_rows, r.d, st);      // (the matrices are the same for every range of a call)
-    hipLaunchKernelGGL(nuts_init_kernel, dim3((unsigned)std::min<size_t>((4 * l.Cp + 255) / 256, 65535)), dim3(256), 0, st, tp);
+    hipLaunchKernelGGL(nuts_init_kernel, dim3(stride_grid(4 * l.Cp)), dim3(256), 0, st, tp);
     GEMM_TRY(hipGetLastError());
 
     const uint32_t n_ntiles = (uint32_t)(l.Cp / TN);

@@ -53,6 +53,7 @@
 // only while everything is finite; a chain whose energies (hmc) / proposal densities (mala) go non-finite is flagged and replayed by literal.hpp.
 
 #include "gemm_samplers.hpp"
+#include "launch_common.hpp"      // cap_grid: the test hook's limit on the grid-stride grids
 #include "det_math.hpp"
 #include "nuts_points.hpp"        // the memoised NUTS trajectory: which points a doubling visits, which tests a point closes (gemm_nuts.hpp)
 #include "hmc_dense.hpp"          // box_transform, box_inv_transform, box_inv_jacobian, box_log_jacobian_term: the reference's element-wise maps, out of line
@@ -853,7 +854,10 @@ static int launch_step_mode(int mode, const StepParams& sp, hipStream_t st)
     return (int)hipErrorInvalidValue;
 }
 
-static dim3 pack_grid(size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)); }
+// the grid of a GRID-STRIDE kernel over n elements, 256 per workgroup: at most max_wg workgroups, and at most the test hook's cap (launch_common.hpp) -- the kernel
+// loops, so the bits do not depend on it.  Only such kernels take it: the step kernel, the class-wise, normals and prepare kernels index by workgroup id
+static unsigned stride_grid(size_t n, size_t max_wg = 65535) { return (unsigned)cap_grid(std::min<size_t>((n + 255) / 256, max_wg)); }
+static dim3 pack_grid(size_t n) { return dim3(stride_grid(n)); }
 // the target's matrices into the workspace, zero-padded: P^T, or X^T and X
 template <int TGT>
 static void pack_target(const TargetWs& w, const double* P, const double* X, uint32_t n_rows, uint32_t d, hipStream_t st)
@@ -876,7 +880,7 @@ static int gradient_product(const TargetWs& w, const double* y, uint32_t n_rows,
         StepParams se = sp;
         se.At = w.A1; se.Bm = B; se.Kp = l.dK; se.ldA = l.nM; se.M_store = l.nK; se.term_out = w.term;
         if (int e = launch_step<EP_ETA, TGT>(se, s)) return e;
-        hipLaunchKernelGGL(gemm_rowterm_kernel, dim3((unsigned)std::min<size_t>((l.rvec + 255) / 256, 1u << 20)), dim3(256), 0, s, y, n_rows, l.nK, l.Cp, w.res, w.term);
+        hipLaunchKernelGGL(gemm_rowterm_kernel, dim3(stride_grid(l.rvec, (size_t)1 << 20)), dim3(256), 0, s, y, n_rows, l.nK, l.Cp, w.res, w.term);
         sp.At = w.A2; sp.Bm = w.res; sp.Kp = l.nK; sp.ldA = l.dM; sp.M_store = l.dK;
     } else {
         sp.At = w.A1; sp.Bm = B; sp.Kp = l.dK; sp.ldA = l.dM; sp.M_store = l.dK;
@@ -954,7 +958,7 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
         return launch_step_mode<TGT>(mode, sp, s);
     };
 
-    const unsigned ew_grid = (unsigned)std::min<size_t>((l.vec + 255) / 256, 65535);
+    const unsigned ew_grid = stride_grid(l.vec);
     const unsigned cls_grid = (unsigned)(l.Cp / 64);                 // 4 waves x 16 chains per workgroup
     auto per_chain = [&](void (*kernel)(DrawParams), const DrawParams& p, hipStream_t s) { hipLaunchKernelGGL(kernel, dim3(cls_grid), dim3(256), 0, s, p); };
     pack_target<TGT>(w, r.P, r.X, r.n_rows, r.d, st);
@@ -1023,7 +1027,7 @@ static int gemm_run_t(const GemmRun& r, hipStream_t st, const char** kernel_name
 
     DrawParams sp_out = dp;
     if (box) sp_out.th = w.xacc;                                       // the final state leaves through inv_transform too: a continued call transforms it again, as the literal kernel does
-    hipLaunchKernelGGL(gemm_store_kernel, dim3((unsigned)std::min<size_t>(((size_t)r.d * r.C + 255) / 256, 65535)), dim3(256), 0, st, sp_out);
+    hipLaunchKernelGGL(gemm_store_kernel, dim3(stride_grid((size_t)r.d * r.C)), dim3(256), 0, st, sp_out);
     GEMM_TRY(hipGetLastError());
     if (kernel_name) {
         static thread_local char name[112];

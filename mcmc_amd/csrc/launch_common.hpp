@@ -8,7 +8,10 @@ namespace mi {
 void note_kernel(const char* fmt, ...);
 // TEST HOOK (mi_mcmc_test_set_grid_cap, mi_mcmc_probes.h): an upper limit on the workgroups of the PERSISTENT grids (nuts_memo.hpp,
 // nuts_lds.hpp), 0 = none.  With a small cap a handful of chains exercises what only > 16 384 chains reach otherwise: the
-// global counter, a slot taking its second and third chain, retire-on-leave.  Process-wide; results never depend on it.
+// global counter, a slot taking its second and third chain, retire-on-leave.  The GRID-STRIDE grids of the matrix-product route
+// (gemm_samplers.hip, gemm_nuts.hpp: pack, load, store, row terms, nuts init -- stride_grid) take it too: under a cap every lane makes
+// the second and later passes of its loop, which otherwise only d K x chains > 16.7 M elements reach.  Kernels that index by workgroup
+// id (the step kernel, the class-wise, normals and prepare kernels) are never capped.  Process-wide; results never depend on it.
 uint64_t test_grid_cap();
 inline uint64_t cap_grid(uint64_t n_wg) { const uint64_t c = test_grid_cap(); return (c != 0 && c < n_wg) ? c : n_wg; }
 }  // namespace mi

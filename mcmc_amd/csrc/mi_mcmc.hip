@@ -109,6 +109,20 @@ extern "C" uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint6
 {
     return mi::gemm::gemm_nuts_range_chains(n_chains, (size_t)chain_bytes, (size_t)fixed_bytes, (size_t)budget);
 }
+// test hooks, declared in mi_mcmc_probes.h, for every sampler of the matrix-product route: never capture a graph (run_gemm, run_gemm_nuts), the memory the capacity
+// condition of hmc / mala / rwmh sees (gemm_fits), and what it compares with it (gemm_need_bytes: host arithmetic)
+namespace {
+std::atomic<int> g_gemm_graph_mode{0};
+std::atomic<uint64_t> g_gemm_ws_bytes{0};
+enum : int { GEMM_PLAIN = 0, GEMM_DENSE_M = 1, GEMM_BOUNDED = 2 };
+size_t gemm_need_bytes(uint64_t d, uint64_t n, uint64_t C, int variant, bool replay);
+}
+extern "C" void mi_mcmc_test_set_gemm_graph(int mode) { g_gemm_graph_mode.store(mode, std::memory_order_relaxed); }
+extern "C" void mi_mcmc_test_set_gemm_ws_bytes(uint64_t bytes) { g_gemm_ws_bytes.store(bytes, std::memory_order_relaxed); }
+extern "C" uint64_t mi_mcmc_test_gemm_need_bytes(uint32_t d, uint32_t n_rows, uint64_t n_chains, int variant, int replay)
+{
+    return gemm_need_bytes(d, n_rows, n_chains, variant, replay != 0);
+}
 
 namespace {
 
@@ -972,42 +986,46 @@ int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_s
 // A DENSE precond_mat (hmc, mala) rides the same route -- products with INV(M), CHOL_LOWER(M), M, INV(eps^2 M) next to the gradient's -- where the route can hold it:
 // what it cannot (a matrix beyond the device factorisations of linalg_device.hip, a launch grid out of range, a workspace -- three more packed matrices, four more
 // state vectors -- beyond the free device memory) stays on the literal kernel, as before
-constexpr uint64_t GEMM_DENSE_M_MAX_D = LINALG_STAGE_BYTES / (2 * sizeof(double));      // 3840: device_inverse's LDS-staged pivot row ...
-bool gemm_dense_mass_fits(const mi_target* target, const mi_chains* chains, hipStream_t st)
+constexpr uint64_t GEMM_DENSE_M_MAX_D = LINALG_STAGE_BYTES / (2 * sizeof(double));      // 3840: device_inverse's LDS-staged pivot row
+// what the capacity condition compares with the memory there is: the route's workspace (with `replay` the flags and the literal replay's matrix and work areas behind
+// it: hmc, mala) and the uploads next to it -- the tables and a host target's matrix; with a dense precond_mat the replay's transposed matrices (lit_upload)
+size_t gemm_need_bytes(uint64_t d, uint64_t n, uint64_t C, int variant, bool replay)
 {
-    const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
-    if (d > GEMM_DENSE_M_MAX_D || !linalg_on_device(0, (size_t)d) || n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
-    const ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, true), C, (uint32_t)d, (uint32_t)(n ? n : d), false);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t uploads = 4 * (size_t)d * d * sizeof(double) + ((size_t)1 << 20);      // the replay's transposed matrices (lit_upload) and the tables
-    return rp.total_bytes + uploads <= free_b + ws_cached_bytes(st);      // (the cached workspace of this stream is given back before a larger one is taken)
+    const bool dm = variant == GEMM_DENSE_M;
+    const ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, dm, variant == GEMM_BOUNDED), C, (uint32_t)d, (uint32_t)(n ? n : d), false);
+    const size_t uploads = (dm ? 4 : 1) * (size_t)d * d * sizeof(double) + ((size_t)1 << 20);
+    return ((replay || dm) ? rp.total_bytes : rp.own_bytes) + uploads;
 }
-// settings.vals_bound rides the route for hmc (identity / DIAGONAL precond_mat) and rwmh (no cov_mat): the chains live in the transformed space and three more state
-// vectors hold x = inv_transform(theta), what the products read.  Capacity is a routing condition here too: what does not fit stays on the literal kernel
-bool gemm_bounded_fits(const mi_target* target, const mi_chains* chains, bool replay, hipStream_t st)
+// Capacity is a routing condition for every variant: what the route cannot hold (a launch grid out of range; a workspace beyond the free device memory; with a dense
+// precond_mat a matrix beyond the device factorisations of linalg_device.hip) stays on the literal kernel, with the same bits.  vals_bound rides the route for hmc
+// (identity / DIAGONAL precond_mat) and rwmh (no cov_mat): three more state vectors hold x = inv_transform(theta), what the products read
+bool gemm_fits(const mi_target* target, const mi_chains* chains, int variant, bool replay, hipStream_t st)
 {
     const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
-    if (d > 0x7fffffffULL || n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
-    const ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, false, true), C, (uint32_t)d, (uint32_t)(n ? n : d), false);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const size_t uploads = (size_t)d * d * sizeof(double) + ((size_t)1 << 20);      // (a host target's matrix and the tables)
-    return (replay ? rp.total_bytes : rp.own_bytes) + uploads <= free_b + ws_cached_bytes(st);
+    if (n > 0x7fffffffULL || (C + 127) / 128 * 2 > 65535) return false;      // (grid.x of the class-wise kernels: Cp / 64)
+    if (variant == GEMM_DENSE_M && (d > GEMM_DENSE_M_MAX_D || !linalg_on_device(0, (size_t)d))) return false;
+    size_t have = (size_t)g_gemm_ws_bytes.load(std::memory_order_relaxed);      // (the test hook: as if this were all there is)
+    if (have == 0) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+        have = free_b + ws_cached_bytes(st);                 // (the cached workspace of this stream is given back before a larger one is taken)
+    }
+    return gemm_need_bytes(d, n, C, variant, replay) <= have;
 }
 bool gemm_case(const mi_target* target, const mi_settings* settings, const mi_chains* chains, bool hmc, bool algo_has_mass = true, hipStream_t st = nullptr)
 {
     if (!((target->kind == MI_TARGET_GAUSS_DENSE || target->kind == MI_TARGET_LOGISTIC) && target->d > 512
           && !chains->mass_diag && target->kernel_hint != MI_KERNEL_LITERAL && (!hmc || settings->n_leap_steps >= 1))) return false;
+    if (target->d > 131056ULL) return false;             // (grid.y of the normals kernel: padded d / 2; gemm_nuts_case has the same guard)
     if (settings->vals_bound) {                          // hmc (identity / diagonal precond_mat) and rwmh (no cov_mat); bounded mala (its proposal covariance is J M per chain) stays literal
         if (!hmc && algo_has_mass) return false;
         if (settings->precond_mat && (!algo_has_mass || !precond_is_diagonal(settings, target->d))) return false;
         if (!settings->lower_bounds || !settings->upper_bounds) return true;      // (run_gemm reports the missing arrays)
-        return gemm_bounded_fits(target, chains, hmc, st);
+        return gemm_fits(target, chains, GEMM_BOUNDED, hmc, st);
     }
-    if (!settings->precond_mat) return true;
-    if (!algo_has_mass) return false;                    // rwmh with a cov_mat: the literal kernel
-    return precond_is_diagonal(settings, target->d) || gemm_dense_mass_fits(target, chains, st);      // (hmc, mala) a DIAGONAL precond_mat, or a dense one that fits
+    if (settings->precond_mat && !algo_has_mass) return false;                   // rwmh with a cov_mat: the literal kernel
+    const bool dense_m = settings->precond_mat && !precond_is_diagonal(settings, target->d);
+    return gemm_fits(target, chains, dense_m ? GEMM_DENSE_M : GEMM_PLAIN, algo_has_mass, st);      // (rwmh has no replay: run_gemm)
 }
 // the mass tables of the matrix-product route: n_tables tables of dK entries in one buffer -- m | sqrt(m) | 1 / m of a diagonal precond_mat, padded with
 // ones; everything else (the identity, a dense matrix, a fourth table) ones
@@ -1097,7 +1115,8 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     }
     // a draw is a handful of launches + one or two per gradient: replayed from a captured graph while a launch is short (few chains); at full size the queue runs ahead anyway
     // (per leapfrog step / mala draw: the gradient's products and, with a dense precond_mat, one / five with the mass matrices)
-    g.use_graph = ((double)d * (double)(logit ? 2 * n : d) + (g.dense_mass ? (algo == 0 ? 1.0 : 5.0) * (double)d * (double)d : 0.0)) * (double)C < 3.0e10;
+    g.use_graph = ((double)d * (double)(logit ? 2 * n : d) + (g.dense_mass ? (algo == 0 ? 1.0 : 5.0) * (double)d * (double)d : 0.0)) * (double)C < 3.0e10
+                  && g_gemm_graph_mode.load(std::memory_order_relaxed) == 0;      // (the test hook: never capture)
     const bool replay = algo != 3;                       // rwmh forms no product with a vector that can be non-finite (rwmh.cpp:126)
     WsLease base;
     ReplayWs rp = replay_layout(mi::gemm::gemm_ws_bytes((uint32_t)d, (uint32_t)n, C, g.dense_mass, bounded), C, (uint32_t)d, (uint32_t)(logit ? n : d), false);
@@ -2947,11 +2966,12 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     g.ws = base.p;
     const char* kname = nullptr;
     uint64_t ticks = 0, points = 0, slots = 0;
+    const bool may_graph = g_gemm_graph_mode.load(std::memory_order_relaxed) == 0;      // (the test hook: never capture)
     for (uint64_t c_off = 0; c_off < C; c_off += plan.range) {           // the chains as consecutive ranges: the same code, the global chain index
         g.c_off = c_off; g.C = std::min<uint64_t>(plan.range, C - c_off); g.pack = c_off == 0;
         // a tick is a handful of short launches while the chains are few: replayed from a captured (linear) graph; at full size the queue runs ahead anyway
         // (the threshold is run_gemm's, taken over and not varied here: at d = 1024 the measured tick is far longer than a launch on both sides of it -- DESIGN 4.22)
-        g.use_graph = (double)d * (double)(logit ? 2 * n : d) * (double)g.C < 3.0e10;
+        g.use_graph = may_graph && (double)d * (double)(logit ? 2 * n : d) * (double)g.C < 3.0e10;
         const int e = mi::gemm::gemm_nuts_run(g, st, &kname);
         if (e != 0) return fail(MI_ERR_HIP, "nuts: matrix-product sampler: %s", hipGetErrorString((hipError_t)e));
         if (g.still_running != 0)

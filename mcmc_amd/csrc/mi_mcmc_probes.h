@@ -14,7 +14,10 @@ int mi_probe_fp64_peak(int use_mfma, int iters, double* tflops_out);
 int mi_probe_mfma_cycles(int waves_per_simd, int use_lds, int iters, double* cycles_per_mfma, double* tflops_out);
 /* Defined in libmi_mcmc.so itself (a test hook, not a product entry point: it is declared here, not in mi_mcmc.h): limits the PERSISTENT grids of
  * the NUTS kernels with dynamic chain hand-out (nuts_memo.hpp, nuts_lds.hpp) to max_workgroups (0 = no limit), so that a test with a
- * few hundred chains runs the global counter, slot re-use and retire-on-leave.  Process-wide.  Results do not depend on it. */
+ * few hundred chains runs the global counter, slot re-use and retire-on-leave.  The grid-stride grids of the matrix-product route beyond d = 512
+ * (gemm_samplers.hip, gemm_nuts.hpp: the packs, the load and store of the state, the logistic row terms, the nuts init) take the same limit, so that a
+ * test of a thousand chains runs the later passes of their loops, which otherwise need more than 16.7 M padded elements (65 535 workgroups; the row
+ * terms: 2^20).  Kernels that index by workgroup id are not limited.  Process-wide.  Results do not depend on it. */
 void mi_mcmc_test_set_grid_cap(uint32_t max_workgroups);
 /* Defined in libmi_mcmc.so itself (a test hook like the one above): lowers the staging budget of the device INV / CHOL_LOWER of a dense precond_mat
  * (host_linalg.hpp, linalg_device.hip: 2 d doubles for INV, d for CHOL_LOWER, 60 KB of LDS) to `bytes` (0, or more than the real budget = the real
@@ -43,6 +46,19 @@ uint64_t mi_mcmc_test_gemm_nuts_tick_ceiling(uint32_t max_tree_depth, uint64_t n
 uint64_t mi_mcmc_test_gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth);
 uint64_t mi_mcmc_test_gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows);
 uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint64_t chain_bytes, uint64_t fixed_bytes, uint64_t budget);
+/* Defined in libmi_mcmc.so itself (test hooks like the ones above), for hmc / mala / rwmh and nuts beyond d = 512 on the matrix-product route:
+ * mode 1 never captures the launches of a draw / a tick into a graph -- every draw enqueues them itself, what a call of 65 536 chains does (its launches are long,
+ * the rule is work x chains < 3e10) --; mode 0 is the rule as it is.  It skips the capture, nothing else: no environment variable, no runtime setting.  Process-wide,
+ * read once per call.  Results do not depend on it. */
+void mi_mcmc_test_set_gemm_graph(int mode);
+/* ... the device memory the capacity condition of hmc / mala / rwmh on the route sees in place of the free memory plus this stream's cached workspace (0 = the real
+ * figure): a call whose need exceeds it stays on the literal kernel, same bits.  Process-wide.  Results do not depend on it. */
+void mi_mcmc_test_set_gemm_ws_bytes(uint64_t bytes);
+/* ... and that need -- exactly the left-hand side of the condition; host arithmetic, no device: the route's workspace (gemm_ws_bytes) rounded up to 256, with
+ * replay != 0 (hmc, mala: always with a dense precond_mat) the non-finite flags and the literal replay's transposed matrix and work areas behind it, and the uploads
+ * next to it -- 1 MiB for the tables plus the target's d x d matrix, with a dense precond_mat the replay's four d x d matrices instead.
+ * variant: 0 identity / diagonal precond_mat, 1 a dense precond_mat, 2 vals_bound.  n_rows = 0: the dense Gaussian. */
+uint64_t mi_mcmc_test_gemm_need_bytes(uint32_t d, uint32_t n_rows, uint64_t n_chains, int variant, int replay);
 #ifdef __cplusplus
 }
 #endif

@@ -40,3 +40,6 @@ case("mala d=192 diag precond (LDS)", "mala", D, 192, precond_mat=np.diag(np.lin
 case("mala d=192 dense precond (LDS)", "mala", D, 192, precond_mat=spd(192))
 lb, ub = box(520)
 case("hmc d=520 diag precond + bounds (matrix-product)", "hmc", D, 520, precond_mat=np.diag(np.linspace(0.5, 2.0, 520)), vals_bound=1, lower_bounds=lb, upper_bounds=ub)
+# the plain variants of the matrix-product route: identity precond_mat, no bounds (capacity is a routing condition for them too: one hipMemGetInfo per call)
+case("hmc d=520 (matrix-product, plain)", "hmc", D, 520)
+case("rwmh d=520 (matrix-product, plain)", "rwmh", D, 520)
