@@ -608,6 +608,52 @@ int mi_mcmc_draws_quantiles(const double* draws_kdc, int32_t mem, uint64_t n_kee
                             const double* probs /* host, n_probs values in [0, 1] */, uint32_t n_probs /* <= 16 */,
                             double* out /* host, [n_probs][d] */, void* stream);
 
+/* Exact ranks, normal scores and the rank-normalised diagnostics of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: Vehtari,
+ * Gelman, Simpson, Carpenter and Buerkner (2021), "Rank-normalization, folding, and localization: an improved R-hat".  Blocking.  Workspace: the
+ * stream's cached one (mi_mcmc_release_workspace).  No CPU path: no device is MI_ERR_NO_DEVICE (mi_mcmc_norm_ppf is host arithmetic and needs none).
+ * MI_ERR_BAD_ARG, before any HIP call: a NULL slab or out; all five outputs NULL; d = 0 or d > 65 536; n_keep or n_chains beyond 32 bits; S = 0 or
+ * S >= 2^32; an unknown `what` or flag bit; n_keep < 2 with MI_RANK_SPLIT; n_keep < 4 for mi_mcmc_draw_stats_ranked.
+ * fp64, every operation rounded once, nothing contracted.
+ * RETAINED ROWS AND LAYOUT.  Without MI_RANK_SPLIT every row is retained and out is [n_keep][d][C].  With it h = floor(n_keep / 2), the retained
+ *   rows are t < h and t >= n_keep - h (the middle row of an odd n_keep is not read) and out is [h][d][2C]:
+ *     out[t][i][c]     from x[t][i][c]
+ *     out[t][i][C + c] from x[n_keep - h + t][i][c]
+ *   the slab of 2C half-chains, which mi_mcmc_draw_stats takes as it is.  S is the number of retained samples of a dimension (n_keep C, or 2 h C).
+ * VALUE RANKED.  v = x, or with MI_RANK_FOLD v = |x - med_i|: one subtraction, then the sign cleared; med_i is the type-7 quantile at p = 0.5 of
+ *   dimension i's S retained samples, by mi_mcmc_draws_quantiles' rule above (K = S).
+ * ORDER.  The 64-bit key of mi_mcmc_draws_order_stats, unchanged: -0.0 sorts below +0.0, every NaN has one key, above +inf.
+ * RANK.  lo = the number of retained keys of the dimension below key(v), hi = the number not above it; R2 = lo + hi + 1 is twice the average
+ *   1-based rank.  MI_RANK_AVERAGE writes 0.5 * (double)R2 (exact: a multiple of 0.5).  A NaN v counts in S and in the ranks of the others, and
+ *   itself comes out as the canonical quiet NaN 0x7FF8000000000000, for both values of `what`.
+ * NORMAL SCORE.  MI_RANK_NORMAL writes z = norm_ppf(p), p = (0.5 * (double)R2 - 0.375) / ((double)S + 0.25).  p lies strictly inside (0, 1) for
+ *   every S >= 1, so z is finite for every non-NaN sample, +-inf included; a constant dimension gives p = 0.5 exactly and z = +0.0.
+ * norm_ppf.  Wichura's algorithm AS 241, routine PPND16, one function for the host and the device (include/mi_mcmc_engine/det_math.hpp): three
+ *   rational polynomials in nested Horner form, plain multiplies and adds, one division; |p - 0.5| <= 0.425 the central one in r = 0.180625 - q^2,
+ *   otherwise r = sqrt(-det_log(min(p, 1 - p))) and the branches r <= 5 and r > 5; coefficients, limits and nesting as in CPython's
+ *   statistics.NormalDist.inv_cdf.  p <= 0 gives -inf, p >= 1 gives +inf, NaN gives NaN.
+ * The ranks come from a full sort of every dimension's keys (mcmc_amd/csrc/draws_rank.hip: a radix sort whose counts are integers, and a search of
+ * every sample in the sorted image): the result depends on no grid, timing or atomic order.  The numpy statement is mcmc_amd/rank_stats.py. */
+#define MI_RANK_AVERAGE 0      /* out = the average 1-based rank, as a double (exact: a multiple of 0.5) */
+#define MI_RANK_NORMAL  1      /* out = z, the normal score of that rank */
+#define MI_RANK_SPLIT   1u     /* flags: split every chain into halves */
+#define MI_RANK_FOLD    2u     /* flags: rank |x - med_i| instead of x */
+int mi_mcmc_draws_rank_transform(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                                 int32_t what, uint32_t flags, double* out /* in `mem` */, void* stream);
+/* The diagnostics, composed of the transform above and mi_mcmc_draw_stats, whose R-hat formula and Geyer ESS are unchanged and here apply to a slab
+ * of 2C half-chains of length h (outputs: HOST arrays [d], any of them may be NULL):
+ *   rhat_bulk, ess_bulk   R-hat and ESS of the MI_RANK_SPLIT, MI_RANK_NORMAL slab
+ *   rhat_tail             R-hat of the MI_RANK_SPLIT | MI_RANK_FOLD, MI_RANK_NORMAL slab
+ *   rhat                  the larger of the two, NaN if either is NaN
+ *   ess_tail              the smaller of the ESS of the two indicator slabs 1{x <= q05_i} and 1{x <= q95_i} (values 0.0 / 1.0 in the split layout; q
+ *                         the type-7 quantile of the retained samples; a NaN x gives a NaN indicator)
+ * The ESS values are per HALF-chain, as mi_mcmc_draw_stats' are per chain: the many-chain figure is 2C times it.  A dimension with a NaN among its
+ * retained samples gives NaN in all five outputs.  What a dimension gives for which mi_mcmc_draw_stats has no defined answer on the composed slab
+ * (a constant dimension) is whatever that function returns there. */
+int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                              double* rhat, double* rhat_bulk, double* rhat_tail, double* ess_bulk, double* ess_tail, /* host [d], any may be NULL */
+                              void* stream);
+int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z);   /* host arrays, host arithmetic, needs no device */
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

@@ -93,6 +93,7 @@ EXPORTS = [
     "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
     "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
     "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
+    "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -780,3 +781,46 @@ def draws_to_chain_major_device(draws, n_keep, d, n_chains, out, stream=None):
     """mi_mcmc_draws_to_chain_major_device: slab [n_keep][d][C] in HBM -> [C][d][n_keep] in HBM (device tensors / pointers)."""
     _check(lib().mi_mcmc_draws_to_chain_major_device(C.c_void_p(_ptr(draws)), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
                                                      C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
+
+
+RANK_AVERAGE, RANK_NORMAL = 0, 1
+RANK_SPLIT, RANK_FOLD = 1, 2
+
+
+def norm_ppf(p):
+    """mi_mcmc_norm_ppf: the standard normal quantile as the library computes it on the host AND on the device (AS 241 PPND16 over the engine's
+    deterministic logarithm; include/mi_mcmc.h).  Needs no device.  Returns an array of p's shape."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    z = np.empty_like(p)
+    _check(lib().mi_mcmc_norm_ppf(C.c_void_p(p.ctypes.data), C.c_uint64(p.size), C.c_void_p(z.ctypes.data)))
+    return z
+
+
+def draws_rank_transform(draws, what="normal", split=False, fold=False, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, out=None):
+    """mi_mcmc_draws_rank_transform: the exact average rank (what="average") or its normal score (what="normal") of every retained sample of a slab
+    [n_keep, d, C] among the retained samples of its dimension (numpy array, or a device tensor / pointer with mem=MEM_DEVICE, explicit shape and a
+    device `out`); split: the halves of every chain side by side, [n_keep // 2, d, 2 C]; fold: ranks of |x - median|.  mcmc_amd.rank_stats states
+    the result bit for bit.  Returns the transformed slab (`out` where one was passed)."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    if what not in ("average", "normal", RANK_AVERAGE, RANK_NORMAL):
+        raise ValueError(f"what = {what!r}: 'average' or 'normal'")
+    w = {"average": RANK_AVERAGE, "normal": RANK_NORMAL}.get(what, what)
+    flags = (RANK_SPLIT if split else 0) | (RANK_FOLD if fold else 0)
+    if out is None:
+        if mem != MEM_HOST:
+            raise ValueError("a device slab needs a device `out`")
+        out = np.zeros((n_keep // 2, d, 2 * n_chains) if split else (n_keep, d, n_chains))
+    _check(lib().mi_mcmc_draws_rank_transform(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
+                                              C.c_int32(w), C.c_uint32(flags), C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
+    return out
+
+
+def draw_stats_ranked(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None):
+    """mi_mcmc_draw_stats_ranked: rank-normalised split-R-hat (rhat = max(rhat_bulk, rhat_tail)), bulk-ESS and tail-ESS per dimension of a slab
+    [n_keep, d, C] (Vehtari et al. 2021).  The ESS values are per half-chain: the many-chain figure is 2 C times them.  Returns a dict of [d] arrays."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    names = ("rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail")
+    res = {k: np.zeros(d) for k in names}
+    _check(lib().mi_mcmc_draw_stats_ranked(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
+                                           *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(stream or 0)))
+    return res

@@ -63,19 +63,6 @@ SelPlan sel_plan(uint64_t n_keep, uint64_t d, uint64_t C, uint32_t n_ranks)
 
 namespace {
 
-__device__ __forceinline__ uint64_t sel_key(double v)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    if ((u & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return ~0ull;       // any NaN
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double sel_unkey(uint64_t k)
-{
-    const uint64_t u = k == ~0ull ? 0x7FF8000000000000ull : ((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k);
-    return __longlong_as_double((long long)u);
-}
-
 // ROUND: 0-based; the prefix holds 8 * ROUND bits.  ROUND 0 is its own instantiation (no state is read, the counts are stored, not added).
 template <bool FIRST>
 __global__ __launch_bounds__(256) void sel_hist_kernel(const double* __restrict__ x, uint64_t n_keep, uint64_t d, uint64_t C, uint64_t dim0, uint32_t n_ranks,

@@ -38,6 +38,20 @@ struct SelPlan {
     size_t o_state0 = 0, o_state1 = 0, o_out = 0, o_part = 0, o_hist = 0, bytes = 0;
 };
 
+// the key of include/mi_mcmc.h's ORDER and its inverse (draws_rank.hip sorts by the same key)
+__device__ __forceinline__ uint64_t sel_key(double v)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    if ((u & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return ~0ull;       // any NaN
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ double sel_unkey(uint64_t k)
+{
+    const uint64_t u = k == ~0ull ? 0x7FF8000000000000ull : ((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k);
+    return __longlong_as_double((long long)u);
+}
+
 struct SelRanks { uint64_t r[SEL_MAX_RANKS]; };        // travels to the round-1 scan as a kernel argument
 
 SelPlan sel_plan(uint64_t n_keep, uint64_t d, uint64_t C, uint32_t n_ranks);

@@ -39,6 +39,7 @@
 #include "gemm_samplers.hpp"
 #include "draws_cov.hpp"
 #include "draws_select.hpp"
+#include "draws_rank.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
 #include "settings_host.hpp"
@@ -116,6 +117,19 @@ std::atomic<int> g_gemm_graph_mode{0};
 std::atomic<uint64_t> g_gemm_ws_bytes{0};
 enum : int { GEMM_PLAIN = 0, GEMM_DENSE_M = 1, GEMM_BOUNDED = 2 };
 size_t gemm_need_bytes(uint64_t d, uint64_t n, uint64_t C, int variant, bool replay);
+}
+// test hooks, declared in mi_mcmc_probes.h: the workspace budget of the rank transform's groups of dimensions (draws_rank.hpp) and the host arithmetic of its
+// group rule, which needs no device
+namespace { std::atomic<uint64_t> g_rank_ws_bytes{0}; }
+extern "C" void mi_mcmc_test_set_rank_ws_bytes(uint64_t bytes) { g_rank_ws_bytes.store(bytes, std::memory_order_relaxed); }
+extern "C" void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes) { mi::drank::rank_counts(sorts, passes); }
+extern "C" uint64_t mi_mcmc_test_rank_dim_bytes(uint64_t n_keep, uint64_t n_chains, uint32_t flags, int stats)
+{
+    return mi::drank::rank_dim_bytes(n_keep, n_chains, flags, stats != 0);
+}
+extern "C" uint64_t mi_mcmc_test_rank_dims_per_group(uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t flags, int stats)
+{
+    return mi::drank::rank_plan(n_keep, d, n_chains, flags, stats != 0, g_rank_ws_bytes.load(std::memory_order_relaxed)).dims_per_group;
 }
 extern "C" void mi_mcmc_test_set_gemm_graph(int mode) { g_gemm_graph_mode.store(mode, std::memory_order_relaxed); }
 extern "C" void mi_mcmc_test_set_gemm_ws_bytes(uint64_t bytes) { g_gemm_ws_bytes.store(bytes, std::memory_order_relaxed); }
@@ -2345,6 +2359,191 @@ int mi_mcmc_draws_quantiles(const double* draws_kdc, int32_t mem, uint64_t n_kee
             }
         }
     }
+    return MI_OK;
+}
+
+namespace {
+// The checks that mi_mcmc_draws_rank_transform and mi_mcmc_draw_stats_ranked share: they need no device
+int rank_check(const char* who, const double* draws_kdc, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t flags)
+{
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (d > mi::drank::RANK_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::drank::RANK_MAX_D);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (flags & ~(uint32_t)(MI_RANK_SPLIT | MI_RANK_FOLD)) return fail(MI_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", who, flags);
+    if ((flags & MI_RANK_SPLIT) && n_keep < 2) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, MI_RANK_SPLIT needs at least 2 draws", who, (unsigned long long)n_keep);
+    const uint64_t rows = (flags & MI_RANK_SPLIT) ? 2 * (n_keep / 2) : n_keep;
+    // rows, n_chains < 2^32: the product does not wrap
+    if (rows * n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: S = 0 retained samples, at least 1 is needed", who);
+    if (rows * n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: S = %llu retained samples per dimension, must be below 2^32", who, (unsigned long long)(rows * n_chains));
+    return MI_OK;
+}
+
+// (lo, hi, g) of the type-7 rule for one probability over S samples: mi_mcmc_draws_quantiles' arithmetic
+void type7_ranks(uint64_t S, double prob, uint64_t* lo, uint64_t* hi, double* g)
+{
+    const double h = prob * (double)(S - 1);
+    const double fl = std::floor(h);
+    *lo = fl >= (double)(S - 1) ? S - 1 : (uint64_t)fl;
+    *g = h - (double)*lo;
+    *hi = *lo + 1 < S ? *lo + 1 : S - 1;
+}
+double type7_value(double x_lo, double x_hi, double g)
+{
+    if (g == 0.0) return x_lo;
+    const double diff = x_hi - x_lo;
+    const double prod = g * diff;
+    return x_lo + prod;
+}
+
+// med (and with tails the 5 % and 95 % quantiles) of the group's dimensions out of the sorted image of their un-folded keys, onto the device at
+// ws + o_med (+ o_q); nan_dims (may be NULL): whether the dimension holds a NaN (its largest key is the NaN key)
+int rank_group_quantiles(const mi::drank::RankPlan& plan, uint64_t dim0, uint64_t nd, const uint64_t* sorted, bool tails, char* W, hipStream_t st,
+                         std::vector<double>& os, std::vector<double>& q, std::vector<uint8_t>* nan_dims)
+{
+    const double probs[3] = {0.5, 0.05, 0.95};
+    uint64_t ranks[8];
+    double g[3];
+    for (int a = 0; a < 3; ++a) type7_ranks(plan.S, probs[a], &ranks[2 * a], &ranks[2 * a + 1], &g[a]);
+    ranks[6] = ranks[7] = plan.S - 1;                    // the largest key: the NaN key if the dimension holds a NaN
+    os.resize(8 * nd);
+    q.resize(3 * nd);
+    HIP_TRY((hipError_t)mi::drank::rank_order_stats_group(plan, nd, sorted, ranks, W, os.data(), st));
+    if (nan_dims)
+        for (uint64_t j = 0; j < nd; ++j) (*nan_dims)[dim0 + j] = os[6 * nd + j] != os[6 * nd + j];
+    for (int a = 0; a < 3; ++a)
+        for (uint64_t j = 0; j < nd; ++j) q[a * nd + j] = type7_value(os[(2 * a) * nd + j], os[(2 * a + 1) * nd + j], g[a]);
+    HIP_TRY(hipMemcpyAsync(W + plan.o_med + dim0 * 8, q.data(), nd * 8, hipMemcpyHostToDevice, st));
+    if (tails) {
+        HIP_TRY(hipMemcpyAsync(W + plan.o_q + dim0 * 8, q.data() + nd, nd * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(W + plan.o_q + (plan.d + dim0) * 8, q.data() + 2 * nd, nd * 8, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // q is this frame's: the uploads have read it
+    return MI_OK;
+}
+}  // namespace
+
+// Average ranks / normal scores of the retained samples of a slab [n_keep][d][C] (draws_rank.hip; the definitions: include/mi_mcmc.h)
+int mi_mcmc_draws_rank_transform(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, int32_t what, uint32_t flags,
+                                 double* out, void* stream)
+{
+    const char* who = "draws_rank_transform";
+    int rc = rank_check(who, draws_kdc, n_keep, d, n_chains, flags);
+    if (rc) return rc;
+    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
+    if (what != MI_RANK_AVERAGE && what != MI_RANK_NORMAL) return fail(MI_ERR_BAD_ARG, "%s: what = %d is neither MI_RANK_AVERAGE nor MI_RANK_NORMAL", who, what);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const mi::drank::RankPlan plan = mi::drank::rank_plan(n_keep, d, n_chains, flags, false, g_rank_ws_bytes.load(std::memory_order_relaxed));
+    DevBuf staged, out_dev;
+    const double* x = draws_kdc;
+    double* o = out;
+    if (mem == MI_MEM_HOST) {
+        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
+        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
+        x = staged.as<double>();
+        HIP_TRY(out_dev.alloc(plan.S * d * 8));
+        o = out_dev.as<double>();
+    }
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    const bool fold = (flags & MI_RANK_FOLD) != 0;
+    std::vector<double> os, q;
+    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
+        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
+        const uint64_t* sorted = nullptr;
+        HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, false, W, st, &sorted));
+        if (fold) {                                      // the medians out of the un-folded image, then the sort of |x - med|
+            rc = rank_group_quantiles(plan, dim0, nd, sorted, false, W, st, os, q, nullptr);
+            if (rc) return rc;
+            HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
+        }
+        HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, fold, what, sorted, W, o, d, dim0, st));
+    }
+    if (mem == MI_MEM_HOST) HIP_TRY(hipMemcpyAsync(out, o, plan.S * d * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // blocking: the staged slab, the staged output and the workspace are ours
+    return MI_OK;
+}
+
+// Rank-normalised split-R-hat, bulk-ESS and tail-ESS: the pieces above and mi_mcmc_draw_stats on the composed slabs (include/mi_mcmc.h)
+int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* rhat, double* rhat_bulk,
+                              double* rhat_tail, double* ess_bulk, double* ess_tail, void* stream)
+{
+    const char* who = "draw_stats_ranked";
+    int rc = rank_check(who, draws_kdc, n_keep, d, n_chains, MI_RANK_SPLIT);
+    if (rc) return rc;
+    if (!rhat && !rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail) return fail(MI_ERR_BAD_ARG, "%s: all five outputs are NULL, nothing is asked for", who);
+    if (n_keep < 4) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, at least 4 draws are needed (two halves of two)", who, (unsigned long long)n_keep);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const mi::drank::RankPlan plan = mi::drank::rank_plan(n_keep, d, n_chains, MI_RANK_SPLIT, true, g_rank_ws_bytes.load(std::memory_order_relaxed));
+    DevBuf staged;
+    const double* x = draws_kdc;
+    if (mem == MI_MEM_HOST) {
+        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
+        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
+        x = staged.as<double>();
+    }
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    double* slab = reinterpret_cast<double*>(W + plan.o_slab);
+    const bool want_bulk = rhat || rhat_bulk || ess_bulk, want_fold = rhat || rhat_tail, want_tail = ess_tail != nullptr;
+    std::vector<double> rb(d), rt(d), eb(d), et(d), e05, e95, os, q;
+    std::vector<uint8_t> has_nan(d, 0);
+    const uint64_t h = plan.h, C2 = 2 * n_chains;
+    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
+        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
+        const uint64_t* sorted = nullptr;
+        HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, false, W, st, &sorted));
+        rc = rank_group_quantiles(plan, dim0, nd, sorted, true, W, st, os, q, &has_nan);
+        if (rc) return rc;
+        if (want_bulk) {
+            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, false, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
+            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rb.data() + dim0, ess_bulk ? eb.data() + dim0 : nullptr, stream);
+            if (rc) return rc;
+        }
+        if (want_tail) {
+            e05.resize(nd); e95.resize(nd);
+            HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 0, W, slab, st));
+            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e05.data(), stream);
+            if (rc) return rc;
+            HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 1, W, slab, st));
+            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e95.data(), stream);
+            if (rc) return rc;
+            for (uint64_t j = 0; j < nd; ++j) et[dim0 + j] = e95[j] < e05[j] ? e95[j] : e05[j];
+        }
+        if (want_fold) {
+            HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
+            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, true, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
+            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rt.data() + dim0, nullptr, stream);
+            if (rc) return rc;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    const double nan = std::nan("");
+    for (uint64_t i = 0; i < d; ++i) {
+        const bool bad = has_nan[i] != 0;                // a NaN among the retained samples: every output of the dimension is NaN
+        if (rhat_bulk) rhat_bulk[i] = bad ? nan : rb[i];
+        if (rhat_tail) rhat_tail[i] = bad ? nan : rt[i];
+        if (rhat) rhat[i] = (bad || rb[i] != rb[i] || rt[i] != rt[i]) ? nan : (rb[i] > rt[i] ? rb[i] : rt[i]);
+        if (ess_bulk) ess_bulk[i] = bad ? nan : eb[i];
+        if (ess_tail) ess_tail[i] = bad ? nan : et[i];
+    }
+    return MI_OK;
+}
+
+int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
+{
+    if (n && (!p || !z)) return fail(MI_ERR_BAD_ARG, "norm_ppf: null array");
+    for (uint64_t k = 0; k < n; ++k) z[k] = mi::norm_ppf(p[k]);
     return MI_OK;
 }
 

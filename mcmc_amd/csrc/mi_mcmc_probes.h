@@ -59,6 +59,17 @@ void mi_mcmc_test_set_gemm_ws_bytes(uint64_t bytes);
  * next to it -- 1 MiB for the tables plus the target's d x d matrix, with a dense precond_mat the replay's four d x d matrices instead.
  * variant: 0 identity / diagonal precond_mat, 1 a dense precond_mat, 2 vals_bound.  n_rows = 0: the dense Gaussian. */
 uint64_t mi_mcmc_test_gemm_need_bytes(uint32_t d, uint32_t n_rows, uint64_t n_chains, int variant, int replay);
+/* Defined in libmi_mcmc.so itself (test hooks like the ones above), for mi_mcmc_draws_rank_transform / mi_mcmc_draw_stats_ranked (draws_rank.hpp): the
+ * workspace budget of one group of dimensions in bytes (0, or more than the real budget = the real budget), so that a test at d = 5 runs the loop over
+ * groups that a slab of gigabytes runs.  Process-wide.  Results do not depend on it. */
+void mi_mcmc_test_set_rank_ws_bytes(uint64_t bytes);
+/* ... and the host arithmetic of the group rule, which needs no device: the bytes a dimension takes (stats != 0: with the composed slab of
+ * mi_mcmc_draw_stats_ranked), and the dimensions per group under the budget set above. */
+uint64_t mi_mcmc_test_rank_dim_bytes(uint64_t n_keep, uint64_t n_chains, uint32_t flags, int stats);
+uint64_t mi_mcmc_test_rank_dims_per_group(uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t flags, int stats);
+/* ... and the sorts run so far (one per group of dimensions and kind of key: x, |x - med|) and the radix passes they executed, at most eight each: a pass
+ * whose digit is one value for every key of the group is skipped, and these counts are the only thing that tells a test so.  Process-wide, monotonic. */
+void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes);
 #ifdef __cplusplus
 }
 #endif
