@@ -654,6 +654,37 @@ int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_k
                               void* stream);
 int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z);   /* host arrays, host arithmetic, needs no device */
 
+/* The log-posterior trace of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: out[t][c] = log K(x[t][:][c]), the target's own
+ * log-kernel at every kept draw of every chain, d = target->d.  The chains' current state mi_chains.theta ([d][C]) is the case n_keep = 1.
+ * target->prec / X / y live in target->mem, as for the samplers; kernel_hint is ignored.  out is [n_keep][C] in `mem` -- exactly a slab [n_keep][1][C],
+ * so mi_mcmc_draw_stats, mi_mcmc_draw_stats_ranked, mi_mcmc_draws_quantiles and mi_mcmc_draws_covariance take it as it is, with d = 1.  A device slab:
+ * the call returns after enqueueing on `stream` (with a target in host memory: once its arrays have been read).  A host slab: blocking.  Draws are
+ * stored in the original space, and the value is the target's log-kernel there: no bounds, no Jacobian.  Workspace: the stream's cached one
+ * (mi_mcmc_release_workspace) -- the packed matrix and the staged copies of a host slab, result and target.  No CPU path: no device is
+ * MI_ERR_NO_DEVICE; what does not fit the free device memory is MI_ERR_OOM.
+ * MI_ERR_BAD_ARG, before any HIP call: a NULL target, slab or out; a struct_size mismatch; d, n_keep or n_chains 0; n_keep or n_chains beyond 32 bits;
+ * d > 65 536; DENSE / DIAG without prec; LOGISTIC / NORMAL_MODEL without their data or with n_rows = 0; NORMAL_MODEL with d != 2; an unknown kind.
+ * MI_ERR_UNSUPPORTED: MI_TARGET_GAUSS_MIXTURE -- left out of this reducer on purpose (mi_mcmc_aees_run evaluates it).
+ * DEFINITION (fp64, every operation rounded once, nothing contracted; exp / log: det_math.hpp).  x is the column, of d values.
+ *   dot4(a, b)  four chains over the n terms: q[i % 4] = fma(a_i, b_i, q[i % 4]), i ascending, each from +0; the result is (q0 + q2) + (q1 + q3)
+ *   sum4(a)     the same with q[i % 4] = q[i % 4] + a_i
+ *   ISO           -0.5 * dot4(x, x)
+ *   DIAG          w_i = prec_i * x_i;  -0.5 * dot4(x, w)
+ *   DENSE         w_i = the fma chain over j ascending of P_ij * x_j, from +0 (row i of the row-major matrix AS GIVEN: symmetry is not assumed);
+ *                 -0.5 * dot4(x, w)
+ *   LOGISTIC      eta_r = the fma chain over j ascending of X_rj * x_j, from +0
+ *                 softplus(eta) = eta > 0 ? eta + log(1 + exp(-eta)) : log(1 + exp(eta))
+ *                 term_r = y_r * eta_r - softplus(eta_r);  ll = sum4(term) over the n_rows rows;  ll - 0.5 * dot4(x, x)
+ *   NORMAL_MODEL  (mu, sigma) = x;  m2 = the chain fma(e, e, m2) over r ascending from +0, e = y_r - mu, n = (double)n_rows
+ *                 -(n * (0.5 * LOG_2PI + log(sigma))) - m2 / (2 * (sigma * sigma))
+ * The dense products run on v_mfma_f64_16x16x4_f64 with the contraction ascending -- the fma chain above -- and w / eta never reach memory
+ * (mcmc_amd/csrc/draws_logk.hip).  The result depends on no grid, timing or atomic order, and has this ONE order for every d: it is the order of the
+ * matrix-product route (d > 512), while for d <= 512 the samplers' internal energies use their routes' own blocked orders and may differ from this
+ * value in the last bits.  Non-finite samples propagate by the IEEE rules through exactly these expressions, in their own column and nowhere else;
+ * nothing is flagged or replayed. */
+int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains,
+                             double* out /* [n_keep][C], in `mem` */, void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

@@ -94,6 +94,7 @@ EXPORTS = [
     "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
     "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
     "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
+    "mi_mcmc_draws_log_kernel",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -824,3 +825,34 @@ def draw_stats_ranked(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, s
     _check(lib().mi_mcmc_draw_stats_ranked(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
                                            *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(stream or 0)))
     return res
+
+
+def draws_log_kernel(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, out=None):
+    """mi_mcmc_draws_log_kernel: the log-posterior trace out[t, c] = log K(draws[t, :, c]) of a slab [n_keep, d, C] under `target` (make_target; d is
+    the target's) -- numpy array, a 2-D [d, C] array being the case n_keep = 1, the chains' state; or a device tensor / pointer with mem=MEM_DEVICE,
+    explicit n_keep and n_chains and a device `out`, written on `stream` without waiting.  include/mi_mcmc.h states the value bit for bit.  Returns
+    [n_keep, C] (`out` where one was passed): as [n_keep, 1, C] it is a slab that draw_stats, draw_stats_ranked and draws_quantiles take."""
+    d = int(target.d)
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d_slab, n_chains = draws.shape
+        if d_slab != d:
+            raise ValueError(f"the slab has d = {d_slab}, the target d = {d}")
+    if out is None:
+        if mem != MEM_HOST:
+            raise ValueError("a device slab needs a device `out`")
+        out = np.zeros((int(n_keep), int(n_chains)))
+    _check(lib().mi_mcmc_draws_log_kernel(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                          C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
+    return out
+
+
+def test_logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_host=True):
+    """mi_mcmc_test_logk_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_log_kernel call, host arithmetic -- a dict of route (0 one lane per column,
+    1 the fused matrix product), grid, block, lds_bytes, Kp, ldA, n_row_tiles, ws_bytes."""
+    o = (C.c_uint64 * 8)()
+    lib().mi_mcmc_test_logk_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
+    return dict(zip(("route", "grid", "block", "lds_bytes", "Kp", "ldA", "n_row_tiles", "ws_bytes"), (int(v) for v in o)))

@@ -40,6 +40,7 @@
 #include "draws_cov.hpp"
 #include "draws_select.hpp"
 #include "draws_rank.hpp"
+#include "draws_logk.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
 #include "settings_host.hpp"
@@ -2544,6 +2545,91 @@ int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
 {
     if (n && (!p || !z)) return fail(MI_ERR_BAD_ARG, "norm_ppf: null array");
     for (uint64_t k = 0; k < n; ++k) z[k] = mi::norm_ppf(p[k]);
+    return MI_OK;
+}
+
+namespace {
+// The checks of mi_mcmc_draws_log_kernel: they need no device
+int log_kernel_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const double* out)
+{
+    if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
+    if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
+    if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (n_keep == 0 || n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = 0, at least 1 sample is needed", who);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (t->d > mi::dlogk::LOGK_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)mi::dlogk::LOGK_MAX_D);
+    switch (t->kind) {
+    case MI_TARGET_GAUSS_ISO: break;
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+        if (!t->prec) return fail(MI_ERR_BAD_ARG, "%s: target.prec is NULL", who);
+        break;
+    case MI_TARGET_LOGISTIC:
+        if (!t->X || !t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
+        break;
+    case MI_TARGET_NORMAL_MODEL:
+        if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
+        if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
+        break;
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is not implemented by this reducer", who);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, t->kind);
+    }
+    return MI_OK;
+}
+}  // namespace
+
+// TEST HOOK (mi_mcmc_probes.h): the plan of mi_mcmc_draws_log_kernel, host arithmetic
+void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out8)
+{
+    const mi::dlogk::LogkPlan p = mi::dlogk::logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host != 0, target_host != 0);
+    out8[0] = (uint64_t)p.route; out8[1] = p.grid; out8[2] = p.block; out8[3] = p.lds_bytes;
+    out8[4] = p.Kp; out8[5] = p.ldA; out8[6] = p.n_row_tiles; out8[7] = p.bytes;
+}
+
+// out[t][c] = log K(x[t][:][c]) of every column of a slab [n_keep][d][C] (draws_logk.hip; the arithmetic: include/mi_mcmc.h)
+int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, double* out, void* stream)
+{
+    const char* who = "draws_log_kernel";
+    int rc = log_kernel_check(who, target, draws_kdc, n_keep, n_chains, out);
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d, K = n_keep * n_chains;
+    // 2^38 columns are 2 TB of results alone: beyond any device, and what keeps the grid and every byte count below inside their types
+    const bool has_rows = target->kind == MI_TARGET_LOGISTIC || target->kind == MI_TARGET_NORMAL_MODEL;
+    if (K > (1ULL << 38) || (has_rows && target->n_rows > (1ULL << 38))) return fail(MI_ERR_OOM, "%s: K = %llu columns / n_rows = %llu do not fit the device memory", who, (unsigned long long)K, (unsigned long long)target->n_rows);
+    const bool slab_host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
+    const mi::dlogk::LogkPlan plan = mi::dlogk::logk_plan(target->kind, d, target->n_rows, n_keep, n_chains, slab_host, target_host);
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    const double* mat = target->kind == MI_TARGET_LOGISTIC ? target->X : target->prec;
+    const double* y = target->y;
+    if (target_host) {
+        if (plan.mat_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_mat, mat, plan.mat_doubles * 8, hipMemcpyHostToDevice, st)); mat = reinterpret_cast<const double*>(W + plan.o_mat); }
+        if (plan.y_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_y, y, plan.y_doubles * 8, hipMemcpyHostToDevice, st)); y = reinterpret_cast<const double*>(W + plan.o_y); }
+    }
+    const double* x = draws_kdc;
+    double* o = out;
+    if (slab_host) {
+        HIP_TRY(hipMemcpyAsync(W + plan.o_slab, draws_kdc, K * d * 8, hipMemcpyHostToDevice, st));
+        x = reinterpret_cast<const double*>(W + plan.o_slab);
+        o = reinterpret_cast<double*>(W + plan.o_out);
+    }
+    HIP_TRY((hipError_t)mi::dlogk::logk_run(plan, x, mat, y, W, o, st));
+    if (slab_host) {
+        HIP_TRY(hipMemcpyAsync(out, o, K * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // blocking: out is the caller's host array
+    } else if (target_host) {
+        HIP_TRY(hipStreamSynchronize(st));               // the caller's host arrays of the target have been read when the call returns
+    }
     return MI_OK;
 }
 

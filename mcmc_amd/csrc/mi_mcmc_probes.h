@@ -70,6 +70,11 @@ uint64_t mi_mcmc_test_rank_dims_per_group(uint64_t n_keep, uint64_t d, uint64_t 
 /* ... and the sorts run so far (one per group of dimensions and kind of key: x, |x - med|) and the radix passes they executed, at most eight each: a pass
  * whose digit is one value for every key of the group is skipped, and these counts are the only thing that tells a test so.  Process-wide, monotonic. */
 void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draws_log_kernel (draws_logk.hpp): the plan of a call, host arithmetic that
+ * needs no device.  kind: mi_target_kind; slab_host / target_host != 0: the slab (with the result) / the target is staged in the workspace.
+ * out8: route (0 one lane per column, 1 the fused matrix product), workgroups, threads per workgroup, LDS bytes per workgroup, the contraction extent Kp,
+ * the padded output rows ldA, the row tiles a workgroup walks, the workspace bytes. */
+void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out8);
 #ifdef __cplusplus
 }
 #endif
