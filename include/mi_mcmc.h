@@ -548,10 +548,16 @@ int mi_mcmc_draws_to_chain_major_device(const double* draws_kdc_dev, uint64_t n_
  *   rhat [d]          Gelman-Rubin potential scale reduction over the C chains
  *   ess  [d]          per-chain effective sample size (Geyer's initial positive sequence on acov); the many-chain ESS is
  *                     C times it.
- * With acov == NULL only as many lags are computed as Geyer's sum needs (blocks of 16, then 32 lags straight from HBM; a slowly
- * mixing series falls through to the full computation).  With acov: every lag for n_keep <= 160; for longer series (the
- * reference's default is 1 000 kept draws) lags 0..127, the acov rows beyond hold NaN and Geyer's sum runs over the computed
- * lags.  Blocking. */
+ * Which kernels serve a call depends on n_keep alone:
+ *   n_keep <= 128          every lag of every dimension in ONE pass over the slab, on the fp64 matrix cores, with or without acov;
+ *   129 <= n_keep <= 160   with acov every lag, in passes of 48 lags; with acov == NULL only as many lags as Geyer's sum needs: the first 16
+ *                          straight from HBM, then passes of 32 and of 48 lags over the dimensions whose sum has not met its first
+ *                          non-positive pair yet (a slowly mixing series goes through every pass);
+ *   n_keep > 160           (the reference's default is 1 000 kept draws) lags 0..127 from a kernel that streams the series through LDS; the
+ *                          acov rows beyond hold NaN and Geyer's sum runs over the computed lags.
+ * Accuracy: every output is that of exact arithmetic on the slab to within a few (n_keep + C) units of roundoff of its own terms -- R-hat to a
+ * relative (n_keep + C + 64) 2^-52 as long as the spread of the chain means stays below 1e6 within-chain standard deviations, whatever the
+ * means themselves are (DESIGN.md states the bounds; tests/draw_stats_ref.py derives them).  Blocking. */
 int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
                        double* mean, double* acov, double* rhat, double* ess, void* stream);
 

@@ -729,6 +729,15 @@ def draw_stats(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=N
     return dict(mean=mean, acov=acov, rhat=rhat, ess=ess)
 
 
+def test_draw_stats_last():
+    """mi_mcmc_test_draw_stats_last (TEST HOOK, mi_mcmc_probes.h): what this thread's last draw_stats call launched -- a dict of route (0 the one-pass Gram
+    kernel, 1 the window + lag-block ladder, 2 the streamed kernel), NB, G, tiles (64-chain tiles of the largest chain group), window_launches, lag_passes,
+    subset_passes, smallest_subset."""
+    o = (C.c_uint64 * 8)()
+    lib().mi_mcmc_test_draw_stats_last(o)
+    return dict(zip(("route", "NB", "G", "tiles", "window_launches", "lag_passes", "subset_passes", "smallest_subset"), (int(v) for v in o)))
+
+
 def draws_covariance(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_mean=True, want_cov=True):
     """mi_mcmc_draws_covariance: pooled mean [d] and covariance [d, d] of the n_keep * C columns of a slab [n_keep, d, C] (numpy array -- a
     2-D [d, C] array is the case n_keep = 1, the chains' state --, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape).

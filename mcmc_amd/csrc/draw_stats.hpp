@@ -22,15 +22,16 @@ constexpr int STATS_MAX_N = 160;          // series length up to which every lag
 constexpr int STATS_TILED_LAGS = 128;     // lags computed for longer series
 constexpr int STATS_TILE_T = 64;          // time steps per tile of the streamed variant: (TILE_T + 2 LAGS) x 64 doubles = 160 KB
 
-// partial sums of x over (t = 0, t_step, 2 t_step, ... < n; chains of group g) per dimension: out[g][j]
-__global__ __launch_bounds__(64) void stats_sum_kernel(const double* __restrict__ draws, uint32_t n, uint32_t t_step, uint32_t d, uint64_t C,
-                                                       uint32_t G, double* __restrict__ out)
+// partial sums of x - centre[j] (centre == nullptr: of x) over (t = 0, t_step, 2 t_step, ... < n; chains of group g) per dimension: out[g][j]
+__global__ __launch_bounds__(64) void stats_sum_kernel(const double* __restrict__ draws, const double* __restrict__ centre, uint32_t n, uint32_t t_step,
+                                                       uint32_t d, uint64_t C, uint32_t G, double* __restrict__ out)
 {
     const uint32_t j = blockIdx.x, g = blockIdx.y;
+    const double cj = centre ? centre[j] : 0.0;
     const uint64_t c_lo = (uint64_t)g * ((C + G - 1) / G), c_hi = (c_lo + (C + G - 1) / G < C) ? c_lo + (C + G - 1) / G : C;
     double s = 0.0;
     for (uint64_t c = c_lo + threadIdx.x; c < c_hi; c += 64)
-        for (uint32_t t = 0; t < n; t += t_step) s += draws[((size_t)t * d + j) * C + c];
+        for (uint32_t t = 0; t < n; t += t_step) s += draws[((size_t)t * d + j) * C + c] - cj;
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
     if (threadIdx.x == 0) out[(size_t)g * d + j] = s;
 }
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(64) void stats_acov_kernel(const double* __restrict
     const uint32_t nd = gridDim.x;
     const uint64_t per = (C + G - 1) / G;
     const uint64_t c_lo = (uint64_t)g * per, c_hi = (c_lo + per < C) ? c_lo + per : C;
-    const double mj = mean[j];
+    const double mj = mean[j], ej = mean[d + j];        // the centre in two parts (see the host): v = (x - mj) - ej
     const uint32_t npl = (b_hi - b_lo) * LB;            // lags of this pass
     for (uint32_t k = 0; k < npl; ++k) accl[(size_t)k * 64 + lane] = 0.0;
     double sm = 0.0, sm2 = 0.0, sv = 0.0;
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(64) void stats_acov_kernel(const double* __restrict
 #pragma unroll
             for (int u = 0; u < LB; ++u) {
                 if (t0 + u < n) {
-                    const double x = on ? xr[u] - mj : 0.0;
+                    const double x = on ? (xr[u] - mj) - ej : 0.0;
                     v[(size_t)(t0 + u) * 64 + lane] = x;
                     s1 += x;
                 }
@@ -138,20 +139,20 @@ __global__ __launch_bounds__(64) void stats_acov_tiled_kernel(const double* __re
     const uint32_t j = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
     const uint64_t per = (C + G - 1) / G;
     const uint64_t c_lo = (uint64_t)g * per, c_hi = (c_lo + per < C) ? c_lo + per : C;
-    const double mj = mean[j];
+    const double mj = mean[j], ej = mean[d + j];        // the centre in two parts (see the host): v = (x - mj) - ej
     for (uint32_t k = 0; k < L; ++k) acc[(size_t)k * 64 + lane] = 0.0;
     double sm = 0.0, sm2 = 0.0, sv = 0.0;
     for (uint64_t c0 = c_lo; c0 < c_hi; c0 += 64) {
         const uint64_t c = c0 + lane;
         const bool on = c < c_hi;
         double s1 = 0.0;
-        for (uint32_t t = 0; t < n; ++t) s1 += on ? draws[((size_t)t * d + j) * C + c] - mj : 0.0;
+        for (uint32_t t = 0; t < n; ++t) s1 += on ? (draws[((size_t)t * d + j) * C + c] - mj) - ej : 0.0;
         const double mc = s1 / (double)n;
         double ss = 0.0;
         for (uint32_t t0 = 0; t0 < n; t0 += T) {
             const uint32_t rows = (n - t0 < T + L) ? n - t0 : T + L;       // tile + halo
             const uint32_t own = (n - t0 < T) ? n - t0 : T;
-            for (uint32_t r = 0; r < rows; ++r) v[(size_t)r * 64 + lane] = on ? draws[((size_t)(t0 + r) * d + j) * C + c] - mj : 0.0;
+            for (uint32_t r = 0; r < rows; ++r) v[(size_t)r * 64 + lane] = on ? (draws[((size_t)(t0 + r) * d + j) * C + c] - mj) - ej : 0.0;
             for (uint32_t r = 0; r < own; ++r) { const double e = v[(size_t)r * 64 + lane] - mc; ss = __builtin_fma(e, e, ss); }
             for (uint32_t k = 0; k < L; ++k) {
                 double s_ = 0.0;
@@ -175,9 +176,11 @@ __global__ __launch_bounds__(64) void stats_acov_tiled_kernel(const double* __re
 // that mixes -- so computing all n lags (n^2 / 2 LDS-fed fmas per series, one wave per CU: the kernels above) is wasted work, and
 // measured slower than the sampler whose draws it summarises.  Here a lane streams its chain's series through a window of L
 // registers (a circular buffer with compile-time indices): one coalesced 512-byte load per time step and wave, L fmas per value,
-// no LDS; many waves per SIMD.  out[g][j][0..L): sum over the group's chains of sum_t v[t] v[t-k]; out2 as above, with the chain
-// variance from sum v^2 - n m_c^2 (v is centred by the pooled mean, so nothing cancels).  The host checks whether Geyer's sum
-// ended inside the L lags and asks for more (2 L, then every lag with the kernels above) if not.
+// no LDS; many waves per SIMD.  out[g][j][0..L): sum over the group's chains of sum_t v[t] v[t-k]; out2 as above.  The chain variance
+// is one-pass, but about the chain's OWN first draw: with w = x - x_first it is (sum w^2 - n mean(w)^2) / (n - 1), and what cancels is
+// relative to the chain's own spread.  (About the pooled mean -- the first version -- it cancels (m_c / sd_c)^2 ulp: nothing while the
+// chains agree, everything when they do not, the case R-hat exists to report.)  The host checks whether Geyer's sum
+// ended inside the L lags and asks for more (the lag-block passes of the kernel above) if not.
 template <int L>
 __global__ __launch_bounds__(64) void stats_window_kernel(const double* __restrict__ draws, const double* __restrict__ mean,
                                                           uint32_t n, uint32_t d, uint64_t C, uint32_t G,
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(64) void stats_window_kernel(const double* __restri
     const uint32_t j = blockIdx.x, g = blockIdx.y, lane = threadIdx.x;
     const uint64_t per = (C + G - 1) / G;
     const uint64_t c_lo = (uint64_t)g * per, c_hi = (c_lo + per < C) ? c_lo + per : C;
-    const double mj = mean[j];
+    const double mj = mean[j], ej = mean[d + j];        // the centre in two parts (see the host): v = (x - mj) - ej
     const size_t row = (size_t)d * C;                   // doubles between consecutive draws of one (dimension, chain)
     double acc[L];
 #pragma unroll
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(64) void stats_window_kernel(const double* __restri
         double win[L];
 #pragma unroll
         for (int u = 0; u < L; ++u) win[u] = 0.0;
-        double s1 = 0.0, q0 = 0.0;
+        double s1 = 0.0, q0 = 0.0, x_first = 0.0;       // sums of w = x - x_first and of w^2
         for (uint32_t t0 = 0; t0 < n; t0 += L) {
             double x[L];
 #pragma unroll
@@ -207,18 +210,22 @@ __global__ __launch_bounds__(64) void stats_window_kernel(const double* __restri
                 const uint32_t t = t0 + (uint32_t)u;
                 x[u] = p[(size_t)(t < n ? t : n - 1) * row];
             }
+            if (t0 == 0) x_first = x[0];
 #pragma unroll
             for (int u = 0; u < L; ++u) {
-                const double v = (on && t0 + (uint32_t)u < n) ? x[u] - mj : 0.0;
+                const bool in = on && t0 + (uint32_t)u < n;
+                const double v = in ? (x[u] - mj) - ej : 0.0;
+                const double w = in ? x[u] - x_first : 0.0;
                 win[u] = v;
-                s1 += v;
-                q0 = __builtin_fma(v, v, q0);
+                s1 += w;
+                q0 = __builtin_fma(w, w, q0);
 #pragma unroll
                 for (int k = 0; k < L; ++k) acc[k] = __builtin_fma(v, win[(u - k + L) % L], acc[k]);
             }
         }
-        const double mc = s1 / (double)n;
-        if (on) { sm += mc; sm2 = __builtin_fma(mc, mc, sm2); sv += (n > 1) ? (q0 - (double)n * mc * mc) / (double)(n - 1) : 0.0; }
+        const double mw = s1 / (double)n;
+        const double mc = ((x_first - mj) - ej) + mw;
+        if (on) { sm += mc; sm2 = __builtin_fma(mc, mc, sm2); sv += (n > 1) ? (q0 - (double)n * mw * mw) / (double)(n - 1) : 0.0; }
     }
 #pragma unroll
     for (int k = 0; k < L; ++k) {
@@ -240,7 +247,7 @@ __global__ __launch_bounds__(64) void stats_window_kernel(const double* __restri
 // NB (NB + 1) / 2 upper blocks of G in its accumulators (NB = n / 16 rounded up: 28 blocks = 224 registers at n = 100) over all its
 // tiles; per 4 chains that is 3.5 KB of draws for 28 MFMAs of 64 cycles: 2 bytes per SIMD cycle, the chip's HBM rate -- the pass
 // is bound by the read of the slab and by the matrix pipe at the same time.  The R-hat moments ride along (per-chain sums as the tile
-// is loaded).  At the end the four waves of a workgroup spill their blocks through LDS one after the other and thread k adds diagonal
+// is loaded, the squared deviations from the chain's mean out of the tile in LDS).  At the end the four waves of a workgroup spill their blocks through LDS one after the other and thread k adds diagonal
 // k in a fixed order; the host adds the G chain groups in order: the result does not depend on scheduling.
 //   out[g][j][0 .. 16 NB): sum over the group's chains of sum_t v[t] v[t + k];  out[g][j][16 NB .. 32 NB): the row sums sum_c v[t][c];
 //   out2[g][j][0..3) as in the kernels above.  v = x - mean[j], where `mean` may be a PROVISIONAL centre (see the host).
@@ -299,10 +306,11 @@ __global__ __launch_bounds__(512, 2) void stats_gram_kernel(const double* __rest
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = __builtin_amdgcn_readfirstlane(wave >> 1), par = __builtin_amdgcn_readfirstlane(wave & 1);
     double* const buf0 = lds;                           // [2][NR][RS]
-    double* const momb = lds + (size_t)2 * NR * RS;     // [2][8 waves][64][2]: per-chain partial sums of a tile's rows
+    double* const momb = lds + (size_t)2 * NR * RS;     // [2][8 waves][64][2]: per-chain partial sums of a tile's rows (first of each pair; the second held sum v^2 and is unused)
     const uint64_t per = (C + G - 1) / G;
     const uint64_t c_lo = (uint64_t)g * per, c_hi = (c_lo + per < C) ? c_lo + per : C;
     const double mj = mean[j];
+    const double inv_n = 1.0 / (double)n;
     const size_t row = (size_t)d * C;
     for (int i = threadIdx.x; i < 2 * NR * RS; i += 512) buf0[i] = 0.0;     // rows n .. NR - 1 and the padding columns stay zero
     double4_g acc[BPW];
@@ -342,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void stats_gram_kernel(const double* __rest
     auto deposit = [&](uint64_t tile, int bi, const auto& xr) __attribute__((always_inline)) {
         const bool on = c_lo + tile * TC + lane < c_hi;
         double* const V = buf0 + (size_t)bi * NR * RS;
-        double s1 = 0.0, q0 = 0.0;
+        double s1 = 0.0;
 #pragma unroll
         for (int u = 0; u < RPW; ++u) {
             const uint32_t t = (uint32_t)(wave + 8 * u);
@@ -350,24 +358,30 @@ __global__ __launch_bounds__(512, 2) void stats_gram_kernel(const double* __rest
                 const double v = on ? xr[u] - mj : 0.0;
                 V[(size_t)t * RS + lane] = v;
                 s1 += v;
-                q0 = __builtin_fma(v, v, q0);
                 rs[u] += v;
             }
         }
-        double* m = momb + (((size_t)bi * 8 + wave) * 64 + lane) * 2;
-        m[0] = s1; m[1] = q0;
+        momb[(((size_t)bi * 8 + wave) * 64 + lane) * 2] = s1;
     };
     // the MFMAs and the R-hat moments of the tile in buffer bi
     auto compute = [&](uint64_t tile, int bi) __attribute__((always_inline)) {
         const double* const V = buf0 + (size_t)bi * NR * RS;
-        if ((uint64_t)wave == (tile & 7)) {             // one wave adds the 8 partial per-chain sums, in order
-            double s1 = 0.0, q0 = 0.0;
-            for (int wv = 0; wv < 8; ++wv) { const double* m = momb + (((size_t)bi * 8 + wv) * 64 + lane) * 2; s1 += m[0]; q0 += m[1]; }
-            if (c_lo + tile * TC + lane < c_hi) {
-                const double mc = s1 / (double)n;
-                sm += mc; sm2 = __builtin_fma(mc, mc, sm2);
-                sv += (n > 1) ? (q0 - (double)n * mc * mc) / (double)(n - 1) : 0.0;
-            }
+        // The within-chain variance is two-pass, over the tile in LDS: every wave adds the 8 partial per-chain sums (in order: the same bits
+        // in every wave), and takes the squared deviations of ITS rows from the chain's mean; sv collects them for all its chains and tiles, the
+        // division by n - 1 comes at the end.  (sum v^2 - n m_c^2 about the kernel's centre -- the first version -- cancels (m_c / sd_c)^2 ulp:
+        // nothing while the chains agree, everything when they do not, the case R-hat exists to report.)  The centre of the deviations needs
+        // the mean to first order only -- sum (v - a)^2 = sum (v - m_c)^2 + n (a - m_c)^2 --, so it is a product with 1 / n, not a division.
+        double s1 = 0.0;
+        for (int wv = 0; wv < 8; ++wv) s1 += momb[(((size_t)bi * 8 + wv) * 64 + lane) * 2];
+        const double ctr = s1 * inv_n;
+#pragma unroll
+        for (int u = 0; u < RPW; ++u) {                 // (lanes past the group's last chain hold zeros: s1 = 0, no deviation)
+            const uint32_t t = (uint32_t)(wave + 8 * u);
+            if (t < n) { const double e = V[(size_t)t * RS + lane] - ctr; sv = __builtin_fma(e, e, sv); }
+        }
+        if ((uint64_t)wave == (tile & 7) && c_lo + tile * TC + lane < c_hi) {      // one wave per tile: the chain means themselves
+            const double mc = s1 / (double)n;
+            sm += mc; sm2 = __builtin_fma(mc, mc, sm2);
         }
         const double* fr = V + (size_t)(lane & 15) * RS + (lane >> 4) + 4 * par;
 #pragma unroll 1
@@ -441,7 +455,7 @@ __global__ __launch_bounds__(512, 2) void stats_gram_kernel(const double* __rest
         double a0 = 0.0, a1 = 0.0, a2 = 0.0;
         for (int wv = 0; wv < 8; ++wv) { a0 += red[wv * 3 + 0]; a1 += red[wv * 3 + 1]; a2 += red[wv * 3 + 2]; }
         double* o = out2 + ((size_t)g * d + j) * 3;
-        o[0] = a0; o[1] = a1; o[2] = a2;
+        o[0] = a0; o[1] = a1; o[2] = (n > 1) ? a2 / (double)(n - 1) : 0.0;
     }
 }
 

@@ -16,7 +16,15 @@
 using mi::host::fail;
 using mi::host::DevBuf;
 
+// what mi_mcmc_test_draw_stats_last reports (mi_mcmc_probes.h): host bookkeeping of this thread's last mi_mcmc_draw_stats call, nothing reads it back
+static thread_local uint64_t draw_stats_last[8];
+
 extern "C" {
+
+void mi_mcmc_test_draw_stats_last(uint64_t* out8)
+{
+    if (out8) std::memcpy(out8, draw_stats_last, sizeof draw_stats_last);
+}
 
 int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
                        double* mean, double* acov, double* rhat, double* ess, void* stream)
@@ -41,11 +49,17 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
                             : (uint32_t)std::min<uint64_t>(64, (C + 63) / 64);
     const bool tiled = n > (size_t)mi::STATS_MAX_N;                          // long series: lags below STATS_TILED_LAGS, streamed kernel
     const size_t nlag_max = tiled ? (size_t)mi::STATS_TILED_LAGS : n;
+    {   // route, NB, G, 64-chain tiles of the largest (first) chain group, window launches, lag passes, lag passes over a subset, smallest subset
+        const uint64_t per = (C + G - 1) / G;
+        uint64_t* const L = draw_stats_last;
+        L[0] = gram ? 0 : (tiled ? 2 : 1); L[1] = gram ? (n + 15) / 16 : 0; L[2] = G; L[3] = (std::min<uint64_t>(per, C) + 63) / 64;
+        L[4] = L[5] = L[6] = L[7] = 0;
+    }
     const size_t pass_lags = (size_t)mi::STATS_PASS_BLOCKS * mi::STATS_LB;
-    // one device buffer for everything: [G d] sums, [d] means, [d] dimension list, [G d 3] moments, [G d max(pass, tiled) lags]
+    // one device buffer for everything: [G d] sums, [2 d] the centre in two parts, [d] dimension list, [G d 3] moments, [G d max(pass, tiled) lags]
     const size_t part_lags = tiled ? nlag_max : std::max<size_t>(std::max<size_t>(pass_lags, 16), (n <= (size_t)mi::STATS_GRAM_MAX_N) ? ((n + 15) / 16) * 32 : 0);
     DevBuf buf;
-    const size_t o_sum = 0, o_mean = o_sum + (size_t)G * d, o_dims = o_mean + d, o_mom = o_dims + d, o_part = o_mom + (size_t)G * d * 3;
+    const size_t o_sum = 0, o_mean = o_sum + (size_t)G * d, o_dims = o_mean + 2 * d, o_mom = o_dims + d, o_part = o_mom + (size_t)G * d * 3;
     HIP_TRY(buf.alloc((o_part + (size_t)G * d * part_lags) * 8));
     double* const B = buf.as<double>();
     // ONE pass over the slab when the Gram kernel serves the request (n <= 128 and more than the mean is asked for): the series are
@@ -53,22 +67,38 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
     // draw alone can sit far from the pooled mean when n_burnin is 0 and the chains share a start far from the mode: with e / sigma large
     // the recentring below would cancel (e / sigma)^2 ulp of the autocovariances) -- and the kernel's row
     // sums R_t = sum_c (x_t - a) move the centre to the pooled mean afterwards (exactly, in the algebra):  sum_c sum_t (v_t - e)(v_{t+k} - e) = S_k - e (sum_{t < n-k} R_t + sum_{t >= k} R_t) + C (n - k) e^2,
-    // e = pooled mean - a.  (Otherwise: the pooled mean first, one read of the slab, then the lag kernels.)
-    const bool one_pass = gram && (acov || rhat || ess);
-    const uint32_t t_step = one_pass ? (uint32_t)std::max<size_t>(1, (n - 1) / 2) : 1u;      // rows 0, (n-1)/2, 2 ((n-1)/2) [= n-1 or n-2] / every row
+    // e = pooled mean - a.
+    // The other routes (n > 128) read the slab once for the pooled mean and then run the lag kernels, which centre as they load.  Their centre has
+    // TWO parts, v = (x - a_j) - e_j: the same provisional a_j, and e_j = the mean of x - a_j over the whole slab.  One double cannot hold the
+    // pooled mean to better than |mean| 2^-53 -- 1e-8 standard deviations at mean = 1e8, sd = 1 --, and series centred that far off carry the
+    // error, times their partial sums, into every autocovariance; x - a_j is exact where it matters (x near a_j) and e_j is small.
+    const bool stats = acov || rhat || ess;
+    const bool one_pass = gram && stats;
+    const uint32_t t_step = stats ? (uint32_t)std::max<size_t>(1, (n - 1) / 2) : 1u;         // rows 0, (n-1)/2, 2 ((n-1)/2) [= n-1 or n-2] / every row
     const uint32_t n_sum = (uint32_t)((n + t_step - 1) / t_step);
-    hipLaunchKernelGGL(mi::stats_sum_kernel, dim3((unsigned)d, G), dim3(64), 0, st, x, (uint32_t)n, t_step, (uint32_t)d, (uint64_t)C, G, B + o_sum);
-    std::vector<double> part((size_t)G * d), mean_h(d);
-    HIP_TRY(hipMemcpyAsync(part.data(), B + o_sum, part.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t j = 0; j < d; ++j) {
-        double s = 0.0;
-        for (uint32_t g = 0; g < G; ++g) s += part[(size_t)g * d + j];
-        mean_h[j] = s / ((double)n_sum * (double)C);
-    }
-    if (!one_pass && mean) std::memcpy(mean, mean_h.data(), d * 8);
-    if (!acov && !rhat && !ess) return MI_OK;
+    std::vector<double> part((size_t)G * d), mean_h(d), e_h(d, 0.0);
+    // mean over the rows 0, t_step, ... of x - centre: the G partials added in order
+    auto row_mean = [&](const double* centre, uint32_t step, uint32_t rows, std::vector<double>& dst) -> int {
+        hipLaunchKernelGGL(mi::stats_sum_kernel, dim3((unsigned)d, G), dim3(64), 0, st, x, centre, (uint32_t)n, step, (uint32_t)d, (uint64_t)C, G, B + o_sum);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(part.data(), B + o_sum, part.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t j = 0; j < d; ++j) {
+            double s = 0.0;
+            for (uint32_t g = 0; g < G; ++g) s += part[(size_t)g * d + j];
+            dst[j] = s / ((double)rows * (double)C);
+        }
+        return MI_OK;
+    };
+    int rc;
+    if ((rc = row_mean(nullptr, t_step, n_sum, mean_h))) return rc;
+    if (!stats) { if (mean) std::memcpy(mean, mean_h.data(), d * 8); return MI_OK; }
     HIP_TRY(hipMemcpyAsync(B + o_mean, mean_h.data(), d * 8, hipMemcpyHostToDevice, st));
+    if (!one_pass) {
+        if ((rc = row_mean(B + o_mean, 1u, (uint32_t)n, e_h))) return rc;
+        HIP_TRY(hipMemcpyAsync(B + o_mean + d, e_h.data(), d * 8, hipMemcpyHostToDevice, st));
+        if (mean) for (size_t j = 0; j < d; ++j) mean[j] = mean_h[j] + e_h[j];
+    }
 
     std::vector<double> ac((size_t)n * d, std::nan(""));     // ac[k * d + j]: pooled over chains, unbiased per lag
     std::vector<double> mp;                                   // [G][d][3] moments for R-hat
@@ -116,7 +146,6 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
         active.swap(next);
     };
     std::vector<double> ap;
-    int rc;
     if (tiled) {
         const size_t lds = (size_t)(mi::STATS_TILE_T + 2 * mi::STATS_TILED_LAGS) * 64 * sizeof(double);
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mi::stats_acov_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -186,6 +215,7 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
             hipLaunchKernelGGL(mi::stats_window_kernel<16>, dim3((unsigned)d, G), dim3(64), 0, st, x, B + o_mean, (uint32_t)n, (uint32_t)d,
                                (uint64_t)C, G, B + o_part, B + o_mom);
             HIP_TRY(hipGetLastError());
+            ++draw_stats_last[4];
             if ((rc = fetch(ap, B + o_part, (size_t)G * d * 16))) return rc;
             if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc;
             HIP_TRY(hipStreamSynchronize(st));
@@ -210,6 +240,11 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
                                (uint64_t)C, G, all_dims ? nullptr : reinterpret_cast<const uint32_t*>(B + o_dims), b_lo, b_hi, want_mom,
                                B + o_part, B + o_mom);
             HIP_TRY(hipGetLastError());
+            ++draw_stats_last[5];
+            if (!all_dims) {
+                draw_stats_last[7] = draw_stats_last[6] ? std::min<uint64_t>(draw_stats_last[7], active.size()) : active.size();
+                ++draw_stats_last[6];
+            }
             if ((rc = fetch(ap, B + o_part, (size_t)G * active.size() * npl))) return rc;
             if (want_mom) { if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc; }
             HIP_TRY(hipStreamSynchronize(st));
