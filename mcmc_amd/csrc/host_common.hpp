@@ -1,6 +1,7 @@
 // host_common.hpp -- shared by the host-side translation units of the C ABI (mi_mcmc.hip: the samplers; callback_host.hip: the
-// host-callback routes; stats_collate.hip: reducers, converters, multi-GPU helpers; probes.hip: diagnostics): the error channel
-// (status code + thread-local message behind mi_mcmc_last_error) and the RAII device buffer.
+// host-callback routes; draws_api.hip: the reducers over a draws slab; stats_collate.hip: multi-GPU collation and the host layout
+// converter; probes.hip: diagnostics): the error channel (status code + thread-local message behind mi_mcmc_last_error), the
+// device probe and the RAII device buffer.  The workspace cache the samplers and the reducers share is workspace.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,6 +27,16 @@ inline int fail(int code, const char* fmt, ...)
     va_end(ap);
     last_error() = buf;
     return code;
+}
+
+// The device probe of an entry point, placed after its argument checks (they need no device): MI_OK with HIP's sticky status cleared -- a stale
+// non-fatal status of the caller's own HIP use (e.g. hipErrorNotReady of an event query) is not ours --, or MI_ERR_NO_DEVICE
+inline int need_device()
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
+    (void)hipGetLastError();
+    return MI_OK;
 }
 
 // RAII device buffer

@@ -21,6 +21,7 @@
 
 #include "../../include/mi_mcmc.h"
 #include "host_common.hpp"
+#include "workspace.hpp"
 #include "host_linalg.hpp"
 #include "det_math.hpp"
 #include "hmc_dense.hpp"
@@ -37,10 +38,6 @@
 #include "logistic_launch.hpp"
 #include "launchers.hpp"
 #include "gemm_samplers.hpp"
-#include "draws_cov.hpp"
-#include "draws_select.hpp"
-#include "draws_rank.hpp"
-#include "draws_logk.hpp"
 #include "small_samplers.hpp"
 #include "literal_host.hpp"
 #include "settings_host.hpp"
@@ -60,6 +57,63 @@ std::string& last_error() { thread_local std::string e; return e; }
 std::string& last_kernel() { thread_local std::string k; return k; }
 int device_inverse(const double* A, size_t d, double* Ainv);                 // linalg_device.hip
 int device_cholesky_lower(const double* A, size_t d, double* L);
+
+// the per-(device, stream) workspace cache (workspace.hpp says what it is): its one definition
+static std::mutex g_ws_mu;
+static std::map<std::pair<int, hipStream_t>, std::unique_ptr<WsEntry>> g_ws;
+
+int ws_get(hipStream_t st, size_t bytes, WsLease& lease)
+{
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    WsEntry* w = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        std::unique_ptr<WsEntry>& slot = g_ws[std::make_pair(dev, st)];
+        if (!slot) slot.reset(new WsEntry);
+        w = slot.get();
+    }
+    lease.lk = std::unique_lock<std::mutex>(w->mu);
+    if (w->cap < bytes) {
+        if (w->p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(w->p)); w->p = nullptr; w->cap = 0; }
+        HIP_TRY(hipMalloc(&w->p, bytes));
+        w->cap = bytes;
+    }
+    lease.p = w->p;
+    return MI_OK;
+}
+
+size_t ws_cached_bytes(hipStream_t st)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    auto it = g_ws.find(std::make_pair(dev, st));
+    return (it == g_ws.end() || !it->second) ? 0 : it->second->cap;
+}
+
+int ws_release(hipStream_t st, bool all_streams, uint64_t* freed)
+{
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::vector<WsEntry*> victims;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mu);
+        for (auto& kv : g_ws)
+            if (kv.first.first == dev && (all_streams || kv.first.second == st)) victims.push_back(kv.second.get());
+    }
+    uint64_t total = 0;
+    for (WsEntry* w : victims) {
+        std::lock_guard<std::mutex> lk(w->mu);
+        if (!w->p) continue;
+        HIP_TRY(all_streams ? hipDeviceSynchronize() : hipStreamSynchronize(st));
+        HIP_TRY(hipFree(w->p));
+        total += w->cap;
+        w->p = nullptr; w->cap = 0;
+    }
+    if (freed) *freed = total;
+    return MI_OK;
+}
 }  // namespace host
 namespace {
 // INV / CHOL_LOWER of a dense precond_mat with d >= 64 run on the device (host_linalg.hpp: same operations per element, same bits)
@@ -119,19 +173,6 @@ std::atomic<uint64_t> g_gemm_ws_bytes{0};
 enum : int { GEMM_PLAIN = 0, GEMM_DENSE_M = 1, GEMM_BOUNDED = 2 };
 size_t gemm_need_bytes(uint64_t d, uint64_t n, uint64_t C, int variant, bool replay);
 }
-// test hooks, declared in mi_mcmc_probes.h: the workspace budget of the rank transform's groups of dimensions (draws_rank.hpp) and the host arithmetic of its
-// group rule, which needs no device
-namespace { std::atomic<uint64_t> g_rank_ws_bytes{0}; }
-extern "C" void mi_mcmc_test_set_rank_ws_bytes(uint64_t bytes) { g_rank_ws_bytes.store(bytes, std::memory_order_relaxed); }
-extern "C" void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes) { mi::drank::rank_counts(sorts, passes); }
-extern "C" uint64_t mi_mcmc_test_rank_dim_bytes(uint64_t n_keep, uint64_t n_chains, uint32_t flags, int stats)
-{
-    return mi::drank::rank_dim_bytes(n_keep, n_chains, flags, stats != 0);
-}
-extern "C" uint64_t mi_mcmc_test_rank_dims_per_group(uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t flags, int stats)
-{
-    return mi::drank::rank_plan(n_keep, d, n_chains, flags, stats != 0, g_rank_ws_bytes.load(std::memory_order_relaxed)).dims_per_group;
-}
 extern "C" void mi_mcmc_test_set_gemm_graph(int mode) { g_gemm_graph_mode.store(mode, std::memory_order_relaxed); }
 extern "C" void mi_mcmc_test_set_gemm_ws_bytes(uint64_t bytes) { g_gemm_ws_bytes.store(bytes, std::memory_order_relaxed); }
 extern "C" uint64_t mi_mcmc_test_gemm_need_bytes(uint32_t d, uint32_t n_rows, uint64_t n_chains, int variant, int replay)
@@ -141,83 +182,11 @@ extern "C" uint64_t mi_mcmc_test_gemm_need_bytes(uint32_t d, uint32_t n_rows, ui
 
 namespace {
 
-using mi::host::fail;
-using mi::host::DevBuf;
-
-// Per-(device, stream) workspace cache.  Kernels of one stream are ordered, so one buffer serves consecutive calls; it is
-// reallocated (after a stream sync) only when a call needs more, and released by mi_mcmc_release_workspace().  A call holds
-// the entry's mutex from ws_get() until its kernels are enqueued (WsLease), so a second host thread on the same stream can
-// neither free nor regrow the buffer between "pointer handed out" and "kernel enqueued"; after that the stream orders them.
-// (hipMallocAsync / hipFreeAsync pool memory was observed to hand the pack -> sample kernel pair of the logistic path
-// buffers whose first blocks read back as zeros; a plain cached hipMalloc does not.)
-struct WsEntry { void* p = nullptr; size_t cap = 0; std::mutex mu; };
-std::mutex g_ws_mu;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<WsEntry>> g_ws;
-
-struct WsLease {
-    std::unique_lock<std::mutex> lk;
-    void* p = nullptr;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-int ws_get(hipStream_t st, size_t bytes, WsLease& lease)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    WsEntry* w = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        std::unique_ptr<WsEntry>& slot = g_ws[std::make_pair(dev, st)];
-        if (!slot) slot.reset(new WsEntry);
-        w = slot.get();
-    }
-    lease.lk = std::unique_lock<std::mutex>(w->mu);
-    if (w->cap < bytes) {
-        if (w->p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(w->p)); w->p = nullptr; w->cap = 0; }
-        HIP_TRY(hipMalloc(&w->p, bytes));
-        w->cap = bytes;
-    }
-    lease.p = w->p;
-    return MI_OK;
-}
-
-// bytes the cache holds for (current device, st) right now
-size_t ws_cached_bytes(hipStream_t st)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    auto it = g_ws.find(std::make_pair(dev, st));
-    return (it == g_ws.end() || !it->second) ? 0 : it->second->cap;
-}
+using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get, ws_cached_bytes, ws_release (workspace.hpp)
 
 #ifndef MI_NUTS_MOMENTA_MAX_BYTES
 #define MI_NUTS_MOMENTA_MAX_BYTES ((size_t)24 << 30)     // the table of momenta of a nuts run (nuts_memo.hpp): 13.6 GB on BASELINE configs[3]
 #endif
-
-// frees the cached workspace of (current device, st); all_streams: every entry of the current device
-int ws_release(hipStream_t st, bool all_streams, uint64_t* freed)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::vector<WsEntry*> victims;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        for (auto& kv : g_ws)
-            if (kv.first.first == dev && (all_streams || kv.first.second == st)) victims.push_back(kv.second.get());
-    }
-    uint64_t total = 0;
-    for (WsEntry* w : victims) {
-        std::lock_guard<std::mutex> lk(w->mu);
-        if (!w->p) continue;
-        HIP_TRY(all_streams ? hipDeviceSynchronize() : hipStreamSynchronize(st));
-        HIP_TRY(hipFree(w->p));
-        total += w->cap;
-        w->p = nullptr; w->cap = 0;
-    }
-    if (freed) *freed = total;
-    return MI_OK;
-}
 
 // ---- literal replay of the non-finite regime (literal.hpp).  The plain throughput kernels flag the chains whose energies /
 // proposal densities went non-finite (nf_flag[c] = 1, nf_flag[C] = 1) and leave their outputs alone; the literal kernel, enqueued
@@ -377,11 +346,7 @@ int check_common(const mi_target* t, const mi_settings* s, const mi_chains* c, b
     if (c->mass_diag && !mass_allowed) return fail(MI_ERR_UNSUPPORTED, "chains.mass_diag (per-chain diagonal masses) is implemented for mi_mcmc_hmc_run only");
     if (c->mass_diag && s->precond_mat) return fail(MI_ERR_BAD_ARG, "chains.mass_diag and settings.precond_mat are two mass matrices: one of them must be NULL");
     if (c->draw0 + s->n_burnin_draws + s->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "draw0 + draws exceeds the 32-bit draw counter");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();      // a stale non-fatal status of the caller's own HIP use (e.g. hipErrorNotReady of an event query) is not ours
-    return MI_OK;
+    return need_device();
 }
 
 // Dense d x d precision on the device for the Gaussian kinds (ISO / DIAG expand to a diagonal
@@ -1291,9 +1256,7 @@ int literal_run_callback(const char* who, int algo, const double* initial_vals, 
     const uint64_t n_keep = settings->n_keep_draws, n_total = settings->n_burnin_draws + n_keep;
     if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
     if (n_keep > 0 && !draws_out) return fail(MI_ERR_BAD_ARG, "%s (callback): draws_out is required", who);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
     const size_t dd = (size_t)d * d;
     PinnedBuf ctl, val, xb, outb;
     HIP_TRY(ctl.alloc(mi::lit::LIT_MB_WORDS * sizeof(uint32_t))); HIP_TRY(val.alloc(8)); HIP_TRY(xb.alloc(d * 8));
@@ -1404,9 +1367,7 @@ int de_run(const mi_target* target, const mi_settings* settings, const mi_de_set
     if (target->kind == MI_TARGET_NORMAL_MODEL)
         return fail(MI_ERR_UNSUPPORTED, "de: MI_TARGET_NORMAL_MODEL has no literal (one workgroup per population) evaluation, which the de kernels are built on");
     if (target->kind < MI_TARGET_GAUSS_ISO || target->kind > MI_TARGET_LOGISTIC) return fail(MI_ERR_UNSUPPORTED, "de: target kind %d not implemented", target->kind);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
 
     const uint64_t n_pop = de->n_pop, n_keep = settings->n_keep_draws;
     const size_t pop_doubles = (size_t)n_pop * d * NP;
@@ -1468,9 +1429,7 @@ int de_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb tar
     if (rc) return rc;
     const uint64_t n_pop = de->n_pop, n_keep = settings->n_keep_draws;
     if (n_keep > 0 && !draws_out) return fail(MI_ERR_BAD_ARG, "de (callback): draws_out is required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
     PinnedBuf ctl, val, xb, outb;
     HIP_TRY(ctl.alloc(mi::lit::LIT_MB_WORDS * sizeof(uint32_t))); HIP_TRY(val.alloc(8)); HIP_TRY(xb.alloc(d * 8)); HIP_TRY(outb.alloc(d * 8));
     std::memset(ctl.p, 0, mi::lit::LIT_MB_WORDS * sizeof(uint32_t));
@@ -1598,9 +1557,7 @@ int aees_run(const mi_target* target, const mi_settings* settings, const mi_aees
     if (target->kind == MI_TARGET_NORMAL_MODEL)
         return fail(MI_ERR_UNSUPPORTED, "aees: MI_TARGET_NORMAL_MODEL has no literal (one workgroup per run) evaluation, which the aees kernel is built on");
     if (target->kind < MI_TARGET_GAUSS_ISO || target->kind > MI_TARGET_GAUSS_MIXTURE) return fail(MI_ERR_UNSUPPORTED, "aees: target kind %d not implemented", target->kind);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
 
     mi::AeesParams prm{};
     AeesTables tb;
@@ -1644,9 +1601,7 @@ int aees_run_callback(const double* initial_vals, uint64_t d, mi_log_kernel_cb t
     if (rc) return rc;
     const uint64_t n_keep = settings->n_keep_draws, K = aees->temper_len + 1;
     if (n_keep > 0 && !draws_out) return fail(MI_ERR_BAD_ARG, "aees (callback): draws_out is required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
     PinnedBuf ctl, val, xb, outb;
     HIP_TRY(ctl.alloc(mi::lit::LIT_MB_WORDS * sizeof(uint32_t))); HIP_TRY(val.alloc(8)); HIP_TRY(xb.alloc(d * 8)); HIP_TRY(outb.alloc(d * 8));
     std::memset(ctl.p, 0, mi::lit::LIT_MB_WORDS * sizeof(uint32_t));
@@ -1734,9 +1689,7 @@ int mi_mcmc_run_user_target(int algo, uint64_t d, mi_small_launch_fn launch, con
     if (settings->struct_size != sizeof(mi_settings) || chains->struct_size != sizeof(mi_chains))
         return fail(MI_ERR_BAD_ARG, "struct_size mismatch (header / library version skew)");
     if (chains->n_chains == 0 || !chains->theta) return fail(MI_ERR_BAD_ARG, "chains.theta and n_chains are required");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
     static const char* const names[5] = {"hmc", "mala", "nuts", "rwmh", "rmhmc"};
     return run_small(names[algo], algo, d, settings, chains, static_cast<hipStream_t>(stream), [&](const mi::SmallParams& p, hipStream_t s_) {
         return launch(algo, &p, target_pod, s_);
@@ -1772,9 +1725,7 @@ int mi_mcmc_run_tile_target(int algo, uint64_t d, int nt, int wpb, uint64_t lds_
     if (chains->n_chains == 0 || !chains->theta) return fail(MI_ERR_BAD_ARG, "chains.theta and n_chains are required");
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
     if (chains->draw0 + n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "draw0 + draws exceeds the 32-bit draw counter");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
+    if (int rc_dev = need_device()) return rc_dev;
     int dev = 0, lds_max = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
@@ -2232,404 +2183,6 @@ int mi_mcmc_hmc_run_mass_adapted(const mi_target* target, const mi_settings* set
                                 (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps, stream, estimate);
     if (rc) return rc;
     if (mass_diag_out) std::memcpy(mass_diag_out, mass.data(), d * 8);
-    return MI_OK;
-}
-
-// Pooled mean and covariance of the K = n_keep * C columns of a slab [n_keep][d][C] (draws_cov.hip; the arithmetic: include/mi_mcmc.h)
-int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* mean, double* cov, void* stream)
-{
-    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "draws_covariance: null slab");
-    if (d == 0) return fail(MI_ERR_BAD_ARG, "draws_covariance: d must be positive");
-    if (!mean && !cov) return fail(MI_ERR_BAD_ARG, "draws_covariance: mean and cov are both NULL, nothing is asked for");
-    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "draws_covariance: n_keep / n_chains do not fit 32 bits");
-    if (n_keep * n_chains < 2) return fail(MI_ERR_BAD_ARG, "draws_covariance: K = n_keep * n_chains = %llu, at least 2 samples are needed", (unsigned long long)(n_keep * n_chains));
-    if (d > mi::dcov::COV_MAX_D) return fail(MI_ERR_BAD_ARG, "draws_covariance: d = %llu is beyond %llu", (unsigned long long)d, (unsigned long long)mi::dcov::COV_MAX_D);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    DevBuf staged;
-    const double* x = draws_kdc;
-    if (mem == MI_MEM_HOST) {
-        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
-        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
-        x = staged.as<double>();
-    }
-    const mi::dcov::CovPlan plan = mi::dcov::cov_plan(n_keep, d, n_chains, cov != nullptr);
-    WsLease ws;
-    int rc = ws_get(st, plan.bytes, ws);
-    if (rc) return rc;
-    HIP_TRY((hipError_t)mi::dcov::cov_run(x, d, n_chains, plan, ws.p, cov != nullptr, st));
-    if (mean) HIP_TRY(hipMemcpyAsync(mean, ws.as<double>() + plan.o_mean, d * 8, hipMemcpyDeviceToHost, st));
-    if (cov) HIP_TRY(hipMemcpyAsync(cov, ws.as<double>() + plan.o_cov, d * d * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                   // blocking: the outputs are the caller's host arrays, the staged slab and the workspace are ours
-    return MI_OK;
-}
-
-namespace {
-// The checks that mi_mcmc_draws_order_stats and mi_mcmc_draws_quantiles share: they need no device
-int order_stats_check(const char* who, const double* draws_kdc, uint64_t n_keep, uint64_t d, uint64_t n_chains, const double* out)
-{
-    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
-    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
-    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
-    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (n_keep * n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = 0, at least 1 sample is needed", who);
-    if (d > mi::dsel::SEL_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::dsel::SEL_MAX_D);
-    return MI_OK;
-}
-
-// out [n_ranks][d] on the host <- the order statistics of a checked call (draws_select.hip); blocking
-int order_stats_run(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const uint64_t* ranks, uint32_t n_ranks, double* out,
-                    void* stream)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    DevBuf staged;
-    const double* x = draws_kdc;
-    if (mem == MI_MEM_HOST) {
-        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
-        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
-        x = staged.as<double>();
-    }
-    mi::dsel::SelRanks r{};
-    for (uint32_t a = 0; a < n_ranks; ++a) r.r[a] = ranks[a];
-    const mi::dsel::SelPlan plan = mi::dsel::sel_plan(n_keep, d, n_chains, n_ranks);
-    WsLease ws;
-    int rc = ws_get(st, plan.bytes, ws);
-    if (rc) return rc;
-    HIP_TRY((hipError_t)mi::dsel::sel_run(x, n_keep, d, n_chains, r, n_ranks, plan, ws.p, st));
-    HIP_TRY(hipMemcpyAsync(out, ws.as<char>() + plan.o_out, (size_t)n_ranks * d * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                   // blocking: out is the caller's host array, the staged slab and the workspace are ours
-    return MI_OK;
-}
-}  // namespace
-
-// The ranks[a]-th smallest key of every dimension of a slab [n_keep][d][C], as a value (the key, the order: include/mi_mcmc.h)
-int mi_mcmc_draws_order_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const uint64_t* ranks, uint32_t n_ranks,
-                              double* out, void* stream)
-{
-    const char* who = "draws_order_stats";
-    int rc = order_stats_check(who, draws_kdc, n_keep, d, n_chains, out);
-    if (rc) return rc;
-    if (!ranks) return fail(MI_ERR_BAD_ARG, "%s: ranks is NULL", who);
-    if (n_ranks == 0 || n_ranks > MI_ORDER_STATS_MAX_RANKS) return fail(MI_ERR_BAD_ARG, "%s: n_ranks = %u, must be 1 .. %d", who, n_ranks, MI_ORDER_STATS_MAX_RANKS);
-    const uint64_t K = n_keep * n_chains;
-    for (uint32_t a = 0; a < n_ranks; ++a)
-        if (ranks[a] >= K) return fail(MI_ERR_BAD_ARG, "%s: ranks[%u] = %llu is not below K = %llu", who, a, (unsigned long long)ranks[a], (unsigned long long)K);
-    return order_stats_run(draws_kdc, mem, n_keep, d, n_chains, ranks, n_ranks, out, stream);
-}
-
-// Type-7 quantiles from two order statistics per probability; the arithmetic below IS include/mi_mcmc.h's statement (this file is compiled with
-// -ffp-contract=off: nothing is fused)
-int mi_mcmc_draws_quantiles(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, const double* probs, uint32_t n_probs,
-                            double* out, void* stream)
-{
-    const char* who = "draws_quantiles";
-    int rc = order_stats_check(who, draws_kdc, n_keep, d, n_chains, out);
-    if (rc) return rc;
-    if (!probs) return fail(MI_ERR_BAD_ARG, "%s: probs is NULL", who);
-    if (n_probs == 0 || n_probs > MI_ORDER_STATS_MAX_RANKS / 2) return fail(MI_ERR_BAD_ARG, "%s: n_probs = %u, must be 1 .. %d", who, n_probs, MI_ORDER_STATS_MAX_RANKS / 2);
-    for (uint32_t a = 0; a < n_probs; ++a)
-        if (!(probs[a] >= 0.0 && probs[a] <= 1.0)) return fail(MI_ERR_BAD_ARG, "%s: probs[%u] = %g is not in [0, 1]", who, a, probs[a]);
-    const uint64_t K = n_keep * n_chains;
-    uint64_t ranks[MI_ORDER_STATS_MAX_RANKS];
-    double g[MI_ORDER_STATS_MAX_RANKS / 2];
-    for (uint32_t a = 0; a < n_probs; ++a) {
-        const double h = probs[a] * (double)(K - 1);
-        const double fl = std::floor(h);
-        const uint64_t lo = fl >= (double)(K - 1) ? K - 1 : (uint64_t)fl;
-        g[a] = h - (double)lo;
-        ranks[2 * a] = lo;
-        ranks[2 * a + 1] = lo + 1 < K ? lo + 1 : K - 1;
-    }
-    std::vector<double> os((size_t)2 * n_probs * d);
-    rc = order_stats_run(draws_kdc, mem, n_keep, d, n_chains, ranks, 2 * n_probs, os.data(), stream);
-    if (rc) return rc;
-    for (uint32_t a = 0; a < n_probs; ++a) {
-        const double* x_lo = os.data() + (size_t)(2 * a) * d;
-        const double* x_hi = x_lo + d;
-        for (uint64_t i = 0; i < d; ++i) {
-            if (g[a] == 0.0) out[(size_t)a * d + i] = x_lo[i];
-            else {
-                const double diff = x_hi[i] - x_lo[i];
-                const double prod = g[a] * diff;
-                out[(size_t)a * d + i] = x_lo[i] + prod;
-            }
-        }
-    }
-    return MI_OK;
-}
-
-namespace {
-// The checks that mi_mcmc_draws_rank_transform and mi_mcmc_draw_stats_ranked share: they need no device
-int rank_check(const char* who, const double* draws_kdc, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t flags)
-{
-    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
-    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
-    if (d > mi::drank::RANK_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::drank::RANK_MAX_D);
-    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (flags & ~(uint32_t)(MI_RANK_SPLIT | MI_RANK_FOLD)) return fail(MI_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", who, flags);
-    if ((flags & MI_RANK_SPLIT) && n_keep < 2) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, MI_RANK_SPLIT needs at least 2 draws", who, (unsigned long long)n_keep);
-    const uint64_t rows = (flags & MI_RANK_SPLIT) ? 2 * (n_keep / 2) : n_keep;
-    // rows, n_chains < 2^32: the product does not wrap
-    if (rows * n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: S = 0 retained samples, at least 1 is needed", who);
-    if (rows * n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: S = %llu retained samples per dimension, must be below 2^32", who, (unsigned long long)(rows * n_chains));
-    return MI_OK;
-}
-
-// (lo, hi, g) of the type-7 rule for one probability over S samples: mi_mcmc_draws_quantiles' arithmetic
-void type7_ranks(uint64_t S, double prob, uint64_t* lo, uint64_t* hi, double* g)
-{
-    const double h = prob * (double)(S - 1);
-    const double fl = std::floor(h);
-    *lo = fl >= (double)(S - 1) ? S - 1 : (uint64_t)fl;
-    *g = h - (double)*lo;
-    *hi = *lo + 1 < S ? *lo + 1 : S - 1;
-}
-double type7_value(double x_lo, double x_hi, double g)
-{
-    if (g == 0.0) return x_lo;
-    const double diff = x_hi - x_lo;
-    const double prod = g * diff;
-    return x_lo + prod;
-}
-
-// med (and with tails the 5 % and 95 % quantiles) of the group's dimensions out of the sorted image of their un-folded keys, onto the device at
-// ws + o_med (+ o_q); nan_dims (may be NULL): whether the dimension holds a NaN (its largest key is the NaN key)
-int rank_group_quantiles(const mi::drank::RankPlan& plan, uint64_t dim0, uint64_t nd, const uint64_t* sorted, bool tails, char* W, hipStream_t st,
-                         std::vector<double>& os, std::vector<double>& q, std::vector<uint8_t>* nan_dims)
-{
-    const double probs[3] = {0.5, 0.05, 0.95};
-    uint64_t ranks[8];
-    double g[3];
-    for (int a = 0; a < 3; ++a) type7_ranks(plan.S, probs[a], &ranks[2 * a], &ranks[2 * a + 1], &g[a]);
-    ranks[6] = ranks[7] = plan.S - 1;                    // the largest key: the NaN key if the dimension holds a NaN
-    os.resize(8 * nd);
-    q.resize(3 * nd);
-    HIP_TRY((hipError_t)mi::drank::rank_order_stats_group(plan, nd, sorted, ranks, W, os.data(), st));
-    if (nan_dims)
-        for (uint64_t j = 0; j < nd; ++j) (*nan_dims)[dim0 + j] = os[6 * nd + j] != os[6 * nd + j];
-    for (int a = 0; a < 3; ++a)
-        for (uint64_t j = 0; j < nd; ++j) q[a * nd + j] = type7_value(os[(2 * a) * nd + j], os[(2 * a + 1) * nd + j], g[a]);
-    HIP_TRY(hipMemcpyAsync(W + plan.o_med + dim0 * 8, q.data(), nd * 8, hipMemcpyHostToDevice, st));
-    if (tails) {
-        HIP_TRY(hipMemcpyAsync(W + plan.o_q + dim0 * 8, q.data() + nd, nd * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(W + plan.o_q + (plan.d + dim0) * 8, q.data() + 2 * nd, nd * 8, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));                   // q is this frame's: the uploads have read it
-    return MI_OK;
-}
-}  // namespace
-
-// Average ranks / normal scores of the retained samples of a slab [n_keep][d][C] (draws_rank.hip; the definitions: include/mi_mcmc.h)
-int mi_mcmc_draws_rank_transform(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, int32_t what, uint32_t flags,
-                                 double* out, void* stream)
-{
-    const char* who = "draws_rank_transform";
-    int rc = rank_check(who, draws_kdc, n_keep, d, n_chains, flags);
-    if (rc) return rc;
-    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
-    if (what != MI_RANK_AVERAGE && what != MI_RANK_NORMAL) return fail(MI_ERR_BAD_ARG, "%s: what = %d is neither MI_RANK_AVERAGE nor MI_RANK_NORMAL", who, what);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const mi::drank::RankPlan plan = mi::drank::rank_plan(n_keep, d, n_chains, flags, false, g_rank_ws_bytes.load(std::memory_order_relaxed));
-    DevBuf staged, out_dev;
-    const double* x = draws_kdc;
-    double* o = out;
-    if (mem == MI_MEM_HOST) {
-        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
-        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
-        x = staged.as<double>();
-        HIP_TRY(out_dev.alloc(plan.S * d * 8));
-        o = out_dev.as<double>();
-    }
-    WsLease ws;
-    rc = ws_get(st, plan.bytes, ws);
-    if (rc) return rc;
-    char* W = ws.as<char>();
-    const bool fold = (flags & MI_RANK_FOLD) != 0;
-    std::vector<double> os, q;
-    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
-        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
-        const uint64_t* sorted = nullptr;
-        HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, false, W, st, &sorted));
-        if (fold) {                                      // the medians out of the un-folded image, then the sort of |x - med|
-            rc = rank_group_quantiles(plan, dim0, nd, sorted, false, W, st, os, q, nullptr);
-            if (rc) return rc;
-            HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
-        }
-        HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, fold, what, sorted, W, o, d, dim0, st));
-    }
-    if (mem == MI_MEM_HOST) HIP_TRY(hipMemcpyAsync(out, o, plan.S * d * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));                   // blocking: the staged slab, the staged output and the workspace are ours
-    return MI_OK;
-}
-
-// Rank-normalised split-R-hat, bulk-ESS and tail-ESS: the pieces above and mi_mcmc_draw_stats on the composed slabs (include/mi_mcmc.h)
-int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* rhat, double* rhat_bulk,
-                              double* rhat_tail, double* ess_bulk, double* ess_tail, void* stream)
-{
-    const char* who = "draw_stats_ranked";
-    int rc = rank_check(who, draws_kdc, n_keep, d, n_chains, MI_RANK_SPLIT);
-    if (rc) return rc;
-    if (!rhat && !rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail) return fail(MI_ERR_BAD_ARG, "%s: all five outputs are NULL, nothing is asked for", who);
-    if (n_keep < 4) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, at least 4 draws are needed (two halves of two)", who, (unsigned long long)n_keep);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const mi::drank::RankPlan plan = mi::drank::rank_plan(n_keep, d, n_chains, MI_RANK_SPLIT, true, g_rank_ws_bytes.load(std::memory_order_relaxed));
-    DevBuf staged;
-    const double* x = draws_kdc;
-    if (mem == MI_MEM_HOST) {
-        HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
-        HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
-        x = staged.as<double>();
-    }
-    WsLease ws;
-    rc = ws_get(st, plan.bytes, ws);
-    if (rc) return rc;
-    char* W = ws.as<char>();
-    double* slab = reinterpret_cast<double*>(W + plan.o_slab);
-    const bool want_bulk = rhat || rhat_bulk || ess_bulk, want_fold = rhat || rhat_tail, want_tail = ess_tail != nullptr;
-    std::vector<double> rb(d), rt(d), eb(d), et(d), e05, e95, os, q;
-    std::vector<uint8_t> has_nan(d, 0);
-    const uint64_t h = plan.h, C2 = 2 * n_chains;
-    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
-        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
-        const uint64_t* sorted = nullptr;
-        HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, false, W, st, &sorted));
-        rc = rank_group_quantiles(plan, dim0, nd, sorted, true, W, st, os, q, &has_nan);
-        if (rc) return rc;
-        if (want_bulk) {
-            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, false, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rb.data() + dim0, ess_bulk ? eb.data() + dim0 : nullptr, stream);
-            if (rc) return rc;
-        }
-        if (want_tail) {
-            e05.resize(nd); e95.resize(nd);
-            HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 0, W, slab, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e05.data(), stream);
-            if (rc) return rc;
-            HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 1, W, slab, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e95.data(), stream);
-            if (rc) return rc;
-            for (uint64_t j = 0; j < nd; ++j) et[dim0 + j] = e95[j] < e05[j] ? e95[j] : e05[j];
-        }
-        if (want_fold) {
-            HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
-            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, true, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rt.data() + dim0, nullptr, stream);
-            if (rc) return rc;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    const double nan = std::nan("");
-    for (uint64_t i = 0; i < d; ++i) {
-        const bool bad = has_nan[i] != 0;                // a NaN among the retained samples: every output of the dimension is NaN
-        if (rhat_bulk) rhat_bulk[i] = bad ? nan : rb[i];
-        if (rhat_tail) rhat_tail[i] = bad ? nan : rt[i];
-        if (rhat) rhat[i] = (bad || rb[i] != rb[i] || rt[i] != rt[i]) ? nan : (rb[i] > rt[i] ? rb[i] : rt[i]);
-        if (ess_bulk) ess_bulk[i] = bad ? nan : eb[i];
-        if (ess_tail) ess_tail[i] = bad ? nan : et[i];
-    }
-    return MI_OK;
-}
-
-int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
-{
-    if (n && (!p || !z)) return fail(MI_ERR_BAD_ARG, "norm_ppf: null array");
-    for (uint64_t k = 0; k < n; ++k) z[k] = mi::norm_ppf(p[k]);
-    return MI_OK;
-}
-
-namespace {
-// The checks of mi_mcmc_draws_log_kernel: they need no device
-int log_kernel_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const double* out)
-{
-    if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
-    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
-    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
-    if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
-    if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
-    if (n_keep == 0 || n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = 0, at least 1 sample is needed", who);
-    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (t->d > mi::dlogk::LOGK_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)mi::dlogk::LOGK_MAX_D);
-    switch (t->kind) {
-    case MI_TARGET_GAUSS_ISO: break;
-    case MI_TARGET_GAUSS_DIAG:
-    case MI_TARGET_GAUSS_DENSE:
-        if (!t->prec) return fail(MI_ERR_BAD_ARG, "%s: target.prec is NULL", who);
-        break;
-    case MI_TARGET_LOGISTIC:
-        if (!t->X || !t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
-        break;
-    case MI_TARGET_NORMAL_MODEL:
-        if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
-        if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
-        break;
-    case MI_TARGET_GAUSS_MIXTURE:
-        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is not implemented by this reducer", who);
-    default:
-        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, t->kind);
-    }
-    return MI_OK;
-}
-}  // namespace
-
-// TEST HOOK (mi_mcmc_probes.h): the plan of mi_mcmc_draws_log_kernel, host arithmetic
-void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out8)
-{
-    const mi::dlogk::LogkPlan p = mi::dlogk::logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host != 0, target_host != 0);
-    out8[0] = (uint64_t)p.route; out8[1] = p.grid; out8[2] = p.block; out8[3] = p.lds_bytes;
-    out8[4] = p.Kp; out8[5] = p.ldA; out8[6] = p.n_row_tiles; out8[7] = p.bytes;
-}
-
-// out[t][c] = log K(x[t][:][c]) of every column of a slab [n_keep][d][C] (draws_logk.hip; the arithmetic: include/mi_mcmc.h)
-int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, double* out, void* stream)
-{
-    const char* who = "draws_log_kernel";
-    int rc = log_kernel_check(who, target, draws_kdc, n_keep, n_chains, out);
-    if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MI_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU path");
-    (void)hipGetLastError();
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint64_t d = target->d, K = n_keep * n_chains;
-    // 2^38 columns are 2 TB of results alone: beyond any device, and what keeps the grid and every byte count below inside their types
-    const bool has_rows = target->kind == MI_TARGET_LOGISTIC || target->kind == MI_TARGET_NORMAL_MODEL;
-    if (K > (1ULL << 38) || (has_rows && target->n_rows > (1ULL << 38))) return fail(MI_ERR_OOM, "%s: K = %llu columns / n_rows = %llu do not fit the device memory", who, (unsigned long long)K, (unsigned long long)target->n_rows);
-    const bool slab_host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
-    const mi::dlogk::LogkPlan plan = mi::dlogk::logk_plan(target->kind, d, target->n_rows, n_keep, n_chains, slab_host, target_host);
-    WsLease ws;
-    rc = ws_get(st, plan.bytes, ws);
-    if (rc) return rc;
-    char* W = ws.as<char>();
-    const double* mat = target->kind == MI_TARGET_LOGISTIC ? target->X : target->prec;
-    const double* y = target->y;
-    if (target_host) {
-        if (plan.mat_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_mat, mat, plan.mat_doubles * 8, hipMemcpyHostToDevice, st)); mat = reinterpret_cast<const double*>(W + plan.o_mat); }
-        if (plan.y_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_y, y, plan.y_doubles * 8, hipMemcpyHostToDevice, st)); y = reinterpret_cast<const double*>(W + plan.o_y); }
-    }
-    const double* x = draws_kdc;
-    double* o = out;
-    if (slab_host) {
-        HIP_TRY(hipMemcpyAsync(W + plan.o_slab, draws_kdc, K * d * 8, hipMemcpyHostToDevice, st));
-        x = reinterpret_cast<const double*>(W + plan.o_slab);
-        o = reinterpret_cast<double*>(W + plan.o_out);
-    }
-    HIP_TRY((hipError_t)mi::dlogk::logk_run(plan, x, mat, y, W, o, st));
-    if (slab_host) {
-        HIP_TRY(hipMemcpyAsync(out, o, K * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));               // blocking: out is the caller's host array
-    } else if (target_host) {
-        HIP_TRY(hipStreamSynchronize(st));               // the caller's host arrays of the target have been read when the call returns
-    }
     return MI_OK;
 }
 

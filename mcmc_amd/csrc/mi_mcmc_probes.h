@@ -75,7 +75,7 @@ void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes);
  * out8: route (0 one lane per column, 1 the fused matrix product), workgroups, threads per workgroup, LDS bytes per workgroup, the contraction extent Kp,
  * the padded output rows ldA, the row tiles a workgroup walks, the workspace bytes. */
 void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out8);
-/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats (draw_stats.hpp, stats_collate.hip): what this thread's last call
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats (draw_stats.hpp, draws_api.hip): what this thread's last call
  * launched.  out8: the route (0 the one-pass Gram kernel, 1 the window + lag-block ladder, 2 the streamed kernel), NB of the Gram kernel (0 on the other
  * routes), the chain groups G, the 64-chain tiles the largest chain group walked, the window launches, the lag-pass launches (stats_acov_kernel), those of
  * them that ran a subset of the dimensions, and the smallest such subset (0: none).  Host bookkeeping, per thread.  Results do not depend on it. */
