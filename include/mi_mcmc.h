@@ -691,6 +691,50 @@ int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z);   /* host arrays, 
 int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains,
                              double* out /* [n_keep][C], in `mem` */, void* stream);
 
+/* The pointwise log-likelihood of a slab [n_keep][d][C] (in `mem`; a host slab is staged) under a target that carries observations, and its fold over the
+ * draws per observation, on the device: for every data row r the log pointwise predictive density lppd_r and the effective number of parameters
+ * p_waic_r (WAIC, Watanabe 2010; Vehtari, Gelman and Gabry 2017), and on request the matrix ll itself.  It is the other fold of the product that
+ * mi_mcmc_draws_log_kernel folds over the rows.  target->X / y live in target->mem; kernel_hint is ignored.  lppd_out, p_waic_out ([n_rows]) and
+ * loglik_out ([n_rows][n_keep][C]) are in `mem`; any may be NULL.  Row r of loglik_out is a slab [n_keep][1][C] that mi_mcmc_draw_stats,
+ * mi_mcmc_draw_stats_ranked, mi_mcmc_draws_quantiles and mi_mcmc_draws_covariance take as it is, and what a host PSIS-LOO reads.  summary (HOST, 4
+ * doubles, may be NULL) = {elpd_waic, p_waic, lppd, se_elpd}.  A device slab with summary == NULL: the call returns after enqueueing on `stream` (with
+ * a target in host memory: once its arrays have been read).  A device slab with summary, or a host slab: blocking.  Workspace: the stream's cached
+ * one (mi_mcmc_release_workspace) -- the packed matrix, the chunk partials (32 n_chunks bytes per padded row), and the staged copies of a host slab,
+ * target and outputs.  No CPU path: no device is MI_ERR_NO_DEVICE; what does not fit the free device memory is MI_ERR_OOM.
+ * MI_ERR_BAD_ARG, before any HIP call: a NULL target or slab; all four outputs NULL; a struct_size mismatch; d 0; n_keep or n_chains beyond 32 bits;
+ * K = n_keep * n_chains < 2; d > 65 536; LOGISTIC / NORMAL_MODEL without their data or with n_rows = 0; NORMAL_MODEL with d != 2; an unknown kind.
+ * MI_ERR_UNSUPPORTED: ISO / DIAG / DENSE / GAUSS_MIXTURE -- they have no observations.
+ * DEFINITION (fp64, every operation rounded once, nothing contracted; exp / log / softplus: det_math.hpp).  K = n_keep * C; sample k = t * C + c is
+ * column (t, c), x its d values.
+ *   LOGISTIC      eta = the fma chain over j ascending of X_rj * x_j, from +0;  ll[r][k] = y_r * eta - softplus(eta)  -- term_r of
+ *                 mi_mcmc_draws_log_kernel, the same bits
+ *   NORMAL_MODEL  (mu, sigma) = x;  e = y_r - mu;  ll[r][k] = -(0.5 * LOG_2PI + log(sigma)) - (e * e) / (2 * (sigma * sigma))
+ *   loglik_out[r][t][c] = ll[r][k]
+ * THE ORDER of the sums over k, for every row r alike (the constants are part of the definition):
+ *   chunks        the columns are cut into chunks of 2048: chunk b holds k = 2048 b .. min(K, 2048 b + 2048) - 1, n_b columns
+ *   shift         sh_b = ll[r][2048 b], the chunk's first column
+ *   slots         the column at offset o = k - 2048 b belongs to slot s = 16 ((o mod 128) div 32) + o mod 16, one of 64.  A slot takes its columns
+ *                 ascending, from +0:  v = ll - sh_b;  S1 = S1 + v;  S2 = S2 + v * v;  A = A + exp(ll)
+ *   tree          each of S1, S2, A: the 16 slots s = 16 w .. 16 w + 15 of w meet as u[i] = u[i] + u[i + 8] (i < 8), then + u[i + 4] (i < 4), + u[i + 2],
+ *                 + u[i + 1]; the four w as (w0 + w1) + (w2 + w3)
+ *   chunk moments mean_b = sh_b + S1 / n_b;  M2_b = S2 - (S1 * S1) / n_b  (n_b as a double)
+ *   merge         chunk 0 starts (n, mean, M2, A) = (n_0, mean_0, M2_0, A_0); then b ascending: delta = mean_b - mean;  nn = n + n_b;
+ *                 mean = mean + delta * (n_b / nn);  M2 = (M2 + M2_b) + (delta * delta) * ((n * n_b) / nn);  n = nn;  A = A + A_b
+ *   lppd_r = log(A / (double)K);   p_waic_r = M2 / (double)(K - 1)  -- the sample variance of ll[r][:], from sums about a shift that is one of the
+ *   values: no difference of two large numbers is formed
+ *   summary       elpd_r = lppd_r - p_waic_r;  elpd_waic, p_waic, lppd: the plain sums over r ascending from +0 of elpd_r, p_waic_r, lppd_r;
+ *                 m = elpd_waic / (double)n_rows;  v = the sum over r ascending of (elpd_r - m) * (elpd_r - m);
+ *                 se_elpd = sqrt((double)n_rows * (v / (double)(n_rows - 1)))  -- NaN for n_rows = 1
+ * The logistic product runs on v_mfma_f64_16x16x4_f64 with the contraction ascending; a workgroup owns 128 rows and one chunk, and ll reaches memory
+ * only where loglik_out asks for it (mcmc_amd/csrc/draws_waic.hip).  The result depends on no device, grid, timing or atomic order.  Non-finite
+ * draws propagate by the IEEE rules through exactly these expressions; nothing is filtered or flagged.  The numpy statement is mcmc_amd/waic.py. */
+int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains,
+                       double* lppd_out,    /* [n_rows] in `mem`, may be NULL */
+                       double* p_waic_out,  /* [n_rows] in `mem`, may be NULL */
+                       double* loglik_out,  /* [n_rows][n_keep][C] in `mem`, may be NULL */
+                       double* summary,     /* HOST, 4 doubles, may be NULL */
+                       void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

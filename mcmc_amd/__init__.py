@@ -94,7 +94,7 @@ EXPORTS = [
     "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
     "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
     "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
-    "mi_mcmc_draws_log_kernel",
+    "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -865,3 +865,39 @@ def test_logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     lib().mi_mcmc_test_logk_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
                                  C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
     return dict(zip(("route", "grid", "block", "lds_bytes", "Kp", "ldA", "n_row_tiles", "ws_bytes"), (int(v) for v in o)))
+
+
+def draws_waic(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_lppd=True, want_p_waic=True, want_loglik=False, want_summary=True,
+               lppd=None, p_waic=None, loglik=None):
+    """mi_mcmc_draws_waic: per observation r of `target` (make_target; LOGISTIC or NORMAL_MODEL) the log pointwise predictive density lppd[r] and the
+    effective number of parameters p_waic[r] of a slab [n_keep, d, C], on request the pointwise log-likelihood loglik[r, t, c] itself, and
+    summary = (elpd_waic, p_waic, lppd, se_elpd) -- numpy array, a 2-D [d, C] array being the case n_keep = 1; or a device tensor / pointer with
+    mem=MEM_DEVICE, explicit n_keep and n_chains and device tensors `lppd`, `p_waic`, `loglik` for what is wanted of them (written on `stream`; the call
+    waits only where the summary is wanted).  include/mi_mcmc.h states every value bit for bit, mcmc_amd.waic repeats it in numpy.  Returns a dict
+    of lppd, p_waic, loglik ([n_rows, n_keep, C]: row r as [n_keep, 1, C] is a slab that draw_stats and draws_quantiles take) and summary (a dict);
+    what was not asked for is None."""
+    d, n_rows = int(target.d), int(target.n_rows)
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d_slab, n_chains = draws.shape
+        if d_slab != d:
+            raise ValueError(f"the slab has d = {d_slab}, the target d = {d}")
+        lppd = np.zeros(n_rows) if want_lppd else None
+        p_waic = np.zeros(n_rows) if want_p_waic else None
+        loglik = np.zeros((n_rows, int(n_keep), int(n_chains))) if want_loglik else None
+    summ = np.zeros(4) if want_summary else None
+    _check(lib().mi_mcmc_draws_waic(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                    C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(p_waic)), C.c_void_p(_ptr(loglik)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    summary = None if summ is None else dict(zip(("elpd_waic", "p_waic", "lppd", "se_elpd"), (float(v) for v in summ)))
+    return dict(lppd=lppd, p_waic=p_waic, loglik=loglik, summary=summary)
+
+
+def test_waic_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_host=True, want_loglik=False):
+    """mi_mcmc_test_waic_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_waic call, host arithmetic -- a dict of route (0 elementwise, 1 the
+    matrix product), chunk, n_chunks, grid, block, lds_bytes, ldR, Kp, merge_grid, ws_bytes."""
+    o = (C.c_uint64 * 10)()
+    lib().mi_mcmc_test_waic_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), C.c_int(int(bool(want_loglik))), o)
+    return dict(zip(("route", "chunk", "n_chunks", "grid", "block", "lds_bytes", "ldR", "Kp", "merge_grid", "ws_bytes"), (int(v) for v in o)))

@@ -1,5 +1,5 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
-// draws_cov.hip, draws_select.hip, draws_rank.hip and draws_logk.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip and draws_waic.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "draws_select.hpp"
 #include "draws_rank.hpp"
 #include "draws_logk.hpp"
+#include "draws_waic.hpp"
 
 using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
@@ -649,6 +650,117 @@ int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, i
         HIP_TRY(hipStreamSynchronize(st));               // blocking: out is the caller's host array
     } else if (target_host) {
         HIP_TRY(hipStreamSynchronize(st));               // the caller's host arrays of the target have been read when the call returns
+    }
+    return MI_OK;
+}
+
+// The checks of mi_mcmc_draws_waic: log_kernel_check's, for the two targets that carry observations; they need no device
+static int waic_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, bool any_out)
+{
+    if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (!any_out) return fail(MI_ERR_BAD_ARG, "%s: lppd_out, p_waic_out, loglik_out and summary are all NULL, nothing is asked for", who);
+    if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
+    if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (n_keep * n_chains < 2) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least 2 samples are needed", who, (unsigned long long)(n_keep * n_chains));
+    if (t->d > mi::dwaic::WAIC_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)mi::dwaic::WAIC_MAX_D);
+    switch (t->kind) {
+    case MI_TARGET_GAUSS_ISO:
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d has no observations: only MI_TARGET_LOGISTIC and MI_TARGET_NORMAL_MODEL have a pointwise log-likelihood", who, t->kind);
+    case MI_TARGET_LOGISTIC:
+        if (!t->X || !t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
+        break;
+    case MI_TARGET_NORMAL_MODEL:
+        if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
+        if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
+        break;
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, t->kind);
+    }
+    return MI_OK;
+}
+
+// {elpd_waic, p_waic, lppd, se_elpd} of the rows' values (include/mi_mcmc.h; this file is compiled with -ffp-contract=off: nothing is fused)
+static void waic_summary(const double* lppd, const double* pw, uint64_t n_rows, double* summary)
+{
+    double elpd = 0.0, p = 0.0, l = 0.0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const double e = lppd[r] - pw[r];
+        elpd = elpd + e;
+        p = p + pw[r];
+        l = l + lppd[r];
+    }
+    const double m = elpd / (double)n_rows;
+    double v = 0.0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const double e = lppd[r] - pw[r];
+        const double dv = e - m;
+        const double sq = dv * dv;
+        v = v + sq;
+    }
+    const double var = v / (double)(n_rows - 1);          // n_rows = 1: 0 / 0, NaN
+    const double nv = (double)n_rows * var;
+    summary[0] = elpd; summary[1] = p; summary[2] = l; summary[3] = std::sqrt(nv);
+}
+
+void mi_mcmc_test_waic_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, int want_loglik, uint64_t* out10)
+{
+    const mi::dwaic::WaicPlan p = mi::dwaic::waic_plan(kind, d, n_rows, n_keep, n_chains, slab_host != 0, target_host != 0, want_loglik != 0);
+    out10[0] = (uint64_t)p.route; out10[1] = mi::dwaic::WAIC_CHUNK; out10[2] = p.n_chunks; out10[3] = p.grid; out10[4] = p.block;
+    out10[5] = p.lds_bytes; out10[6] = p.ldR; out10[7] = p.Kp; out10[8] = p.merge_grid; out10[9] = p.bytes;
+}
+
+// Pointwise log-likelihood, lppd and p_waic per data row of a slab [n_keep][d][C], and the WAIC summary (draws_waic.hip; the arithmetic: include/mi_mcmc.h).
+// The slab and the target's arrays are staged into the workspace by the plan, as mi_mcmc_draws_log_kernel stages them.
+int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, double* lppd_out, double* p_waic_out,
+                       double* loglik_out, double* summary, void* stream)
+{
+    const char* who = "draws_waic";
+    int rc = waic_check(who, target, draws_kdc, n_keep, n_chains, lppd_out || p_waic_out || loglik_out || summary);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d, K = n_keep * n_chains, n_rows = target->n_rows;
+    const bool slab_host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
+    // what keeps the grids and every byte count inside their types: 2^38 columns or rows are beyond any device
+    if (K > (1ULL << 38) || n_rows > (1ULL << 38)) return fail(MI_ERR_OOM, "%s: K = %llu columns / n_rows = %llu do not fit the device memory", who, (unsigned long long)K, (unsigned long long)n_rows);
+    const mi::dwaic::WaicPlan plan = mi::dwaic::waic_plan(target->kind, d, n_rows, n_keep, n_chains, slab_host, target_host, loglik_out != nullptr);
+    if (plan.grid >= (1ULL << 31)) return fail(MI_ERR_OOM, "%s: %llu chunks x %llu rows do not fit the device memory", who, (unsigned long long)plan.n_chunks, (unsigned long long)n_rows);
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    const double* mat = target->X;
+    const double* y = target->y;
+    if (target_host) {
+        if (plan.mat_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_mat, mat, plan.mat_doubles * 8, hipMemcpyHostToDevice, st)); mat = reinterpret_cast<const double*>(W + plan.o_mat); }
+        HIP_TRY(hipMemcpyAsync(W + plan.o_y, y, plan.y_doubles * 8, hipMemcpyHostToDevice, st));
+        y = reinterpret_cast<const double*>(W + plan.o_y);
+    }
+    const double* x = draws_kdc;
+    double* ll = loglik_out;
+    if (slab_host) {
+        HIP_TRY(hipMemcpyAsync(W + plan.o_slab, draws_kdc, K * d * 8, hipMemcpyHostToDevice, st));
+        x = reinterpret_cast<const double*>(W + plan.o_slab);
+        if (loglik_out) ll = reinterpret_cast<double*>(W + plan.o_ll);
+    }
+    HIP_TRY((hipError_t)mi::dwaic::waic_run(plan, x, mat, y, W, ll, st));
+    const hipMemcpyKind back = slab_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (lppd_out) HIP_TRY(hipMemcpyAsync(lppd_out, W + plan.o_lppd, n_rows * 8, back, st));
+    if (p_waic_out) HIP_TRY(hipMemcpyAsync(p_waic_out, W + plan.o_pw, n_rows * 8, back, st));
+    if (slab_host && loglik_out) HIP_TRY(hipMemcpyAsync(loglik_out, ll, K * n_rows * 8, hipMemcpyDeviceToHost, st));
+    if (summary) {
+        std::vector<double> lp(n_rows), pw(n_rows);
+        HIP_TRY(hipMemcpyAsync(lp.data(), W + plan.o_lppd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(pw.data(), W + plan.o_pw, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // blocking: summary is written on the host
+        waic_summary(lp.data(), pw.data(), n_rows, summary);
+    } else if (slab_host || target_host) {
+        HIP_TRY(hipStreamSynchronize(st));               // the outputs are the caller's host arrays / the target's host arrays have been read
     }
     return MI_OK;
 }

@@ -80,6 +80,12 @@ void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t 
  * routes), the chain groups G, the 64-chain tiles the largest chain group walked, the window launches, the lag-pass launches (stats_acov_kernel), those of
  * them that ran a subset of the dimensions, and the smallest such subset (0: none).  Host bookkeeping, per thread.  Results do not depend on it. */
 void mi_mcmc_test_draw_stats_last(uint64_t* out8);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draws_waic (draws_waic.hpp): the plan of a call, host arithmetic that needs
+ * no device.  kind: mi_target_kind (LOGISTIC or NORMAL_MODEL); slab_host / target_host != 0: staged in the workspace; want_loglik != 0: the matrix ll is
+ * asked for.  out10: route (0 elementwise, 1 the matrix product), the chunk length in columns, the chunks, workgroups, threads per workgroup, LDS bytes per
+ * workgroup, the padded rows ldR, the contraction extent Kp, the merge kernel's workgroups, the workspace bytes. */
+void mi_mcmc_test_waic_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, int want_loglik,
+                            uint64_t* out10);
 #ifdef __cplusplus
 }
 #endif
