@@ -580,35 +580,37 @@ int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
     return MI_OK;
 }
 
-// The checks of mi_mcmc_draws_log_kernel: they need no device
-static int log_kernel_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const double* out)
+// The checks that mi_mcmc_draws_log_kernel and mi_mcmc_draws_waic share, in the order in which a call that fails several reports them; they need no
+// device.  nothing_asked: NULL, or what to say of the call's outputs; the call needs at least min_K = 1 or 2 samples.  The two targets that carry
+// observations are checked here; what an entry point makes of the other kinds is its own, after this
+static int target_slab_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const char* nothing_asked,
+                             uint64_t min_K, uint64_t max_d)
 {
     if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
     if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
-    if (!out) return fail(MI_ERR_BAD_ARG, "%s: out is NULL", who);
+    if (nothing_asked) return fail(MI_ERR_BAD_ARG, "%s: %s", who, nothing_asked);
     if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
     if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
-    if (n_keep == 0 || n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = 0, at least 1 sample is needed", who);
     if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (t->d > mi::dlogk::LOGK_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)mi::dlogk::LOGK_MAX_D);
-    switch (t->kind) {
-    case MI_TARGET_GAUSS_ISO: break;
-    case MI_TARGET_GAUSS_DIAG:
-    case MI_TARGET_GAUSS_DENSE:
-        if (!t->prec) return fail(MI_ERR_BAD_ARG, "%s: target.prec is NULL", who);
-        break;
-    case MI_TARGET_LOGISTIC:
-        if (!t->X || !t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
-        break;
-    case MI_TARGET_NORMAL_MODEL:
+    if (n_keep * n_chains < min_K)
+        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least %s needed", who, (unsigned long long)(n_keep * n_chains), min_K == 1 ? "1 sample is" : "2 samples are");
+    if (t->d > max_d) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)max_d);
+    if (t->kind == MI_TARGET_LOGISTIC && (!t->X || !t->y || t->n_rows == 0)) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
+    if (t->kind == MI_TARGET_NORMAL_MODEL) {
         if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
         if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
-        break;
-    case MI_TARGET_GAUSS_MIXTURE:
-        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is not implemented by this reducer", who);
-    default:
-        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, t->kind);
     }
+    return MI_OK;
+}
+
+// What the two calls stage into the workspace W of their plan (its areas o_mat, o_y, o_slab): the arrays of a host target (mat_doubles of mat -- prec or
+// X --, y_doubles of y) and a host slab, the copies enqueued on st.  *x, *mat, *y: the caller's pointers on entry, the device's on return
+static int stage_target_slab(char* W, size_t o_mat, size_t o_y, size_t o_slab, size_t mat_doubles, size_t y_doubles, bool target_host, bool slab_host, size_t slab_doubles,
+                             hipStream_t st, const double** x, const double** mat, const double** y)
+{
+    if (target_host && mat_doubles) { HIP_TRY(hipMemcpyAsync(W + o_mat, *mat, mat_doubles * 8, hipMemcpyHostToDevice, st)); *mat = reinterpret_cast<const double*>(W + o_mat); }
+    if (target_host && y_doubles) { HIP_TRY(hipMemcpyAsync(W + o_y, *y, y_doubles * 8, hipMemcpyHostToDevice, st)); *y = reinterpret_cast<const double*>(W + o_y); }
+    if (slab_host) { HIP_TRY(hipMemcpyAsync(W + o_slab, *x, slab_doubles * 8, hipMemcpyHostToDevice, st)); *x = reinterpret_cast<const double*>(W + o_slab); }
     return MI_OK;
 }
 
@@ -617,8 +619,19 @@ static int log_kernel_check(const char* who, const mi_target* t, const double* d
 int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, double* out, void* stream)
 {
     const char* who = "draws_log_kernel";
-    int rc = log_kernel_check(who, target, draws_kdc, n_keep, n_chains, out);
+    int rc = target_slab_check(who, target, draws_kdc, n_keep, n_chains, out ? nullptr : "out is NULL", 1, mi::dlogk::LOGK_MAX_D);
     if (rc) return rc;
+    switch (target->kind) {
+    case MI_TARGET_GAUSS_ISO: case MI_TARGET_LOGISTIC: case MI_TARGET_NORMAL_MODEL: break;
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+        if (!target->prec) return fail(MI_ERR_BAD_ARG, "%s: target.prec is NULL", who);
+        break;
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is not implemented by this reducer", who);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, target->kind);
+    }
     if ((rc = need_device())) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t d = target->d, K = n_keep * n_chains;
@@ -631,55 +644,15 @@ int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, i
     rc = ws_get(st, plan.bytes, ws);
     if (rc) return rc;
     char* W = ws.as<char>();
-    const double* mat = target->kind == MI_TARGET_LOGISTIC ? target->X : target->prec;
-    const double* y = target->y;
-    if (target_host) {
-        if (plan.mat_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_mat, mat, plan.mat_doubles * 8, hipMemcpyHostToDevice, st)); mat = reinterpret_cast<const double*>(W + plan.o_mat); }
-        if (plan.y_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_y, y, plan.y_doubles * 8, hipMemcpyHostToDevice, st)); y = reinterpret_cast<const double*>(W + plan.o_y); }
-    }
-    const double* x = draws_kdc;
-    double* o = out;
-    if (slab_host) {
-        HIP_TRY(hipMemcpyAsync(W + plan.o_slab, draws_kdc, K * d * 8, hipMemcpyHostToDevice, st));
-        x = reinterpret_cast<const double*>(W + plan.o_slab);
-        o = reinterpret_cast<double*>(W + plan.o_out);
-    }
+    const double *x = draws_kdc, *mat = target->kind == MI_TARGET_LOGISTIC ? target->X : target->prec, *y = target->y;
+    if ((rc = stage_target_slab(W, plan.o_mat, plan.o_y, plan.o_slab, plan.mat_doubles, plan.y_doubles, target_host, slab_host, K * d, st, &x, &mat, &y))) return rc;
+    double* o = slab_host ? reinterpret_cast<double*>(W + plan.o_out) : out;
     HIP_TRY((hipError_t)mi::dlogk::logk_run(plan, x, mat, y, W, o, st));
     if (slab_host) {
         HIP_TRY(hipMemcpyAsync(out, o, K * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));               // blocking: out is the caller's host array
     } else if (target_host) {
         HIP_TRY(hipStreamSynchronize(st));               // the caller's host arrays of the target have been read when the call returns
-    }
-    return MI_OK;
-}
-
-// The checks of mi_mcmc_draws_waic: log_kernel_check's, for the two targets that carry observations; they need no device
-static int waic_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, bool any_out)
-{
-    if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
-    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
-    if (!any_out) return fail(MI_ERR_BAD_ARG, "%s: lppd_out, p_waic_out, loglik_out and summary are all NULL, nothing is asked for", who);
-    if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
-    if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
-    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (n_keep * n_chains < 2) return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least 2 samples are needed", who, (unsigned long long)(n_keep * n_chains));
-    if (t->d > mi::dwaic::WAIC_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)mi::dwaic::WAIC_MAX_D);
-    switch (t->kind) {
-    case MI_TARGET_GAUSS_ISO:
-    case MI_TARGET_GAUSS_DIAG:
-    case MI_TARGET_GAUSS_DENSE:
-    case MI_TARGET_GAUSS_MIXTURE:
-        return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d has no observations: only MI_TARGET_LOGISTIC and MI_TARGET_NORMAL_MODEL have a pointwise log-likelihood", who, t->kind);
-    case MI_TARGET_LOGISTIC:
-        if (!t->X || !t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
-        break;
-    case MI_TARGET_NORMAL_MODEL:
-        if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
-        if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
-        break;
-    default:
-        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, t->kind);
     }
     return MI_OK;
 }
@@ -720,8 +693,20 @@ int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t
                        double* loglik_out, double* summary, void* stream)
 {
     const char* who = "draws_waic";
-    int rc = waic_check(who, target, draws_kdc, n_keep, n_chains, lppd_out || p_waic_out || loglik_out || summary);
+    const bool any_out = lppd_out || p_waic_out || loglik_out || summary;
+    int rc = target_slab_check(who, target, draws_kdc, n_keep, n_chains, any_out ? nullptr : "lppd_out, p_waic_out, loglik_out and summary are all NULL, nothing is asked for",
+                               2, mi::dwaic::WAIC_MAX_D);
     if (rc) return rc;
+    switch (target->kind) {
+    case MI_TARGET_LOGISTIC: case MI_TARGET_NORMAL_MODEL: break;
+    case MI_TARGET_GAUSS_ISO:
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d has no observations: only MI_TARGET_LOGISTIC and MI_TARGET_NORMAL_MODEL have a pointwise log-likelihood", who, target->kind);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, target->kind);
+    }
     if ((rc = need_device())) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t d = target->d, K = n_keep * n_chains, n_rows = target->n_rows;
@@ -734,20 +719,9 @@ int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t
     rc = ws_get(st, plan.bytes, ws);
     if (rc) return rc;
     char* W = ws.as<char>();
-    const double* mat = target->X;
-    const double* y = target->y;
-    if (target_host) {
-        if (plan.mat_doubles) { HIP_TRY(hipMemcpyAsync(W + plan.o_mat, mat, plan.mat_doubles * 8, hipMemcpyHostToDevice, st)); mat = reinterpret_cast<const double*>(W + plan.o_mat); }
-        HIP_TRY(hipMemcpyAsync(W + plan.o_y, y, plan.y_doubles * 8, hipMemcpyHostToDevice, st));
-        y = reinterpret_cast<const double*>(W + plan.o_y);
-    }
-    const double* x = draws_kdc;
-    double* ll = loglik_out;
-    if (slab_host) {
-        HIP_TRY(hipMemcpyAsync(W + plan.o_slab, draws_kdc, K * d * 8, hipMemcpyHostToDevice, st));
-        x = reinterpret_cast<const double*>(W + plan.o_slab);
-        if (loglik_out) ll = reinterpret_cast<double*>(W + plan.o_ll);
-    }
+    const double *x = draws_kdc, *mat = target->X, *y = target->y;
+    if ((rc = stage_target_slab(W, plan.o_mat, plan.o_y, plan.o_slab, plan.mat_doubles, plan.y_doubles, target_host, slab_host, K * d, st, &x, &mat, &y))) return rc;
+    double* ll = (slab_host && loglik_out) ? reinterpret_cast<double*>(W + plan.o_ll) : loglik_out;
     HIP_TRY((hipError_t)mi::dwaic::waic_run(plan, x, mat, y, W, ll, st));
     const hipMemcpyKind back = slab_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (lppd_out) HIP_TRY(hipMemcpyAsync(lppd_out, W + plan.o_lppd, n_rows * 8, back, st));

@@ -3,20 +3,18 @@
 // (k / C) d C + (k % C) and its row stride is C, for every column -- so a tile of columns may span several t.
 //
 //   logk_elem_kernel<KIND>      ISO / DIAG / NORMAL_MODEL: one lane per column, coalesced along c, any d; the four strided chains of dot4 in four registers.
-//   logk_pack_kernel            DENSE / LOGISTIC, once per call: the matrix (P: d x d, X: n_rows x d, row-major as given) TRANSPOSED and zero-padded into
-//                               At [Kp][ldA] -- At[j][i] = M[i][j]: a row of At holds, for one contraction index j, the 128 output rows of a tile contiguously.
+//   dprod::pack_kernel          DENSE / LOGISTIC, once per call: the matrix (P: d x d, X: n_rows x d, row-major as given) TRANSPOSED and zero-padded into
+//                               At [Kp][ldA] (draws_product.hpp; draws_waic.hip packs its X through the same launcher, defined here).
 //   logk_product_kernel<TGT>    the fused product and reduction.  A workgroup of four waves owns 128 columns, a wave 32 of them (two 16-column tiles of
 //                               v_mfma_f64_16x16x4_f64) for ALL rows: it walks the row tiles of 128 rows ascending, 16 accumulators (8 row blocks x 2 column
-//                               tiles) per row tile, the contraction in steps of 16 through a double-buffered LDS stage: At's 16 rows by direct-to-LDS loads
-//                               (global_load_lds_dwordx4, as gemm_step_kernel stages them), the columns' 16 rows through registers -- one column per thread with
-//                               its own base and the common stride C, 8-byte loads (a row of the slab is 16-byte aligned only for an even C), TRUE zeros
-//                               beyond d (0 * inf in a padded slot would poison the column); a column beyond K reads the slab's first column instead of a
-//                               wild base and is never folded into anything or stored -- both issued one step ahead.  Element (i, k) of the product is ONE fma chain over j ascending (the k-steps
-//                               of an MFMA and the loop both ascend): w_i of the definition, or eta_r.  It never reaches memory: the C/D map of the instruction,
+//                               tiles) per row tile, the contraction in steps of 16 through a double-buffered LDS stage, staged as draws_product.hpp
+//                               states (a wave moves 4 of At's 16 rows, a thread 8 of its column's), one step ahead.  Element (i, k) of the product is ONE
+//                               fma chain over j ascending (the k-steps of an MFMA and the loop both ascend): w_i of the definition, or eta_r.  It never
+//                               reaches memory: the C/D map of the instruction,
 //                               col = lane & 15, row = (lane >> 4) + 4 reg, gives lane group g = lane >> 4 exactly the rows i = g (mod 4) -- chain g of dot4 /
 //                               sum4 -- so after a row tile every lane folds its rows, ascending, into one q per column:
 //                                   DENSE     q = fma(x_i, w_i, q)                     (x_i re-read from the slab: the workgroup has just streamed it)
-//                                   LOGISTIC  q = q + (y_r eta_r - softplus(eta_r))    (softplus: gemm_rowterm_kernel's two branches, det_math.hpp)
+//                                   LOGISTIC  q = q + (y_r eta_r - softplus(eta_r))    (dprod::logit_term)
 //                               rows beyond d / n_rows are SKIPPED, not added as zeros (a padded logistic row would add -log 2, and fma(0, 0, -0) is +0).
 //                               The fold runs as a rolled loop over the 8 row blocks that rotates the accumulators down by one block per turn (register
 //                               moves, ~1 % of a row tile's matrix time), so the 64 row terms of a lane share 8 inlined copies of exp / log.  At the end
@@ -30,15 +28,34 @@
 #include <algorithm>
 
 namespace mi {
+namespace dprod {
+
+namespace {
+__global__ __launch_bounds__(256) void pack_kernel(const double* __restrict__ M, uint64_t rows, uint64_t cols, uint64_t Kp, uint64_t ld, double* __restrict__ At)
+{
+    const uint64_t n = Kp * ld;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
+        const uint64_t j = e / ld, i = e % ld;
+        At[e] = (i < rows && j < cols) ? M[i * cols + j] : 0.0;
+    }
+}
+}  // namespace
+
+int pack_transposed(const double* M, uint64_t rows, uint64_t cols, uint64_t Kp, uint64_t ld, uint64_t grid, double* At, hipStream_t st)
+{
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)grid), dim3(256), 0, st, M, rows, cols, Kp, ld, At);
+    return (int)hipGetLastError();
+}
+
+}  // namespace dprod
+
 namespace dlogk {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-constexpr double LOGK_LOG_2PI = 1.83787706640934548356;      // MCMC_LOG_2PI (settings_host.hpp)
-constexpr int STAGE = 2 * (int)LOGK_TK * (int)LOGK_LDS_STRIDE;      // doubles per stage: rows 0..15 of At's tile, rows 16..31 the columns
+using dprod::LDS_STRIDE;
+using dprod::STAGE;
+using dprod::align256;
+using dprod::double4_t;
 enum : int { TGT_DENSE = 0, TGT_LOGISTIC = 1 };
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 LogkPlan logk_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t C, bool slab_host, bool target_host)
 {
@@ -52,10 +69,10 @@ LogkPlan logk_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
     size_t pack = 0;
     if (p.route == LOGK_ROUTE_PRODUCT) {
         const uint64_t rows = kind == LOGK_DENSE ? d : n_rows;
-        p.Kp = LOGK_TK * ((d + LOGK_TK - 1) / LOGK_TK);
-        p.ldA = LOGK_TM * ((rows + LOGK_TM - 1) / LOGK_TM);
-        p.n_row_tiles = p.ldA / LOGK_TM;
-        p.grid = (p.K + LOGK_TN - 1) / LOGK_TN;
+        p.Kp = TK * ((d + TK - 1) / TK);
+        p.ldA = TM * ((rows + TM - 1) / TM);
+        p.n_row_tiles = p.ldA / TM;
+        p.grid = (p.K + TN - 1) / TN;
         p.pack_grid = std::min<uint64_t>((p.Kp * p.ldA + 255) / 256, 1u << 16);
         p.lds_bytes = LOGK_LDS_BYTES;
         pack = (size_t)(p.Kp * p.ldA) * sizeof(double);
@@ -104,7 +121,7 @@ __global__ __launch_bounds__(256) void logk_elem_kernel(const double* __restrict
             m2 = dfma(e, e, m2);
         }
         const double s2 = sigma * sigma;
-        out[k] = -(n * (0.5 * LOGK_LOG_2PI + det_log(sigma))) - m2 / (2.0 * s2);
+        out[k] = -(n * (0.5 * dprod::LOG_2PI + det_log(sigma))) - m2 / (2.0 * s2);
     } else {
         auto w_of = [&](uint64_t i, double xv) -> double { return KIND == LOGK_DIAG ? prec[i] * xv : xv; };
         double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
@@ -120,16 +137,6 @@ __global__ __launch_bounds__(256) void logk_elem_kernel(const double* __restrict
         if (i + 1 < d) { const double xv = col[(i + 1) * C]; q1 = dfma(xv, w_of(i + 1, xv), q1); }
         if (i + 2 < d) { const double xv = col[(i + 2) * C]; q2 = dfma(xv, w_of(i + 2, xv), q2); }
         out[k] = -0.5 * ((q0 + q2) + (q1 + q3));
-    }
-}
-
-// M (rows x cols, row-major) -> At[j * ldA + i] = M[i][j] for j < Kp, i < ldA, zeros outside the matrix
-__global__ __launch_bounds__(256) void logk_pack_kernel(const double* __restrict__ M, uint64_t rows, uint64_t cols, uint64_t Kp, uint64_t ldA, double* __restrict__ At)
-{
-    const uint64_t n = Kp * ldA;
-    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
-        const uint64_t j = e / ldA, i = e % ldA;
-        At[e] = (i < rows && j < cols) ? M[i * cols + j] : 0.0;
     }
 }
 
@@ -152,7 +159,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void logk_product_kernel(con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane >> 4, c16 = lane & 15;
     const uint64_t d = prm.d, C = prm.C, K = prm.K;
-    const uint64_t n0 = (uint64_t)blockIdx.x * LOGK_TN;
+    const uint64_t n0 = (uint64_t)blockIdx.x * TN;
     // the column this thread stages (rows 8 s_half .. 8 s_half + 7 of every step), and the two columns whose results it holds
     const int s_c = tid & 127, s_half = tid >> 7;
     const uint64_t s_k = n0 + (uint64_t)s_c;
@@ -169,48 +176,14 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void logk_product_kernel(con
     }
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)lds;
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    // wave w moves rows w, w + 4, w + 8, w + 12 of At's 16 staged rows, 1 KiB each (inside At for every kb < nkb, mt < n_row_tiles)
+    const uint32_t d32 = (uint32_t)d;
+    // the staging of draws_product.hpp: four waves share At's 16 rows, a thread moves 8 rows of its column
     auto issue_a = [&](uint32_t kb, uint32_t mt, int stage) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = wave + 4 * i;
-            const double* src = prm.At + ((uint64_t)(kb * LOGK_TK + r) * prm.ldA + (uint64_t)mt * LOGK_TM);
-            const uint32_t dst = lds_base + (uint32_t)((stage * STAGE + r * (int)LOGK_LDS_STRIDE) * 8);
-            uint32_t m0_saved;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_saved) : "v"(lane16), "s"(dst), "s"(src) : "memory");
-        }
+        dprod::issue_a<4>(prm.At, prm.ldA, kb * TK, (uint64_t)mt * TM, lds_base, stage, wave, lane16);
     };
-    // (d <= 65 536 and C < 2^32: 32-bit factors.)  The loads are unconditional -- no branch per element, and the direct-to-LDS loads issued right behind them
-    // keep them where they are: a step whose 16 rows all exist (a uniform test) takes them as they are; the ragged last step of a row tile loads row
-    // min(j, d - 1) and, on the way to LDS a step later, REPLACES what lies beyond d by a true zero, whatever was loaded.  A column beyond K is read
-    // from the slab's first column, a place that exists; its product is garbage that nothing folds or stores (an MFMA column touches no other column)
-    const uint32_t d32 = (uint32_t)d, C32 = (uint32_t)C;
-    auto load_b = [&](uint32_t kb, double (&v)[8]) __attribute__((always_inline)) {
-        const uint32_t j0 = kb * LOGK_TK + (uint32_t)(8 * s_half);
-        if (kb * LOGK_TK + LOGK_TK <= d32) {
-            const double* bp = s_col + (uint64_t)j0 * (uint64_t)C32;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = bp[(uint64_t)u * C];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const uint32_t jj = j0 + (uint32_t)u;
-                const uint32_t jc = jj < d32 ? jj : d32 - 1u;
-                v[u] = s_col[(uint64_t)jc * (uint64_t)C32];
-            }
-        }
-    };
+    auto load_b = [&](uint32_t kb, double (&v)[8]) __attribute__((always_inline)) { dprod::load_b<8>(s_col, kb, s_half, d32, C, v); };
     auto store_b = [&](uint32_t kb, int stage, const double (&v)[8]) __attribute__((always_inline)) {
-        double* dst = lds + stage * STAGE + ((int)LOGK_TK + 8 * s_half) * (int)LOGK_LDS_STRIDE + s_c;
-        if (kb * LOGK_TK + LOGK_TK <= d32) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) dst[u * (int)LOGK_LDS_STRIDE] = v[u];
-        } else {
-            const uint32_t j0 = kb * LOGK_TK + (uint32_t)(8 * s_half);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) dst[u * (int)LOGK_LDS_STRIDE] = (j0 + (uint32_t)u < d32) ? v[u] : 0.0;
-        }
+        dprod::store_b<8>(lds + stage * STAGE, kb, s_half, s_c, d32, v);
     };
 
     double4_t acc[8][2];
@@ -235,25 +208,12 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void logk_product_kernel(con
         if (kb1 == nkb) { kb1 = 0; mt1 = mt + 1; }
         const bool more = s + 1 < total;
         if (more) { load_b(kb1, bv); issue_a(kb1, mt1, stage ^ 1); }      // the columns first: what the compiler waits for before it reuses bv is already there
-        const double* As = lds + stage * STAGE + j * (int)LOGK_LDS_STRIDE + c16;
-        const double* Bs = lds + stage * STAGE + ((int)LOGK_TK + j) * (int)LOGK_LDS_STRIDE + 32 * wave + c16;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            double a[8], b[2];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) a[t] = As[4 * kk * (int)LOGK_LDS_STRIDE + 16 * t];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) b[t] = Bs[4 * kk * (int)LOGK_LDS_STRIDE + 16 * t];
-#pragma unroll
-            for (int ti = 0; ti < 8; ++ti)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) acc[ti][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[ni], acc[ti][ni], 0, 0, 0);
-        }
+        dprod::mfma_step<8>(lds + stage * STAGE + j * (int)LDS_STRIDE + c16, lds + stage * STAGE + ((int)TK + j) * (int)LDS_STRIDE + 32 * wave + c16, acc);
         if (more) store_b(kb1, stage ^ 1, bv);
         if (kb == nkb - 1) {
             // the row tile is complete: acc[ti][ni][r] is element (row 128 mt + 16 ti + 4 r + j, column e_k[ni]).  Fold block 0, rotate, eight times:
             // the rows of a lane ascend (r inside a block, then the blocks), and the accumulators come out as zeros for the next row tile
-            const uint64_t m0 = (uint64_t)mt * LOGK_TM;
+            const uint64_t m0 = (uint64_t)mt * TM;
 #pragma unroll 1
             for (int it = 0; it < 8; ++it) {
                 const uint64_t rb = m0 + (uint64_t)(16 * it);
@@ -273,12 +233,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void logk_product_kernel(con
                             const double yv = rok ? prm.y[row] : 0.0;
 #pragma unroll
                             for (int ni = 0; ni < 2; ++ni) {
-                                const double eta = acc[0][ni][r];
-                                const double ex = det_exp(eta > 0.0 ? -eta : eta);
-                                const double l1p = det_log(1.0 + ex);
-                                const double sp = (eta > 0.0) ? (eta + l1p) : l1p;
-                                const double term = yv * eta - sp;
-                                const double f = q[ni] + term;
+                                const double f = q[ni] + dprod::logit_term(yv, acc[0][ni][r]);
                                 q[ni] = rok ? f : q[ni];
                             }
                         }
@@ -336,9 +291,8 @@ int logk_run(const LogkPlan& p, const double* x, const double* mat, const double
     }
     double* At = reinterpret_cast<double*>(static_cast<char*>(ws) + p.o_pack);
     const uint64_t rows = p.kind == LOGK_DENSE ? p.d : p.n_rows;
-    hipLaunchKernelGGL(logk_pack_kernel, dim3((unsigned)p.pack_grid), dim3(256), 0, st, mat, rows, p.d, p.Kp, p.ldA, At);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    const int e = dprod::pack_transposed(mat, rows, p.d, p.Kp, p.ldA, p.pack_grid, At, st);
+    if (e) return e;
     ProdParams prm;
     prm.At = At;
     prm.x = x;
@@ -349,7 +303,7 @@ int logk_run(const LogkPlan& p, const double* x, const double* mat, const double
     prm.K = p.K;
     prm.rows = rows;
     prm.ldA = p.ldA;
-    prm.nkb = (uint32_t)(p.Kp / LOGK_TK);
+    prm.nkb = (uint32_t)(p.Kp / TK);
     prm.n_row_tiles = (uint32_t)p.n_row_tiles;
     return p.kind == LOGK_DENSE ? launch_product<TGT_DENSE>(p, prm, st) : launch_product<TGT_LOGISTIC>(p, prm, st);
 }

@@ -1,22 +1,19 @@
-// draws_logk.hpp -- interface of the log-kernel reducer of a draws slab (draws_logk.hip; the C entry is mi_mcmc_draws_log_kernel in mi_mcmc.hip, where
+// draws_logk.hpp -- interface of the log-kernel reducer of a draws slab (draws_logk.hip; the C entry is mi_mcmc_draws_log_kernel in draws_api.hip, where
 // the stream's cached workspace lives): out[t][c] = log K(x[t][:][c]) for every column of a slab [n_keep][d][C].  The arithmetic is stated in
 // include/mi_mcmc.h and has ONE order for every shape, so the plan below decides time and memory only, never a bit of the result; it is a function of
 // (kind, d, n_rows, n_keep, C) and of where the slab and the target live (what is staged) alone.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <cstddef>
-#include <cstdint>
+#include "draws_product.hpp"
 
 namespace mi {
 namespace dlogk {
 
+using dprod::TM;              // the tiles of the product (draws_product.hpp): a workgroup owns TN = 128 columns, 32 per wave, for ALL rows
+using dprod::TN;
+using dprod::TK;
 constexpr uint64_t LOGK_MAX_D = 65536;
-constexpr uint32_t LOGK_TM = 128;                      // output rows (dimensions i / data rows r) of a tile of the product
-constexpr uint32_t LOGK_TN = 128;                      // columns of a workgroup: 32 per wave, owned for ALL rows
-constexpr uint32_t LOGK_TK = 16;                       // contraction entries per staged step
-constexpr uint32_t LOGK_LDS_STRIDE = 144;              // doubles per staged row (gemm_samplers.hip: the two 16-lane groups of a fragment read on disjoint bank halves)
-constexpr size_t LOGK_LDS_BYTES = (size_t)2 * 2 * LOGK_TK * LOGK_LDS_STRIDE * sizeof(double);      // two stages of 16 matrix rows and 16 column rows
+constexpr size_t LOGK_LDS_BYTES = (size_t)2 * dprod::STAGE * sizeof(double);      // two stages of 16 matrix rows and 16 column rows
 
 // the kinds are mi_target_kind's values
 enum : int { LOGK_ISO = 1, LOGK_DIAG = 2, LOGK_DENSE = 3, LOGK_LOGISTIC = 4, LOGK_NORMAL_MODEL = 5 };

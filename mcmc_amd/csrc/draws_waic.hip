@@ -2,17 +2,16 @@
 // (mi_mcmc_draws_waic; include/mi_mcmc.h states the arithmetic and its order, draws_waic.hpp the plan).  The samples are the K = n_keep * C columns
 // k = t * C + c of a slab [n_keep][d][C], as in draws_logk.hip; they are cut into chunks of 2048.
 //
-//   logk_pack_kernel's twin     LOGISTIC, once per call: X TRANSPOSED and zero-padded into At [Kp][ldR] (draws_logk.hip).
+//   dprod::pack_kernel          LOGISTIC, once per call: X TRANSPOSED and zero-padded into At [Kp][ldR] (draws_product.hpp's launcher, in draws_logk.hip).
 //   waic_shift_kernel           LOGISTIC: the shift of every (chunk, row), ll[r][first column of the chunk], one thread each, the plain fma chain.
 //   waic_product_kernel         LOGISTIC.  draws_logk.hip's product with the loop nest turned around: a workgroup of EIGHT waves owns one 128-row tile
 //                               of X and one chunk of columns, and walks the chunk's column tiles of 128 ascending.  Wave (h, wc) = (wave >> 2, wave & 3)
 //                               holds rows 64 h .. 64 h + 63 of the tile and columns 32 wc .. 32 wc + 31 of the column tile: 8 accumulators (4 row blocks
 //                               x 2 column tiles of v_mfma_f64_16x16x4_f64), HALF of what a wave of draws_logk.hip holds, so that the running sums of
-//                               16 rows x (A, S1, S2) = 96 VGPRs fit next to them at two waves per SIMD.  The staging is draws_logk.hip's: At's 16 rows by
-//                               direct-to-LDS loads, the columns through registers with true zeros beyond d, a column beyond K read from the slab's first
-//                               column and never folded or stored.  After a column tile every lane folds the 16 rows x 2 columns it holds (C/D map:
+//                               16 rows x (A, S1, S2) = 96 VGPRs fit next to them at two waves per SIMD.  The staging is draws_product.hpp's (a wave moves
+//                               2 of At's 16 rows, a thread 4 of its column's).  After a column tile every lane folds the 16 rows x 2 columns it holds (C/D map:
 //                               col = lane & 15, row = (lane >> 4) + 4 reg) into ITS OWN sums of those rows -- nothing crosses lanes inside the loop:
-//                                   ll = y_r eta - softplus(eta);  v = ll - shift;  S1 += v;  S2 += v * v;  A += exp(ll)
+//                                   ll = dprod::logit_term(y_r, eta);  v = ll - shift;  S1 += v;  S2 += v * v;  A += exp(ll)
 //                               and stores ll (8 bytes, 16 lanes contiguous along c) where the matrix is asked for.  The fold is a rolled loop over the
 //                               4 row blocks that rotates the accumulators down (zeros come in) and the sums around (after 4 turns they are back).
 //                               At the end of the chunk the 16 column lanes meet by __shfl_xor 8, 4, 2, 1 and the four column waves through LDS as
@@ -29,13 +28,12 @@
 namespace mi {
 namespace dwaic {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-constexpr double WAIC_LOG_2PI = 1.83787706640934548356;      // MCMC_LOG_2PI (settings_host.hpp)
-constexpr int STAGE = 2 * (int)WAIC_TK * (int)WAIC_LDS_STRIDE;      // doubles per stage: rows 0..15 of At's tile, rows 16..31 the columns
+using dprod::LDS_STRIDE;
+using dprod::STAGE;
+using dprod::align256;
+using dprod::double4_t;
+using dprod::logit_term;
 constexpr int YSH = 2 * STAGE;                                     // y [128], shift [128] behind the two stages
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 WaicPlan waic_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t C, bool slab_host, bool target_host, bool want_loglik)
 {
@@ -47,12 +45,12 @@ WaicPlan waic_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
     p.K = n_keep * C;
     p.route = kind == WAIC_LOGISTIC ? WAIC_ROUTE_PRODUCT : WAIC_ROUTE_ELEMENTWISE;
     p.n_chunks = (p.K + WAIC_CHUNK - 1) / WAIC_CHUNK;
-    p.ldR = WAIC_TM * ((n_rows + WAIC_TM - 1) / WAIC_TM);
+    p.ldR = TM * ((n_rows + TM - 1) / TM);
     p.merge_grid = (n_rows + 255) / 256;
     size_t pack = 0;
     if (p.route == WAIC_ROUTE_PRODUCT) {
-        p.Kp = WAIC_TK * ((d + WAIC_TK - 1) / WAIC_TK);
-        p.n_row_tiles = p.ldR / WAIC_TM;
+        p.Kp = TK * ((d + TK - 1) / TK);
+        p.n_row_tiles = p.ldR / TM;
         p.grid = p.n_chunks * p.n_row_tiles;
         p.block = 512;
         p.pack_grid = std::min<uint64_t>((p.Kp * p.ldR + 255) / 256, 1u << 16);
@@ -78,25 +76,6 @@ WaicPlan waic_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
 
 namespace {
 
-// M (rows x cols, row-major) -> At[j * ldA + i] = M[i][j] for j < Kp, i < ldA, zeros outside the matrix (draws_logk.hip's pack)
-__global__ __launch_bounds__(256) void waic_pack_kernel(const double* __restrict__ M, uint64_t rows, uint64_t cols, uint64_t Kp, uint64_t ldA, double* __restrict__ At)
-{
-    const uint64_t n = Kp * ldA;
-    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
-        const uint64_t j = e / ldA, i = e % ldA;
-        At[e] = (i < rows && j < cols) ? M[i * cols + j] : 0.0;
-    }
-}
-
-// term_r of the logistic definition (draws_logk.hip's fold, the same expressions)
-__device__ __forceinline__ double logit_ll(double yv, double eta)
-{
-    const double ex = det_exp(eta > 0.0 ? -eta : eta);
-    const double l1p = det_log(1.0 + ex);
-    const double sp = (eta > 0.0) ? (eta + l1p) : l1p;
-    return yv * eta - sp;
-}
-
 // part[(ch * 4 + 0) * ldR + r] = ll[r][2048 ch]: eta is the fma chain over j ascending from +0, the chain an MFMA accumulator runs
 __global__ __launch_bounds__(256) void waic_shift_kernel(const double* __restrict__ At, const double* __restrict__ x, const double* __restrict__ y, uint64_t d, uint64_t C,
                                                          uint64_t rows, uint64_t ldR, uint64_t row_blocks, double* __restrict__ part)
@@ -107,7 +86,7 @@ __global__ __launch_bounds__(256) void waic_shift_kernel(const double* __restric
     const double* col = x + (k0 / C) * d * C + (k0 % C);
     double eta = 0.0;
     for (uint64_t j = 0; j < d; ++j) eta = dfma(At[j * ldR + r], col[j * C], eta);
-    part[(ch * 4) * ldR + r] = logit_ll(y[r], eta);
+    part[(ch * 4) * ldR + r] = logit_term(y[r], eta);
 }
 
 struct ProdParams {
@@ -143,63 +122,31 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const 
     const uint64_t ch = blockIdx.x / prm.n_row_tiles;
     const uint64_t c0 = ch * WAIC_CHUNK;
     const uint64_t cend = (K - c0 < WAIC_CHUNK) ? K : c0 + WAIC_CHUNK;
-    const uint32_t n_ct = (uint32_t)((cend - c0 + WAIC_TN - 1) / WAIC_TN);
-    const uint64_t m0 = (uint64_t)mt * WAIC_TM;
+    const uint32_t n_ct = (uint32_t)((cend - c0 + TN - 1) / TN);
+    const uint64_t m0 = (uint64_t)mt * TM;
     // the column this thread stages (rows 4 s_q .. 4 s_q + 3 of every step) in column tile ct; a column beyond K: the slab's first column
     const int s_c = tid & 127, s_q = tid >> 7;
     auto col_of = [&](uint32_t ct) -> const double* {
-        const uint64_t k = c0 + (uint64_t)ct * WAIC_TN + (uint64_t)s_c;
+        const uint64_t k = c0 + (uint64_t)ct * TN + (uint64_t)s_c;
         return prm.x + (k < K ? (k / C) * d * C + (k % C) : 0);
     };
     const double* s_col = col_of(0);
-    if (tid < (int)WAIC_TM) {
+    if (tid < (int)TM) {
         const uint64_t row = m0 + (uint64_t)tid;
         const bool rok = row < prm.rows;
         lds[YSH + tid] = rok ? prm.y[row] : 0.0;
-        lds[YSH + (int)WAIC_TM + tid] = rok ? prm.part[(ch * 4) * prm.ldR + row] : 0.0;
+        lds[YSH + (int)TM + tid] = rok ? prm.part[(ch * 4) * prm.ldR + row] : 0.0;
     }
     const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double*)lds;
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    // wave w moves rows w and w + 8 of At's 16 staged rows, 1 KiB each (inside At for every kb < nkb, mt < n_row_tiles)
+    const uint32_t d32 = (uint32_t)d;
+    // the staging of draws_product.hpp: eight waves share At's 16 rows, a thread moves 4 rows of its column
     auto issue_a = [&](uint32_t kb, int stage) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = wave + 8 * i;
-            const double* src = prm.At + ((uint64_t)(kb * WAIC_TK + r) * prm.ldR + m0);
-            const uint32_t dst = lds_base + (uint32_t)((stage * STAGE + r * (int)WAIC_LDS_STRIDE) * 8);
-            uint32_t m0_saved;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_saved) : "v"(lane16), "s"(dst), "s"(src) : "memory");
-        }
+        dprod::issue_a<8>(prm.At, prm.ldR, kb * TK, m0, lds_base, stage, wave, lane16);
     };
-    // (draws_logk.hip's column staging, four rows per thread: unconditional loads, row min(j, d - 1) in the ragged last step, true zeros beyond d on the
-    // way to LDS)
-    const uint32_t d32 = (uint32_t)d, C32 = (uint32_t)C;
-    auto load_b = [&](uint32_t kb, double (&v)[4]) __attribute__((always_inline)) {
-        const uint32_t j0 = kb * WAIC_TK + (uint32_t)(4 * s_q);
-        if (kb * WAIC_TK + WAIC_TK <= d32) {
-            const double* bp = s_col + (uint64_t)j0 * (uint64_t)C32;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = bp[(uint64_t)u * C];
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t jj = j0 + (uint32_t)u;
-                const uint32_t jc = jj < d32 ? jj : d32 - 1u;
-                v[u] = s_col[(uint64_t)jc * (uint64_t)C32];
-            }
-        }
-    };
+    auto load_b = [&](uint32_t kb, double (&v)[4]) __attribute__((always_inline)) { dprod::load_b<4>(s_col, kb, s_q, d32, C, v); };
     auto store_b = [&](uint32_t kb, int stage, const double (&v)[4]) __attribute__((always_inline)) {
-        double* dst = lds + stage * STAGE + ((int)WAIC_TK + 4 * s_q) * (int)WAIC_LDS_STRIDE + s_c;
-        if (kb * WAIC_TK + WAIC_TK <= d32) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dst[u * (int)WAIC_LDS_STRIDE] = v[u];
-        } else {
-            const uint32_t j0 = kb * WAIC_TK + (uint32_t)(4 * s_q);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) dst[u * (int)WAIC_LDS_STRIDE] = (j0 + (uint32_t)u < d32) ? v[u] : 0.0;
-        }
+        dprod::store_b<4>(lds + stage * STAGE, kb, s_q, s_c, d32, v);
     };
 
     double4_t acc[4][2];
@@ -233,20 +180,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const 
             load_b(kb1, bv);
             issue_a(kb1, stage ^ 1);
         }
-        const double* As = lds + stage * STAGE + j * (int)WAIC_LDS_STRIDE + 64 * h + c16;
-        const double* Bs = lds + stage * STAGE + ((int)WAIC_TK + j) * (int)WAIC_LDS_STRIDE + 32 * wc + c16;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            double a[4], b[2];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) a[t] = As[4 * kk * (int)WAIC_LDS_STRIDE + 16 * t];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) b[t] = Bs[4 * kk * (int)WAIC_LDS_STRIDE + 16 * t];
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) acc[ti][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[ni], acc[ti][ni], 0, 0, 0);
-        }
+        dprod::mfma_step<4>(lds + stage * STAGE + j * (int)LDS_STRIDE + 64 * h + c16, lds + stage * STAGE + ((int)TK + j) * (int)LDS_STRIDE + 32 * wc + c16, acc);
         if (more) store_b(kb1, stage ^ 1, bv);
         if (kb == nkb - 1) {
             // the column tile is complete: acc[ti][ni][r] is element (row m0 + 64 h + 16 ti + 4 r + j, column e_k[ni]).  Fold block 0, rotate, four times
@@ -254,7 +188,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const 
             bool e_ok[2];
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
-                e_k[ni] = c0 + (uint64_t)ct * WAIC_TN + (uint64_t)(32 * wc + 16 * ni + c16);
+                e_k[ni] = c0 + (uint64_t)ct * TN + (uint64_t)(32 * wc + 16 * ni + c16);
                 e_ok[ni] = e_k[ni] < K;
             }
 #pragma unroll 1
@@ -266,10 +200,10 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const 
                         const int rl = rl0 + 4 * r + j;
                         const uint64_t row = m0 + (uint64_t)rl;
                         const bool rok = row < prm.rows;
-                        const double yv = lds[YSH + rl], sh = lds[YSH + (int)WAIC_TM + rl];
+                        const double yv = lds[YSH + rl], sh = lds[YSH + (int)TM + rl];
 #pragma unroll
                         for (int ni = 0; ni < 2; ++ni) {
-                            const double ll = logit_ll(yv, acc[0][ni][r]);
+                            const double ll = logit_term(yv, acc[0][ni][r]);
                             const double v = ll - sh;
                             const double vv = v * v;
                             const double ex = det_exp(ll);
@@ -310,19 +244,19 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const 
             const double tA = tree16(sA[a][r]), t1 = tree16(s1[a][r]), t2 = tree16(s2[a][r]);
             const int rl = 64 * h + 16 * a + 4 * r + j;
             if (c16 == 0) {
-                red[(wc * 3 + 0) * (int)WAIC_TM + rl] = tA;
-                red[(wc * 3 + 1) * (int)WAIC_TM + rl] = t1;
-                red[(wc * 3 + 2) * (int)WAIC_TM + rl] = t2;
+                red[(wc * 3 + 0) * (int)TM + rl] = tA;
+                red[(wc * 3 + 1) * (int)TM + rl] = t1;
+                red[(wc * 3 + 2) * (int)TM + rl] = t2;
             }
         }
     __syncthreads();
-    if (tid < (int)WAIC_TM) {
+    if (tid < (int)TM) {
         const uint64_t row = m0 + (uint64_t)tid;
         if (row < prm.rows) {
 #pragma unroll
             for (int st = 0; st < 3; ++st) {
-                const double w0 = red[(0 * 3 + st) * (int)WAIC_TM + tid], w1 = red[(1 * 3 + st) * (int)WAIC_TM + tid];
-                const double w2 = red[(2 * 3 + st) * (int)WAIC_TM + tid], w3 = red[(3 * 3 + st) * (int)WAIC_TM + tid];
+                const double w0 = red[(0 * 3 + st) * (int)TM + tid], w1 = red[(1 * 3 + st) * (int)TM + tid];
+                const double w2 = red[(2 * 3 + st) * (int)TM + tid], w3 = red[(3 * 3 + st) * (int)TM + tid];
                 prm.part[(ch * 4 + 1 + (uint64_t)st) * prm.ldR + row] = (w0 + w1) + (w2 + w3);
             }
         }
@@ -348,7 +282,7 @@ __global__ __launch_bounds__(256) void waic_elem_kernel(const double* __restrict
     {
         const double* col = x + (c0 / C) * 2 * C + (c0 % C);
         const double mu = col[0], sigma = col[C];
-        const double base = -(0.5 * WAIC_LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
+        const double base = -(0.5 * dprod::LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint64_t row = row0 + (uint64_t)(j + 4 * i);
@@ -358,13 +292,13 @@ __global__ __launch_bounds__(256) void waic_elem_kernel(const double* __restrict
         }
     }
     // the slot's columns ascending: offsets 32 wc + c16 and + 16 of every column tile of 128
-    const uint32_t n_half = 2 * (uint32_t)((cend - c0 + WAIC_TN - 1) / WAIC_TN);
+    const uint32_t n_half = 2 * (uint32_t)((cend - c0 + TN - 1) / TN);
     for (uint32_t q = 0; q < n_half; ++q) {
-        const uint64_t k = c0 + (uint64_t)(q >> 1) * WAIC_TN + (uint64_t)(32 * wc + 16 * (int)(q & 1u) + c16);
+        const uint64_t k = c0 + (uint64_t)(q >> 1) * TN + (uint64_t)(32 * wc + 16 * (int)(q & 1u) + c16);
         if (k >= cend) continue;
         const double* col = x + (k / C) * 2 * C + (k % C);
         const double mu = col[0], sigma = col[C];
-        const double base = -(0.5 * WAIC_LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
+        const double base = -(0.5 * dprod::LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint64_t row = row0 + (uint64_t)(j + 4 * i);
@@ -393,7 +327,7 @@ __global__ __launch_bounds__(256) void waic_elem_kernel(const double* __restrict
             // the shift of (chunk, row), as every thread of the row formed it above, for the merge
             const double* col = x + (c0 / C) * 2 * C + (c0 % C);
             const double mu = col[0], sigma = col[C];
-            const double base = -(0.5 * WAIC_LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
+            const double base = -(0.5 * dprod::LOG_2PI + det_log(sigma)), den = 2.0 * (sigma * sigma);
             part[(ch * 4) * ldR + row] = ll_of(y[row], mu, base, den);
 #pragma unroll
             for (int st = 0; st < 3; ++st) {
@@ -445,8 +379,8 @@ int waic_run(const WaicPlan& p, const double* x, const double* mat, const double
     hipError_t e;
     if (p.route == WAIC_ROUTE_PRODUCT) {
         double* At = reinterpret_cast<double*>(W + p.o_pack);
-        hipLaunchKernelGGL(waic_pack_kernel, dim3((unsigned)p.pack_grid), dim3(256), 0, st, mat, p.n_rows, p.d, p.Kp, p.ldR, At);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+        const int pe = dprod::pack_transposed(mat, p.n_rows, p.d, p.Kp, p.ldR, p.pack_grid, At, st);
+        if (pe) return pe;
         // (n_chunks * ceil(n_rows / 256) <= the product kernel's grid, which the entry point keeps below 2^31)
         hipLaunchKernelGGL(waic_shift_kernel, dim3((unsigned)(p.n_chunks * p.merge_grid)), dim3(256), 0, st, At, x, y, p.d, p.C, p.n_rows, p.ldR, p.merge_grid, part);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
@@ -461,7 +395,7 @@ int waic_run(const WaicPlan& p, const double* x, const double* mat, const double
         prm.K = p.K;
         prm.rows = p.n_rows;
         prm.ldR = p.ldR;
-        prm.nkb = (uint32_t)(p.Kp / WAIC_TK);
+        prm.nkb = (uint32_t)(p.Kp / TK);
         prm.n_row_tiles = (uint32_t)p.n_row_tiles;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(waic_product_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
         if (e != hipSuccess) return (int)e;

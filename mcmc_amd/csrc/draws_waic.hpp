@@ -5,29 +5,26 @@
 // function of (kind, d, n_rows, n_keep, C), of where the slab and the target live and of whether the matrix ll is asked for, alone.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <cstddef>
-#include <cstdint>
+#include "draws_product.hpp"
 
 namespace mi {
 namespace dwaic {
 
+using dprod::TM;              // the tiles of the product (draws_product.hpp): a row tile of TM = 128 is two halves of 64, a wave holds 64 rows
+using dprod::TN;
+using dprod::TK;
 constexpr uint64_t WAIC_MAX_D = 65536;
 constexpr uint32_t WAIC_CHUNK = 2048;                  // columns of a chunk: the unit of the fold's order, and of a partial
-constexpr uint32_t WAIC_TM = 128;                      // rows of a tile of the product (two halves of 64: a wave holds 64 rows)
-constexpr uint32_t WAIC_TN = 128;                      // columns of a column tile: 32 per wave
-constexpr uint32_t WAIC_TK = 16;                       // contraction entries per staged step
 constexpr uint32_t WAIC_SLOTS = 64;                    // running sums per (chunk, row): slot(o) = 16 ((o mod 128) div 32) + o mod 16 of column offset o
 constexpr uint32_t WAIC_NORMAL_ROWS = 16;              // rows of a workgroup of the elementwise route
-constexpr uint32_t WAIC_LDS_STRIDE = 144;              // doubles per staged row (draws_logk.hpp)
-constexpr size_t WAIC_LDS_BYTES = (size_t)2 * 2 * WAIC_TK * WAIC_LDS_STRIDE * sizeof(double) + (size_t)2 * WAIC_TM * sizeof(double);      // two stages; y and the shift of the row tile
+constexpr size_t WAIC_LDS_BYTES = (size_t)2 * dprod::STAGE * sizeof(double) + (size_t)2 * TM * sizeof(double);      // two stages; y and the shift of the row tile
 
 // the kinds are mi_target_kind's values
 enum : int { WAIC_LOGISTIC = 4, WAIC_NORMAL_MODEL = 5 };
 enum : int { WAIC_ROUTE_ELEMENTWISE = 0, WAIC_ROUTE_PRODUCT = 1 };
 
 // THE PLAN.  n_chunks = ceil(K / 2048) chunks of columns, ldR = 128 ceil(n_rows / 128) padded rows.
-//   LOGISTIC (product): X packed as draws_logk.hip packs it, [Kp][ldR]; a workgroup of EIGHT waves owns one 128-row tile and one chunk and walks the
+//   LOGISTIC (product): X packed as At [Kp][ldR] (draws_product.hpp); a workgroup of EIGHT waves owns one 128-row tile and one chunk and walks the
 //     chunk's column tiles of 128 ascending, Kp / 16 staged steps each: grid = n_chunks * n_row_tiles (the row tile runs fastest: neighbours share the
 //     chunk's columns), 512 threads, WAIC_LDS_BYTES of LDS.  Before it, one thread per (chunk, row) forms the chunk's shift: grid (ceil(n_rows / 256), n_chunks).
 //   NORMAL_MODEL (elementwise): a workgroup of four waves owns 16 rows and one chunk: grid = n_chunks * ceil(n_rows / 16), 256 threads.

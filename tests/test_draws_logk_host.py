@@ -121,8 +121,8 @@ def _want_plan(kind, d, n_rows, n_keep, C_, slab_host, target_host):
 
 D, L = mcmc_amd.TARGET_GAUSS_DENSE, mcmc_amd.TARGET_LOGISTIC
 # (kind, d, n_rows, n_keep, C): the GPU tests' shapes, then the timing tool's
-PLAN_SHAPES = [(D, 1, 0, 1, 3), (D, 5, 0, 2, 7), (D, 17, 0, 3, 37), (D, 130, 0, 2, 333), (D, 520, 0, 1, 19),
-               (L, 3, 5, 2, 5), (L, 70, 130, 3, 37), (L, 520, 70, 1, 19),
+PLAN_SHAPES = [(D, 1, 0, 1, 3), (D, 5, 0, 2, 7), (D, 17, 0, 3, 37), (D, 130, 0, 2, 333), (D, 520, 0, 1, 19), (D, 32, 0, 2, 7),
+               (L, 3, 5, 2, 5), (L, 70, 130, 3, 37), (L, 520, 70, 1, 19), (L, 32, 16, 2, 5),
                (mcmc_amd.TARGET_GAUSS_ISO, 300, 0, 3, 37), (mcmc_amd.TARGET_GAUSS_DIAG, 300, 0, 3, 37), (mcmc_amd.TARGET_NORMAL_MODEL, 2, 50, 4, 37),
                (D, 128, 0, 100, 65536), (D, 1024, 0, 1, 65536), (L, 512, 1024, 1, 32768)]
 

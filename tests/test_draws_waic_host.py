@@ -126,7 +126,7 @@ def _want_plan(kind, d, n_rows, n_keep, C_, slab_host, target_host, want_loglik)
 
 L, N = mcmc_amd.TARGET_LOGISTIC, mcmc_amd.TARGET_NORMAL_MODEL
 # (kind, d, n_rows, n_keep, C): the GPU tests' shapes, then the measured ones (K = 65 536, and the 6.5 M draws of the issue)
-PLAN_SHAPES = [(L, 3, 5, 2, 5), (L, 70, 130, 3, 37), (L, 520, 70, 1, 19), (L, 5, 9, 3, 1366), (N, 2, 50, 4, 37), (N, 2, 21, 3, 1366),
+PLAN_SHAPES = [(L, 3, 5, 2, 5), (L, 70, 130, 3, 37), (L, 520, 70, 1, 19), (L, 5, 9, 3, 1366), (L, 32, 16, 2, 5), (N, 2, 50, 4, 37), (N, 2, 21, 3, 1366),
                (L, 1024, 4096, 1, 65536), (L, 1024, 4096, 16, 65536), (L, 1024, 4096, 100, 65536)]
 
 

@@ -9,7 +9,9 @@ contraction in steps of 16.  Which shape (n_keep, d, C) reaches what:
            (3, 17, 37)     a ragged contraction (17 = 16 + 1) and row block; K = 111: tiles that span t, a ragged last wave
            (2, 130, 333)   two row tiles (130 = 128 + 2), six workgroups of columns, an odd C: rows of the slab on both 8-byte alignments
            (1, 520, 19)    five row tiles, 33 contraction steps
-  LOGISTIC (2, 3, 5) with 5 rows, (3, 70, 37) with 130 rows (two row tiles, the second with 2 rows), (1, 520, 19) with 70 rows
+           (2, 32, 7)      d a multiple of 16: a contraction of full steps only, no ragged last step
+  LOGISTIC (2, 3, 5) with 5 rows, (3, 70, 37) with 130 rows (two row tiles, the second with 2 rows), (1, 520, 19) with 70 rows,
+           (2, 32, 5) with 16 rows (full steps only)
   ISO, DIAG (3, 300, 37) and NORMAL_MODEL (4, 2, 37) with 50 observations: one lane per column."""
 import functools
 
@@ -22,8 +24,8 @@ from mcmc_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-DENSE_SHAPES = [(1, 1, 3), (2, 5, 7), (3, 17, 37), (2, 130, 333), (1, 520, 19)]
-LOGIT_SHAPES = [((2, 3, 5), 5), ((3, 70, 37), 130), ((1, 520, 19), 70)]
+DENSE_SHAPES = [(1, 1, 3), (2, 5, 7), (3, 17, 37), (2, 130, 333), (1, 520, 19), (2, 32, 7)]
+LOGIT_SHAPES = [((2, 3, 5), 5), ((3, 70, 37), 130), ((1, 520, 19), 70), ((2, 32, 5), 16)]
 _KIND = {"iso": (mcmc_amd.TARGET_GAUSS_ISO, orc.TARGET_ISO), "diag": (mcmc_amd.TARGET_GAUSS_DIAG, orc.TARGET_DIAG),
          "dense": (mcmc_amd.TARGET_GAUSS_DENSE, orc.TARGET_DENSE), "logistic": (mcmc_amd.TARGET_LOGISTIC, orc.TARGET_LOGISTIC),
          "normal": (mcmc_amd.TARGET_NORMAL_MODEL, orc.TARGET_NORMAL_MODEL)}

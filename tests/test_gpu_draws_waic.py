@@ -10,6 +10,7 @@ Which shape (n_keep, d, C) reaches what:
            (3, 70, 37), 130 rows   two row tiles, the second with 2 rows; a ragged contraction; a column tile that spans t; an odd C
            (1, 520, 19), 70 rows   33 contraction steps
            (3, 5, 1366), 9 rows    K = 4098 = 2 * 2048 + 2: three chunks, the last with two columns
+           (2, 32, 5), 16 rows     d a multiple of 16: a contraction of full steps only, no ragged last step
   NORMAL_MODEL (4, 2, 37), 50 rows    K = 148: two column tiles, four row groups of 16, the last with 2 rows
                (3, 2, 1366), 21 rows  three chunks, the last with two columns"""
 import functools
@@ -28,7 +29,8 @@ ORC_MATH = dict(dot=lambda a, b: orc.dot(a, b, 1), exp=lambda x: orc.math_eval(0
                 softplus=lambda x: orc.math_eval(3, x)[0])
 LOGIT_SHAPES = [((2, 3, 5), 5), ((3, 70, 37), 130), ((1, 520, 19), 70), ((3, 5, 1366), 9)]
 NORMAL_SHAPES = [((4, 2, 37), 50), ((3, 2, 1366), 21)]
-CASES = [("logistic", s, r) for s, r in LOGIT_SHAPES] + [("normal", s, r) for s, r in NORMAL_SHAPES]
+FULL_STEPS = ((2, 32, 5), 16)            # d a multiple of 16; behind the others, which the tests below pick by index
+CASES = [("logistic", s, r) for s, r in LOGIT_SHAPES] + [("normal", s, r) for s, r in NORMAL_SHAPES] + [("logistic",) + FULL_STEPS]
 _IDS = [f"{n}-{'x'.join(map(str, s))}-{r}rows" for n, s, r in CASES]
 _KIND = {"logistic": (mcmc_amd.TARGET_LOGISTIC, waic.LOGISTIC), "normal": (mcmc_amd.TARGET_NORMAL_MODEL, waic.NORMAL_MODEL)}
 
