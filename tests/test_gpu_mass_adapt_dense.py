@@ -1,10 +1,14 @@
 """GPU: mi_mcmc_{hmc,mala}_run_mass_adapted_dense -- hmc / mala with a DENSE mass matrix pooled over the chains (NOT a reference mode).
 What is checked: given the reported matrix the run is the oracle's mcmc::hmc bit for bit; the matrix is the header's five steps, transcribed
 in numpy; the whole run is the chain of ordinary calls the header says it is, on every route a dense precond_mat has; a degenerate start runs
-with M = I; and it does what it is for: a ROTATED ill-conditioned Gaussian, which defeats the identity and the diagonal mass alike, mixes."""
+with M = I; and it does what it is for: a ROTATED ill-conditioned Gaussian, which defeats the identity and the diagonal mass alike, mixes.
+Step 1 of the five takes S from mcmc_amd.draws_covariance itself; so that S has a reference of its own, the starting state's S is held bit for bit to
+mcmc_amd/covariance.py, the numpy statement of the header's order, over the oracle's fma chain: the full matrix at d = 24 and d = 130, the corners and
+random elements of each of the 15 tiles at d = 520 (tests/draws_cov_cases.py)."""
 import numpy as np
 import pytest
 
+import draws_cov_cases as cov_cases
 import mcmc_amd
 import orc
 from mcmc_amd import synth
@@ -28,10 +32,15 @@ def _adapted(algo, kind, prec, init, n_windows, burn, keep, L, eps, seed=5):
     return draws, nacc, M, theta
 
 
-def _five_steps(theta):
-    """include/mi_mcmc.h, mi_mcmc_hmc_run_mass_adapted_dense: THE ESTIMATE, from the chains' state [d][C]"""
+def _five_steps(theta, mirror_S=False):
+    """include/mi_mcmc.h, mi_mcmc_hmc_run_mass_adapted_dense: THE ESTIMATE, from the chains' state [d][C]; mirror_S: S is first held to the mirror"""
     d, C = theta.shape
     _, S = mcmc_amd.draws_covariance(theta, want_mean=False)                             # 1.
+    if mirror_S:
+        ref = cov_cases.mirror(theta)
+        assert (ref["cov"] is None) == (d > 400) and (d <= 400 or len(ref["elements"]) >= 5 * len(cov_cases.tiles(d)))
+        cov_cases.assert_is_the_mirror(None, S, ref, ("S of the state", d, C))
+        assert np.array_equal(cov_cases.bits(S), cov_cases.bits(S.T))
     ok = bool(np.isfinite(S).all() and (np.diag(S) > 0.0).all())
     M = None
     if ok:
@@ -44,12 +53,13 @@ def _five_steps(theta):
     return M if ok else np.eye(d)
 
 
-def _by_hand(algo, kind, prec, init, n_windows, burn, keep, L, eps, seed=5):
-    """the same run from draws_covariance -> the five steps -> an ordinary call with that precond_mat, part by part through draw0"""
+def _by_hand(algo, kind, prec, init, n_windows, burn, keep, L, eps, seed=5, mirror_S=False):
+    """the same run from draws_covariance -> the five steps -> an ordinary call with that precond_mat, part by part through draw0
+    (mirror_S: the S of the STARTING state is held to the mirror of the header's order on the way)"""
     state = np.ascontiguousarray(init.T.copy())                                          # [d][C]
     n_parts, done, Ms = n_windows + 1, 0, []
     draws = nacc = None
-    M = _five_steps(state)
+    M = _five_steps(state, mirror_S)
     for part in range(n_parts):
         last = part + 1 == n_parts
         upto = burn if last else (burn * (part + 1)) // n_parts
@@ -71,7 +81,7 @@ def test_given_the_matrix_the_run_is_the_oracles_hmc_and_the_matrix_is_the_five_
     prec = synth.dense_gaussian_precision(d)
     init = synth.initial_states(C, d, seed=2)
     draws, nacc, M, _ = _adapted("hmc", mcmc_amd.TARGET_GAUSS_DENSE, prec, init, 0, burn, keep, L, eps)
-    assert np.array_equal(M, _five_steps(np.ascontiguousarray(init.T))) and np.array_equal(M, M.T) and not np.array_equal(M, np.eye(d))
+    assert np.array_equal(M, _five_steps(np.ascontiguousarray(init.T), mirror_S=True)) and np.array_equal(M, M.T) and not np.array_equal(M, np.eye(d))
     t = orc.TargetSpec(orc.TARGET_DENSE, d, prec=prec, W=4)
     s = orc.make_settings(seed=5, n_burnin=burn, n_keep=keep, n_leap=L, step=eps, W=4, precond=M)
     o, info = orc.run_many(orc.ALGO_HMC, t, init, s)
@@ -88,7 +98,7 @@ def test_the_run_is_a_chain_of_ordinary_calls(algo, d, C, burn, keep, L, want):
     prec = synth.dense_gaussian_precision(d)
     init = synth.initial_states(C, d, seed=4)
     kind = mcmc_amd.TARGET_GAUSS_DENSE
-    h_draws, h_nacc, h_M, h_theta, Ms = _by_hand(algo, kind, prec, init, n_windows, burn, keep, L, eps)
+    h_draws, h_nacc, h_M, h_theta, Ms = _by_hand(algo, kind, prec, init, n_windows, burn, keep, L, eps, mirror_S=want is not None)
     draws, nacc, M, theta = _adapted(algo, kind, prec, init, n_windows, burn, keep, L, eps)
     name = mcmc_amd.last_kernel()
     if want == "lds":
