@@ -696,7 +696,8 @@ int mi_mcmc_draws_log_kernel(const mi_target* target, const double* draws_kdc, i
  * p_waic_r (WAIC, Watanabe 2010; Vehtari, Gelman and Gabry 2017), and on request the matrix ll itself.  It is the other fold of the product that
  * mi_mcmc_draws_log_kernel folds over the rows.  target->X / y live in target->mem; kernel_hint is ignored.  lppd_out, p_waic_out ([n_rows]) and
  * loglik_out ([n_rows][n_keep][C]) are in `mem`; any may be NULL.  Row r of loglik_out is a slab [n_keep][1][C] that mi_mcmc_draw_stats,
- * mi_mcmc_draw_stats_ranked, mi_mcmc_draws_quantiles and mi_mcmc_draws_covariance take as it is, and what a host PSIS-LOO reads.  summary (HOST, 4
+ * mi_mcmc_draw_stats_ranked, mi_mcmc_draws_quantiles and mi_mcmc_draws_covariance take as it is; PSIS-LOO does not need it copied out: mi_mcmc_draws_psis_loo
+ * below forms and consumes it on the device, a group of rows at a time.  summary (HOST, 4
  * doubles, may be NULL) = {elpd_waic, p_waic, lppd, se_elpd}.  A device slab with summary == NULL: the call returns after enqueueing on `stream` (with
  * a target in host memory: once its arrays have been read).  A device slab with summary, or a host slab: blocking.  Workspace: the stream's cached
  * one (mi_mcmc_release_workspace) -- the packed matrix, the chunk partials (32 n_chunks bytes per padded row), and the staged copies of a host slab,
@@ -734,6 +735,51 @@ int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t
                        double* loglik_out,  /* [n_rows][n_keep][C] in `mem`, may be NULL */
                        double* summary,     /* HOST, 4 doubles, may be NULL */
                        void* stream);
+
+/* PSIS-LOO: the Pareto-smoothed importance-sampling leave-one-out estimate elpd_loo_r of every data row r of a target that carries observations, and the
+ * shape pareto_k_r of the generalised Pareto distribution fitted to the row's largest importance ratios, its reliability diagnostic (Vehtari, Gelman and
+ * Gabry 2017; Vehtari, Simpson, Gelman, Yao and Gabry 2024; the fit: Zhang and Stephens 2009), of a slab [n_keep][d][C] on the device.  The matrix ll of
+ * mi_mcmc_draws_waic never leaves the device: the rows are walked in consecutive groups of G (a multiple of 128 whose block ll [G][K] fits a budget of
+ * 4 GiB, never less than 128, at most n_rows); a group's block is written by the WAIC kernels, every row of it is fully sorted by the radix sort of
+ * mi_mcmc_draws_rank_transform, and mcmc_amd/csrc/draws_psis.hip reads the sorted rows.  Targets, target->mem, staging of a host slab / target and
+ * MI_ERR_NO_DEVICE / MI_ERR_OOM / MI_ERR_UNSUPPORTED are those of mi_mcmc_draws_waic.  elpd_loo_out, pareto_k_out, lppd_out ([n_rows]) are in `mem`, any
+ * may be NULL; lppd_out holds the bits of mi_mcmc_draws_waic's lppd_out.  summary (HOST, 5 doubles, may be NULL) = {elpd_loo, p_loo, lppd, se_elpd_loo,
+ * n_bad}.  ALWAYS blocking (the sort waits for its digit histograms).  Workspace: the stream's cached one -- the block ll, the sort's two key images and
+ * counts (its own budget of 2 GiB), the WAIC workspace of a group, and the staged copies of a host slab and target.
+ * MI_ERR_BAD_ARG, before any HIP call: as mi_mcmc_draws_waic, with all four outputs NULL, and K = n_keep * n_chains < 25 (the tail would have fewer than
+ * five values: nothing is fitted) or K >= 2^32.
+ * DEFINITION (fp64, every operation rounded once, nothing contracted; exp / log: det_math.hpp; sqrt and division: IEEE).  For one data row r:
+ *   sorted row    ll[r][k] is mi_mcmc_draws_waic's, the same bits; s_0 <= ... <= s_{K-1} its K values ascending by the key of mi_mcmc_draws_order_stats.
+ *                 The importance ratios of leaving r out are exp(-ll): the largest come first.  Everything below is a function of the sorted row, hence
+ *                 of the multiset of the values.  s_0 or s_{K-1} not finite: elpd_loo_r = pareto_k_r = NaN (the other rows are untouched)
+ *   tail length   M = min(K div 5, m3), m3 the smallest integer with m3 * m3 >= 9 K (ceil(3 sqrt(K)), in integers).  5 <= M < K
+ *   cutoff        d = s_0 - s_M;  cut = d > -708.3964185322641 ? d : -708.3964185322641 (log of the smallest normal double);  ec = exp(cut)
+ *   exceedances   x_j = exp(s_0 - s_{M-j}) - ec, j = 1 .. M: ascending
+ *   SUM           SUM(v_0 .. v_{n-1}), the one order of every sum over tail or body values: slot t (t < 256) takes v_t, v_{t+256}, ... ascending from +0;
+ *                 the 256 slots meet as u[i] = u[i] + u[i + 128] (i < 128), then + u[i + 64] (i < 64), ..., + u[i + 1]
+ *   fit           n = (double)M;  m = 30 + floor(sqrt(M)) (integer);  q = x_{(M + 2) div 4} (= x_{floor(M / 4 + 0.5)});  for j = 1 .. m:
+ *                 b_j = (1 - sqrt((double)m / ((double)j - 0.5))) / (3 * q) + 1 / x_M;   k_j = SUM_i(log(1 - b_j * x_i)) / n  (i = 1 .. M, v_{i-1});
+ *                 L_j = n * ((log(-(b_j / k_j)) - k_j) - 1);   w_j = 1 / (the sum over l = 1 .. m ascending from +0 of exp(L_l - L_j));
+ *                 w_j >= 10 * 2^-52 ? kept : replaced by +0;  sw = the sum over j ascending from +0 of w_j;  bh = the sum over j ascending from +0 of
+ *                 b_j * (w_j / sw);  k0 = SUM_i(log(1 - bh * x_i)) / n;  sigma = -(k0 / bh);  khat = (n * k0 + 5) / (n + 10)
+ *   degenerate    !(q > 0), or khat not finite, or !(sigma > 0) -- ties that fill a quarter of the tail, a constant row --: nothing is smoothed, t_j is the raw
+ *                 s_0 - s_{M-j}, and pareto_k_r = +inf
+ *   smoothed tail otherwise, j = 1 .. M:  p = ((double)j - 0.5) / n;  lg = log(1 - p);  g = khat == 0 ? -(sigma * lg) : (sigma * (exp((-khat) * lg) - 1)) / khat;
+ *                 lt = log(g + ec);  t_j = lt < 0 ? lt : 0  -- the truncation at the largest raw ratio; t_j replaces the log-ratio of s_{M-j}
+ *   folds         Wt = SUM_j(exp(t_j));  Nt = SUM_j(exp(t_j + (s_{M-j} - s_0)))  (v_{j-1});  the body values e = 0 .. K - M - 1, exp(s_0 - s_{M+e}), in pieces
+ *                 of 16 384: B = the sum over the pieces ascending from +0 of SUM(the piece);  W = B + Wt;  N = (double)(K - M) + Nt  (a body term of
+ *                 the numerator is exp(0) = 1);  elpd_loo_r = (s_0 + log(N)) - log(W);  pareto_k_r = khat
+ *   summary       elpd_loo, lppd: the plain sums over r ascending from +0 of elpd_loo_r, lppd_r;  p_loo = lppd - elpd_loo;  se_elpd_loo: se_elpd of
+ *                 mi_mcmc_draws_waic on elpd_loo_r;  n_bad = the number of rows with !(pareto_k_r <= 0.7) (NaN and +inf count), as a double
+ * log(1 - t) and exp(t) - 1 go through log and exp as written (det_math.hpp has no log1p / expm1); what that costs is measured in DESIGN.md 4.27.
+ * The tail of a row is held in LDS up to 8 192 values and re-read from the sorted row beyond; the result depends on neither, nor on the groups, a
+ * grid, timing or an atomic order.  The numpy statement is mcmc_amd/psis.py. */
+int mi_mcmc_draws_psis_loo(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains,
+                           double* elpd_loo_out,  /* [n_rows] in `mem`, may be NULL */
+                           double* pareto_k_out,  /* [n_rows] in `mem`, may be NULL */
+                           double* lppd_out,      /* [n_rows] in `mem`, may be NULL: the bits of mi_mcmc_draws_waic's lppd_out */
+                           double* summary,       /* HOST, 5 doubles, may be NULL */
+                           void* stream);
 
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */

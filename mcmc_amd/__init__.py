@@ -94,7 +94,7 @@ EXPORTS = [
     "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
     "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
     "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
-    "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic",
+    "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic", "mi_mcmc_draws_psis_loo",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -901,3 +901,48 @@ def test_waic_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     lib().mi_mcmc_test_waic_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
                                  C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), C.c_int(int(bool(want_loglik))), o)
     return dict(zip(("route", "chunk", "n_chunks", "grid", "block", "lds_bytes", "ldR", "Kp", "merge_grid", "ws_bytes"), (int(v) for v in o)))
+
+
+def draws_psis_loo(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_elpd_loo=True, want_pareto_k=True, want_lppd=True, want_summary=True,
+                   elpd_loo=None, pareto_k=None, lppd=None):
+    """mi_mcmc_draws_psis_loo: per observation r of `target` (make_target; LOGISTIC or NORMAL_MODEL) the PSIS-LOO estimate elpd_loo[r], the Pareto shape
+    pareto_k[r] of its importance ratios and lppd[r] (mi_mcmc_draws_waic's, the same bits) of a slab [n_keep, d, C], and summary = (elpd_loo, p_loo, lppd,
+    se_elpd_loo, n_bad: the rows with k > 0.7, NaN or inf) -- numpy array, a 2-D [d, C] array being the case n_keep = 1; or a device tensor / pointer with
+    mem=MEM_DEVICE, explicit n_keep and n_chains and device tensors `elpd_loo`, `pareto_k`, `lppd` for what is wanted of them.  The call always waits.
+    include/mi_mcmc.h states every value bit for bit, mcmc_amd.psis repeats it in numpy.  Returns a dict of elpd_loo, pareto_k, lppd ([n_rows]) and summary
+    (a dict); what was not asked for is None."""
+    d, n_rows = int(target.d), int(target.n_rows)
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d_slab, n_chains = draws.shape
+        if d_slab != d:
+            raise ValueError(f"the slab has d = {d_slab}, the target d = {d}")
+        elpd_loo = np.zeros(n_rows) if want_elpd_loo else None
+        pareto_k = np.zeros(n_rows) if want_pareto_k else None
+        lppd = np.zeros(n_rows) if want_lppd else None
+    summ = np.zeros(5) if want_summary else None
+    _check(lib().mi_mcmc_draws_psis_loo(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                        C.c_void_p(_ptr(elpd_loo)), C.c_void_p(_ptr(pareto_k)), C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    summary = None if summ is None else dict(zip(("elpd_loo", "p_loo", "lppd", "se_elpd_loo", "n_bad"), (float(v) for v in summ)))
+    return dict(elpd_loo=elpd_loo, pareto_k=pareto_k, lppd=lppd, summary=summary)
+
+
+def test_set_psis_ll_bytes(n_bytes):
+    """mi_mcmc_test_set_psis_ll_bytes (TEST HOOK, mi_mcmc_probes.h): the budget of a row group's block ll of draws_psis_loo (0 = the real one)."""
+    lib().mi_mcmc_test_set_psis_ll_bytes(C.c_uint64(int(n_bytes)))
+
+
+def test_set_psis_lds_tail(n_doubles):
+    """mi_mcmc_test_set_psis_lds_tail (TEST HOOK, mi_mcmc_probes.h): the tail values draws_psis_loo keeps in LDS (0 = the real capacity)."""
+    lib().mi_mcmc_test_set_psis_lds_tail(C.c_uint32(int(n_doubles)))
+
+
+def test_psis_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_host=True):
+    """mi_mcmc_test_psis_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_psis_loo call under the hooks set, host arithmetic -- a dict of M, m, G,
+    n_groups, last_rows, tail_route (0 LDS, 1 re-read), lds_bytes, n_pieces, piece, sort_rows, ll_bytes, ws_bytes."""
+    o = (C.c_uint64 * 12)()
+    lib().mi_mcmc_test_psis_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
+    return dict(zip(("M", "m", "G", "n_groups", "last_rows", "tail_route", "lds_bytes", "n_pieces", "piece", "sort_rows", "ll_bytes", "ws_bytes"), (int(v) for v in o)))

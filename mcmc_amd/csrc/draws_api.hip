@@ -1,11 +1,12 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
-// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip and draws_waic.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip and draws_psis.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -18,6 +19,7 @@
 #include "draws_rank.hpp"
 #include "draws_logk.hpp"
 #include "draws_waic.hpp"
+#include "draws_psis.hpp"
 
 using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
@@ -580,8 +582,8 @@ int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
     return MI_OK;
 }
 
-// The checks that mi_mcmc_draws_log_kernel and mi_mcmc_draws_waic share, in the order in which a call that fails several reports them; they need no
-// device.  nothing_asked: NULL, or what to say of the call's outputs; the call needs at least min_K = 1 or 2 samples.  The two targets that carry
+// The checks that mi_mcmc_draws_log_kernel, mi_mcmc_draws_waic and mi_mcmc_draws_psis_loo share, in the order in which a call that fails several reports them; they need no
+// device.  nothing_asked: NULL, or what to say of the call's outputs; the call needs at least min_K samples.  The two targets that carry
 // observations are checked here; what an entry point makes of the other kinds is its own, after this
 static int target_slab_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const char* nothing_asked,
                              uint64_t min_K, uint64_t max_d)
@@ -592,8 +594,12 @@ static int target_slab_check(const char* who, const mi_target* t, const double* 
     if (t->struct_size != sizeof(mi_target)) return fail(MI_ERR_BAD_ARG, "%s: struct_size mismatch (header / library version skew)", who);
     if (t->d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
     if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
-    if (n_keep * n_chains < min_K)
-        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least %s needed", who, (unsigned long long)(n_keep * n_chains), min_K == 1 ? "1 sample is" : "2 samples are");
+    if (n_keep * n_chains < min_K) {
+        char need[48];
+        if (min_K == 1) std::snprintf(need, sizeof need, "1 sample is");
+        else std::snprintf(need, sizeof need, "%llu samples are", (unsigned long long)min_K);
+        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least %s needed", who, (unsigned long long)(n_keep * n_chains), need);
+    }
     if (t->d > max_d) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)max_d);
     if (t->kind == MI_TARGET_LOGISTIC && (!t->X || !t->y || t->n_rows == 0)) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
     if (t->kind == MI_TARGET_NORMAL_MODEL) {
@@ -736,6 +742,118 @@ int mi_mcmc_draws_waic(const mi_target* target, const double* draws_kdc, int32_t
     } else if (slab_host || target_host) {
         HIP_TRY(hipStreamSynchronize(st));               // the outputs are the caller's host arrays / the target's host arrays have been read
     }
+    return MI_OK;
+}
+
+// test hooks, declared in mi_mcmc_probes.h: the budget of a row group's block ll and the LDS capacity of the tail of mi_mcmc_draws_psis_loo
+// (draws_psis.hpp), and the host arithmetic of its plan under them and under the rank budget above
+static std::atomic<uint64_t> g_psis_ll_bytes{0};
+static std::atomic<uint32_t> g_psis_lds_tail{0};
+void mi_mcmc_test_set_psis_ll_bytes(uint64_t bytes) { g_psis_ll_bytes.store(bytes, std::memory_order_relaxed); }
+void mi_mcmc_test_set_psis_lds_tail(uint32_t n_doubles) { g_psis_lds_tail.store(n_doubles, std::memory_order_relaxed); }
+static mi::dpsis::PsisPlan psis_plan_now(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, bool slab_host, bool target_host)
+{
+    return mi::dpsis::psis_plan(kind, d, n_rows, n_keep, n_chains, slab_host, target_host, g_psis_ll_bytes.load(std::memory_order_relaxed),
+                                g_psis_lds_tail.load(std::memory_order_relaxed), g_rank_ws_bytes.load(std::memory_order_relaxed));
+}
+void mi_mcmc_test_psis_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out12)
+{
+    const mi::dpsis::PsisPlan p = psis_plan_now(kind, d, n_rows, n_keep, n_chains, slab_host != 0, target_host != 0);
+    out12[0] = p.M; out12[1] = p.m; out12[2] = p.G; out12[3] = p.n_groups; out12[4] = n_rows - (p.n_groups - 1) * p.G; out12[5] = (uint64_t)p.tail_route;
+    out12[6] = p.lds_bytes; out12[7] = p.n_pieces; out12[8] = mi::dpsis::PSIS_BODY_PIECE; out12[9] = p.rank.dims_per_group; out12[10] = p.o_rank - p.o_ll;
+    out12[11] = p.bytes;
+}
+
+// {elpd_loo, p_loo, lppd, se_elpd_loo, n_bad} of the rows' values (include/mi_mcmc.h; nothing is fused)
+static void psis_summary(const double* elpd, const double* pk, const double* lppd, uint64_t n_rows, double* summary)
+{
+    double e = 0.0, l = 0.0, bad = 0.0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        e = e + elpd[r];
+        l = l + lppd[r];
+        if (!(pk[r] <= 0.7)) bad = bad + 1.0;
+    }
+    const double m = e / (double)n_rows;
+    double v = 0.0;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        const double dv = elpd[r] - m;
+        const double sq = dv * dv;
+        v = v + sq;
+    }
+    const double var = v / (double)(n_rows - 1);          // n_rows = 1: 0 / 0, NaN
+    const double nv = (double)n_rows * var;
+    summary[0] = e; summary[1] = l - e; summary[2] = l; summary[3] = std::sqrt(nv); summary[4] = bad;
+}
+
+// PSIS-LOO and Pareto k per data row of a slab [n_keep][d][C] (draws_psis.hip; the arithmetic: include/mi_mcmc.h).  The rows go in groups: the block ll
+// of a group by draws_waic.hip, its rows sorted by draws_rank.hip, the tail fit and the folds by draws_psis.hip.  Always blocking.
+int mi_mcmc_draws_psis_loo(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, double* elpd_loo_out,
+                           double* pareto_k_out, double* lppd_out, double* summary, void* stream)
+{
+    const char* who = "draws_psis_loo";
+    const bool any_out = elpd_loo_out || pareto_k_out || lppd_out || summary;
+    int rc = target_slab_check(who, target, draws_kdc, n_keep, n_chains,
+                               any_out ? nullptr : "elpd_loo_out, pareto_k_out, lppd_out and summary are all NULL, nothing is asked for", mi::dpsis::PSIS_MIN_K,
+                               mi::dwaic::WAIC_MAX_D);
+    if (rc) return rc;
+    if (n_keep * n_chains > 0xffffffffULL)
+        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu samples per row, must be below 2^32", who, (unsigned long long)(n_keep * n_chains));
+    switch (target->kind) {
+    case MI_TARGET_LOGISTIC: case MI_TARGET_NORMAL_MODEL: break;
+    case MI_TARGET_GAUSS_ISO:
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d has no observations: only MI_TARGET_LOGISTIC and MI_TARGET_NORMAL_MODEL have a pointwise log-likelihood", who, target->kind);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, target->kind);
+    }
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d, K = n_keep * n_chains, n_rows = target->n_rows;
+    const bool slab_host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
+    if (n_rows > (1ULL << 38)) return fail(MI_ERR_OOM, "%s: n_rows = %llu do not fit the device memory", who, (unsigned long long)n_rows);
+    const mi::dpsis::PsisPlan plan = psis_plan_now(target->kind, d, n_rows, n_keep, n_chains, slab_host, target_host);
+    if (plan.waic.grid >= (1ULL << 31)) return fail(MI_ERR_OOM, "%s: %llu chunks x %llu rows of a group do not fit the device memory", who, (unsigned long long)plan.waic.n_chunks, (unsigned long long)plan.G);
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    const double *x = draws_kdc, *mat = target->X, *y = target->y;
+    if ((rc = stage_target_slab(W, plan.o_mat, plan.o_y, plan.o_slab, plan.mat_doubles, plan.y_doubles, target_host, slab_host, K * d, st, &x, &mat, &y))) return rc;
+    double* const elpd = reinterpret_cast<double*>(W + plan.o_elpd);
+    double* const pk = reinterpret_cast<double*>(W + plan.o_k);
+    double* const lppd = reinterpret_cast<double*>(W + plan.o_lppd);
+    double* const part = reinterpret_cast<double*>(W + plan.o_part);
+    double* const ll = reinterpret_cast<double*>(W + plan.o_ll);
+    const bool logistic = target->kind == MI_TARGET_LOGISTIC;
+    for (uint64_t r0 = 0; r0 < n_rows; r0 += plan.G) {
+        const uint64_t g = std::min<uint64_t>(plan.G, n_rows - r0);
+        // the sub-target: rows r0 .. r0 + g of the row-major X are contiguous
+        const mi::dwaic::WaicPlan wp = g == plan.G ? plan.waic : mi::dwaic::waic_plan(target->kind, d, g, n_keep, n_chains, false, false, true);
+        HIP_TRY((hipError_t)mi::dwaic::waic_run(wp, x, logistic ? mat + r0 * d : mat, y + r0, W + plan.o_waic, ll, st));
+        HIP_TRY(hipMemcpyAsync(lppd + r0, W + plan.o_waic + wp.o_lppd, g * 8, hipMemcpyDeviceToDevice, st));
+        // the block [g][K] is a slab [1][g][K]: every row sorted, in the rank plan's own groups
+        for (uint64_t dim0 = 0; dim0 < g; dim0 += plan.rank.dims_per_group) {
+            const uint64_t nd = std::min<uint64_t>(plan.rank.dims_per_group, g - dim0);
+            const uint64_t* sorted = nullptr;
+            HIP_TRY((hipError_t)mi::drank::rank_sort_group(ll, plan.rank, dim0, nd, false, W + plan.o_rank, st, &sorted));
+            HIP_TRY((hipError_t)mi::dpsis::psis_run_group(plan, sorted, nd, part, elpd + r0 + dim0, pk + r0 + dim0, st));
+        }
+    }
+    const hipMemcpyKind back = slab_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (elpd_loo_out) HIP_TRY(hipMemcpyAsync(elpd_loo_out, elpd, n_rows * 8, back, st));
+    if (pareto_k_out) HIP_TRY(hipMemcpyAsync(pareto_k_out, pk, n_rows * 8, back, st));
+    if (lppd_out) HIP_TRY(hipMemcpyAsync(lppd_out, lppd, n_rows * 8, back, st));
+    if (summary) {
+        std::vector<double> h(3 * n_rows);
+        HIP_TRY(hipMemcpyAsync(h.data(), elpd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.data() + n_rows, pk, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.data() + 2 * n_rows, lppd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        psis_summary(h.data(), h.data() + n_rows, h.data() + 2 * n_rows, n_rows, summary);
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // always blocking: the sorts have waited already, and the workspace is read until here
     return MI_OK;
 }
 

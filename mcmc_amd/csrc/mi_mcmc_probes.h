@@ -86,6 +86,16 @@ void mi_mcmc_test_draw_stats_last(uint64_t* out8);
  * workgroup, the padded rows ldR, the contraction extent Kp, the merge kernel's workgroups, the workspace bytes. */
 void mi_mcmc_test_waic_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, int want_loglik,
                             uint64_t* out10);
+/* Defined in libmi_mcmc.so itself (test hooks like the ones above), for mi_mcmc_draws_psis_loo (draws_psis.hpp): the budget of the block ll [G][K] of one
+ * row group in bytes (0, or more than the real budget = the real budget; a group never has fewer than 128 rows), so that a test of 300 rows runs the
+ * loop over row groups that a call of terabytes runs; and the values of a row's tail a workgroup keeps in LDS (0, or more than the real capacity = the
+ * real capacity), so that a test at M = 260 runs the route that re-reads the tail from the sorted row.  Process-wide.  Results do not depend on them. */
+void mi_mcmc_test_set_psis_ll_bytes(uint64_t bytes);
+void mi_mcmc_test_set_psis_lds_tail(uint32_t n_doubles);
+/* ... and the plan of a call under the two hooks above and mi_mcmc_test_set_rank_ws_bytes, host arithmetic that needs no device.  out12: the tail length M,
+ * the fit points m, the rows G of a group, the groups, the rows of the last group, the tail route (0 LDS, 1 re-read), LDS bytes of the tail, the pieces of
+ * a row's body fold, the values of a piece, the rows per group of the sort, the bytes of the block ll, the workspace bytes. */
+void mi_mcmc_test_psis_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out12);
 #ifdef __cplusplus
 }
 #endif
