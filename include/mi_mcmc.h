@@ -781,6 +781,42 @@ int mi_mcmc_draws_psis_loo(const mi_target* target, const double* draws_kdc, int
                            double* summary,       /* HOST, 5 doubles, may be NULL */
                            void* stream);
 
+/* WAIC and PSIS-LOO of a pointwise log-likelihood matrix that the CALLER supplies -- the way to both for a user-defined device target
+ * (mi_mcmc_target.hpp, mi_mcmc_tile_target.hpp) or a host callback target, which the two entries above do not take: who can sample a model with a
+ * functor of their own can fill ll[r][k] with a kernel of their own (examples/user_loglik.hip), and the matrix need not leave the device.
+ * loglik (in `mem`; a host matrix is staged whole into the stream's cached workspace) holds n_rows x K doubles, K = n_keep * n_chains, in one of two layouts: */
+enum { MI_LOGLIK_ROWS = 0,   /* [n_rows][n_keep][C]: the layout of mi_mcmc_draws_waic's loglik_out                      */
+       MI_LOGLIK_SLAB = 1 }; /* [n_keep][n_rows][C]: a draws slab whose "dimensions" are the observations -- what a
+                                kernel with one thread per chain writes next to the draws                                 */
+/* DEFINITION.  ll[r][k] is the caller's value at sample k = t * C + c.  After that nothing new is defined:
+ *   mi_mcmc_loglik_waic      lppd_r, p_waic_r and summary = {elpd_waic, p_waic, lppd, se_elpd} are the section THE ORDER of mi_mcmc_draws_waic, unchanged:
+ *                            chunks of 2 048, the chunk's first column as shift, 64 slots, tree, chunk moments, merge, summary.
+ *   mi_mcmc_loglik_psis_loo  elpd_loo_r, pareto_k_r and summary = {elpd_loo, p_loo, lppd, se_elpd_loo, n_bad} are the section DEFINITION of
+ *                            mi_mcmc_draws_psis_loo, unchanged; lppd_out carries the bits of mi_mcmc_loglik_waic's.
+ * Both layouts describe the same matrix, so they give the same bits; fed mi_mcmc_draws_waic's loglik_out, the two entries give the bits of
+ * mi_mcmc_draws_waic and mi_mcmc_draws_psis_loo.  The result depends on no device, grid, timing or atomic order; non-finite values propagate by the IEEE
+ * rules through those expressions.  The numpy statements are mcmc_amd/waic.py (row_stats, summary) and mcmc_amd/psis.py (psis_ref).
+ * The outputs ([n_rows]) are in `mem`, any may be NULL; summary is on the HOST, may be NULL.  mi_mcmc_loglik_waic on a device matrix with summary == NULL
+ * returns after enqueueing on `stream`; with summary, or on a host matrix, it blocks.  mi_mcmc_loglik_psis_loo ALWAYS blocks (the sort waits for its
+ * digit histograms).  The matrix is read where it lies: the sorter of mi_mcmc_draws_rank_transform takes it as its slab, nothing is copied or grouped
+ * beyond the sorter's own groups (its budget of 2 GiB).  Workspace: the stream's cached one (mi_mcmc_release_workspace) -- the chunk partials (32 n_chunks
+ * bytes per padded row), the results, the sort's key images and counts, the staged copy of a host matrix.  No CPU path: no device is MI_ERR_NO_DEVICE;
+ * what does not fit the free device memory is MI_ERR_OOM, as are K or n_rows beyond 2^38 and a matrix of more than 2^40 values.
+ * MI_ERR_BAD_ARG, before any HIP call, in this order: a NULL matrix; all outputs NULL; an unknown layout; n_rows = 0; n_keep or n_chains beyond 32 bits;
+ * K < 2 (mi_mcmc_loglik_waic) or K < 25 (mi_mcmc_loglik_psis_loo); K >= 2^32 (mi_mcmc_loglik_psis_loo); MI_LOGLIK_SLAB with n_rows > 65 536, the bound on
+ * the dimensions of a slab of mi_mcmc_draws_rank_transform (MI_LOGLIK_ROWS has no such bound). */
+int mi_mcmc_loglik_waic(const double* loglik, int32_t layout, int32_t mem, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains,
+                        double* lppd_out,    /* [n_rows] in `mem`, may be NULL */
+                        double* p_waic_out,  /* [n_rows] in `mem`, may be NULL */
+                        double* summary,     /* HOST, 4 doubles, may be NULL */
+                        void* stream);
+int mi_mcmc_loglik_psis_loo(const double* loglik, int32_t layout, int32_t mem, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains,
+                            double* elpd_loo_out,  /* [n_rows] in `mem`, may be NULL */
+                            double* pareto_k_out,  /* [n_rows] in `mem`, may be NULL */
+                            double* lppd_out,      /* [n_rows] in `mem`, may be NULL: the bits of mi_mcmc_loglik_waic's lppd_out */
+                            double* summary,       /* HOST, 5 doubles, may be NULL */
+                            void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

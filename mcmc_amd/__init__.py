@@ -95,6 +95,7 @@ EXPORTS = [
     "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
     "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
     "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic", "mi_mcmc_draws_psis_loo",
+    "mi_mcmc_loglik_waic", "mi_mcmc_loglik_psis_loo",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -946,3 +947,65 @@ def test_psis_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     lib().mi_mcmc_test_psis_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
                                  C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
     return dict(zip(("M", "m", "G", "n_groups", "last_rows", "tail_route", "lds_bytes", "n_pieces", "piece", "sort_rows", "ll_bytes", "ws_bytes"), (int(v) for v in o)))
+
+
+LOGLIK_ROWS, LOGLIK_SLAB = 0, 1
+
+
+def _loglik_shape(loglik, layout, n_rows, n_keep, n_chains, mem):
+    if layout not in (LOGLIK_ROWS, LOGLIK_SLAB):
+        raise ValueError(f"layout = {layout!r}: LOGLIK_ROWS or LOGLIK_SLAB")
+    if mem == MEM_HOST:
+        loglik = np.ascontiguousarray(loglik, dtype=np.float64)
+        if loglik.ndim == 2:                              # [n_rows, K]: the case n_keep = 1
+            loglik = loglik[:, None, :] if layout == LOGLIK_ROWS else loglik[None]
+        if layout == LOGLIK_ROWS:
+            n_rows, n_keep, n_chains = loglik.shape
+        else:
+            n_keep, n_rows, n_chains = loglik.shape
+    return loglik, int(n_rows), int(n_keep), int(n_chains)
+
+
+def loglik_waic(loglik, layout=LOGLIK_ROWS, n_rows=None, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_lppd=True, want_p_waic=True, want_summary=True,
+                lppd=None, p_waic=None):
+    """mi_mcmc_loglik_waic: draws_waic's lppd[r], p_waic[r] and summary of a pointwise log-likelihood matrix of the caller's own -- what a user-defined
+    target has instead of a built-in one.  loglik: a numpy array [n_rows, n_keep, C] (layout=LOGLIK_ROWS, the layout of draws_waic's loglik; 2-D
+    [n_rows, K] being n_keep = 1) or [n_keep, n_rows, C] (LOGLIK_SLAB, a draws slab whose dimensions are the observations); or a device tensor / pointer
+    with mem=MEM_DEVICE, explicit n_rows, n_keep and n_chains and device tensors `lppd`, `p_waic` for what is wanted of them (written on `stream`; the call
+    waits only where the summary is wanted).  The bits are those of mcmc_amd.waic.row_stats and summary.  Returns a dict of lppd, p_waic, loglik (always
+    None: the matrix is the caller's) and summary (a dict); what was not asked for is None."""
+    loglik, n_rows, n_keep, n_chains = _loglik_shape(loglik, layout, n_rows, n_keep, n_chains, mem)
+    if mem == MEM_HOST:
+        lppd = np.zeros(n_rows) if want_lppd else None
+        p_waic = np.zeros(n_rows) if want_p_waic else None
+    summ = np.zeros(4) if want_summary else None
+    _check(lib().mi_mcmc_loglik_waic(C.c_void_p(_ptr(loglik)), C.c_int32(layout), C.c_int32(mem), C.c_uint64(n_rows), C.c_uint64(n_keep), C.c_uint64(n_chains),
+                                     C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(p_waic)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    summary = None if summ is None else dict(zip(("elpd_waic", "p_waic", "lppd", "se_elpd"), (float(v) for v in summ)))
+    return dict(lppd=lppd, p_waic=p_waic, loglik=None, summary=summary)
+
+
+def loglik_psis_loo(loglik, layout=LOGLIK_ROWS, n_rows=None, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_elpd_loo=True, want_pareto_k=True,
+                    want_lppd=True, want_summary=True, elpd_loo=None, pareto_k=None, lppd=None):
+    """mi_mcmc_loglik_psis_loo: draws_psis_loo's elpd_loo[r], pareto_k[r], lppd[r] and summary of a pointwise log-likelihood matrix of the caller's own
+    (loglik, layout and the device form as loglik_waic's; device tensors `elpd_loo`, `pareto_k`, `lppd`).  The call always waits.  The bits are those of
+    mcmc_amd.psis.psis_ref.  Returns a dict of elpd_loo, pareto_k, lppd ([n_rows]) and summary (a dict); what was not asked for is None."""
+    loglik, n_rows, n_keep, n_chains = _loglik_shape(loglik, layout, n_rows, n_keep, n_chains, mem)
+    if mem == MEM_HOST:
+        elpd_loo = np.zeros(n_rows) if want_elpd_loo else None
+        pareto_k = np.zeros(n_rows) if want_pareto_k else None
+        lppd = np.zeros(n_rows) if want_lppd else None
+    summ = np.zeros(5) if want_summary else None
+    _check(lib().mi_mcmc_loglik_psis_loo(C.c_void_p(_ptr(loglik)), C.c_int32(layout), C.c_int32(mem), C.c_uint64(n_rows), C.c_uint64(n_keep), C.c_uint64(n_chains),
+                                         C.c_void_p(_ptr(elpd_loo)), C.c_void_p(_ptr(pareto_k)), C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    summary = None if summ is None else dict(zip(("elpd_loo", "p_loo", "lppd", "se_elpd_loo", "n_bad"), (float(v) for v in summ)))
+    return dict(elpd_loo=elpd_loo, pareto_k=pareto_k, lppd=lppd, summary=summary)
+
+
+def test_loglik_plan(layout, n_rows, n_keep, n_chains, mat_host=True, psis=True):
+    """mi_mcmc_test_loglik_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a loglik_waic (psis=False) or loglik_psis_loo call under the hooks set, host
+    arithmetic -- a dict of n_chunks, fold_grid, M, m, sort_rows, sort_groups, tail_route (0 LDS, 1 re-read), ws_bytes."""
+    o = (C.c_uint64 * 8)()
+    lib().mi_mcmc_test_loglik_plan(C.c_int32(int(layout)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                   C.c_int(int(bool(mat_host))), C.c_int(int(bool(psis))), o)
+    return dict(zip(("n_chunks", "fold_grid", "M", "m", "sort_rows", "sort_groups", "tail_route", "ws_bytes"), (int(v) for v in o)))

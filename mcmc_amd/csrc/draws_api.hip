@@ -1,5 +1,5 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
-// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip and draws_psis.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip and draws_loglik.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +20,7 @@
 #include "draws_logk.hpp"
 #include "draws_waic.hpp"
 #include "draws_psis.hpp"
+#include "draws_loglik.hpp"
 
 using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
@@ -850,6 +851,125 @@ int mi_mcmc_draws_psis_loo(const mi_target* target, const double* draws_kdc, int
         HIP_TRY(hipMemcpyAsync(h.data(), elpd, n_rows * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h.data() + n_rows, pk, n_rows * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h.data() + 2 * n_rows, lppd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        psis_summary(h.data(), h.data() + n_rows, h.data() + 2 * n_rows, n_rows, summary);
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // always blocking: the sorts have waited already, and the workspace is read until here
+    return MI_OK;
+}
+
+// The plan of the two entries below under the hooks of the LDS tail and the rank budget, and its test hook (mi_mcmc_probes.h)
+static mi::dloglik::LoglikPlan loglik_plan_now(int32_t layout, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, bool mat_host, bool psis)
+{
+    return mi::dloglik::loglik_plan(layout, n_rows, n_keep, n_chains, mat_host, psis, g_psis_lds_tail.load(std::memory_order_relaxed),
+                                    g_rank_ws_bytes.load(std::memory_order_relaxed));
+}
+void mi_mcmc_test_loglik_plan(int32_t layout, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int mat_host, int psis, uint64_t* out8)
+{
+    const mi::dloglik::LoglikPlan p = loglik_plan_now(layout, n_rows, n_keep, n_chains, mat_host != 0, psis != 0);
+    out8[0] = p.n_chunks; out8[1] = p.fold_grid; out8[2] = p.psis.M; out8[3] = p.psis.m; out8[4] = p.psis.rank.dims_per_group; out8[5] = p.psis.rank.n_groups;
+    out8[6] = (uint64_t)p.psis.tail_route; out8[7] = p.bytes;
+}
+
+// The checks that mi_mcmc_loglik_waic and mi_mcmc_loglik_psis_loo share, in the order in which a call that fails several reports them; they need no device
+static int loglik_check(const char* who, const double* loglik, const char* nothing_asked, int32_t layout, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains,
+                        uint64_t min_K, bool psis)
+{
+    if (!loglik) return fail(MI_ERR_BAD_ARG, "%s: null matrix", who);
+    if (nothing_asked) return fail(MI_ERR_BAD_ARG, "%s: %s", who, nothing_asked);
+    if (layout != MI_LOGLIK_ROWS && layout != MI_LOGLIK_SLAB) return fail(MI_ERR_BAD_ARG, "%s: layout = %d is neither MI_LOGLIK_ROWS nor MI_LOGLIK_SLAB", who, layout);
+    if (n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: n_rows must be positive", who);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (n_keep * n_chains < min_K)
+        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least %llu samples are needed", who, (unsigned long long)(n_keep * n_chains), (unsigned long long)min_K);
+    if (psis && n_keep * n_chains > 0xffffffffULL)
+        return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu samples per row, must be below 2^32", who, (unsigned long long)(n_keep * n_chains));
+    if (layout == MI_LOGLIK_SLAB && n_rows > mi::drank::RANK_MAX_D)
+        return fail(MI_ERR_BAD_ARG, "%s: MI_LOGLIK_SLAB with n_rows = %llu is beyond %llu", who, (unsigned long long)n_rows, (unsigned long long)mi::drank::RANK_MAX_D);
+    return MI_OK;
+}
+
+// After the device probe: what does not fit any device (and would leave a byte count or a grid outside its type), the plan, the workspace, a host
+// matrix staged into it.  *mat: the caller's pointer on entry, the device's on return
+static int loglik_begin(const char* who, int32_t layout, int32_t mem, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, bool psis, hipStream_t st,
+                        mi::dloglik::LoglikPlan& plan, WsLease& ws, const double** mat)
+{
+    const uint64_t K = n_keep * n_chains;
+    if (K > (1ULL << 38) || n_rows > (1ULL << 38) || n_rows > mi::dloglik::LOGLIK_MAX_ELEMS / K)
+        return fail(MI_ERR_OOM, "%s: K = %llu columns x n_rows = %llu do not fit the device memory", who, (unsigned long long)K, (unsigned long long)n_rows);
+    const bool mat_host = mem == MI_MEM_HOST;
+    plan = loglik_plan_now(layout, n_rows, n_keep, n_chains, mat_host, psis);
+    if (plan.fold_grid >= (1ULL << 31)) return fail(MI_ERR_OOM, "%s: %llu chunks x %llu rows do not fit the device memory", who, (unsigned long long)plan.n_chunks, (unsigned long long)n_rows);
+    int rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    if (mat_host) {
+        char* W = ws.as<char>();
+        HIP_TRY(hipMemcpyAsync(W + plan.o_mat, *mat, n_rows * K * 8, hipMemcpyHostToDevice, st));
+        *mat = reinterpret_cast<const double*>(W + plan.o_mat);
+    }
+    return MI_OK;
+}
+
+// lppd, p_waic and the WAIC summary of a caller-supplied matrix ll (draws_loglik.hip; the order: mi_mcmc_draws_waic's in include/mi_mcmc.h)
+int mi_mcmc_loglik_waic(const double* loglik, int32_t layout, int32_t mem, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, double* lppd_out, double* p_waic_out,
+                        double* summary, void* stream)
+{
+    const char* who = "loglik_waic";
+    const bool any_out = lppd_out || p_waic_out || summary;
+    int rc = loglik_check(who, loglik, any_out ? nullptr : "lppd_out, p_waic_out and summary are all NULL, nothing is asked for", layout, n_rows, n_keep, n_chains, 2, false);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    mi::dloglik::LoglikPlan plan;
+    WsLease ws;
+    const double* mat = loglik;
+    if ((rc = loglik_begin(who, layout, mem, n_rows, n_keep, n_chains, false, st, plan, ws, &mat))) return rc;
+    char* W = ws.as<char>();
+    HIP_TRY((hipError_t)mi::dloglik::loglik_fold(plan, mat, W, st));
+    const bool mat_host = mem == MI_MEM_HOST;
+    const hipMemcpyKind back = mat_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (lppd_out) HIP_TRY(hipMemcpyAsync(lppd_out, W + plan.o_lppd, n_rows * 8, back, st));
+    if (p_waic_out) HIP_TRY(hipMemcpyAsync(p_waic_out, W + plan.o_pw, n_rows * 8, back, st));
+    if (summary) {
+        std::vector<double> lp(n_rows), pw(n_rows);
+        HIP_TRY(hipMemcpyAsync(lp.data(), W + plan.o_lppd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(pw.data(), W + plan.o_pw, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // blocking: summary is written on the host
+        waic_summary(lp.data(), pw.data(), n_rows, summary);
+    } else if (mat_host) {
+        HIP_TRY(hipStreamSynchronize(st));               // the matrix and the outputs are the caller's host arrays
+    }
+    return MI_OK;
+}
+
+// PSIS-LOO and Pareto k of a caller-supplied matrix ll: the matrix is the slab the sorter takes (draws_loglik.hip, draws_rank.hip, draws_psis.hip; the
+// arithmetic: mi_mcmc_draws_psis_loo's in include/mi_mcmc.h).  Always blocking.
+int mi_mcmc_loglik_psis_loo(const double* loglik, int32_t layout, int32_t mem, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, double* elpd_loo_out,
+                            double* pareto_k_out, double* lppd_out, double* summary, void* stream)
+{
+    const char* who = "loglik_psis_loo";
+    const bool any_out = elpd_loo_out || pareto_k_out || lppd_out || summary;
+    int rc = loglik_check(who, loglik, any_out ? nullptr : "elpd_loo_out, pareto_k_out, lppd_out and summary are all NULL, nothing is asked for", layout, n_rows, n_keep,
+                          n_chains, mi::dpsis::PSIS_MIN_K, true);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    mi::dloglik::LoglikPlan plan;
+    WsLease ws;
+    const double* mat = loglik;
+    if ((rc = loglik_begin(who, layout, mem, n_rows, n_keep, n_chains, true, st, plan, ws, &mat))) return rc;
+    char* W = ws.as<char>();
+    if (lppd_out || summary) HIP_TRY((hipError_t)mi::dloglik::loglik_fold(plan, mat, W, st));
+    HIP_TRY((hipError_t)mi::dloglik::loglik_psis(plan, mat, W, st));
+    const hipMemcpyKind back = mem == MI_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (elpd_loo_out) HIP_TRY(hipMemcpyAsync(elpd_loo_out, W + plan.o_elpd, n_rows * 8, back, st));
+    if (pareto_k_out) HIP_TRY(hipMemcpyAsync(pareto_k_out, W + plan.o_k, n_rows * 8, back, st));
+    if (lppd_out) HIP_TRY(hipMemcpyAsync(lppd_out, W + plan.o_lppd, n_rows * 8, back, st));
+    if (summary) {
+        std::vector<double> h(3 * n_rows);
+        HIP_TRY(hipMemcpyAsync(h.data(), W + plan.o_elpd, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.data() + n_rows, W + plan.o_k, n_rows * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.data() + 2 * n_rows, W + plan.o_lppd, n_rows * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         psis_summary(h.data(), h.data() + n_rows, h.data() + 2 * n_rows, n_rows, summary);
     }

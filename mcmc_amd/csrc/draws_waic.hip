@@ -409,5 +409,11 @@ int waic_run(const WaicPlan& p, const double* x, const double* mat, const double
     return (int)hipGetLastError();
 }
 
+int waic_merge(const double* part, uint64_t n_chunks, uint64_t K, uint64_t n_rows, uint64_t ldR, double* lppd, double* p_waic, hipStream_t st)
+{
+    hipLaunchKernelGGL(waic_merge_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, part, n_chunks, K, n_rows, ldR, lppd, p_waic);
+    return (int)hipGetLastError();
+}
+
 }  // namespace dwaic
 }  // namespace mi

@@ -46,6 +46,8 @@ WaicPlan waic_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
 // enqueues the kernels on `st`.  x, mat (X), y, loglik (NULL: not asked for): device memory; ws: the workspace; lppd and p_waic go to ws + plan.o_lppd /
 // plan.o_pw.  Returns a hipError_t as int (0 = enqueued)
 int waic_run(const WaicPlan& plan, const double* x, const double* mat, const double* y, void* ws, double* loglik, hipStream_t st);
+// enqueues the merge kernel alone, over chunk partials [n_chunks][4][ldR] that somebody else formed in the order above (draws_loglik.hip): lppd, p_waic [n_rows]
+int waic_merge(const double* part, uint64_t n_chunks, uint64_t K, uint64_t n_rows, uint64_t ldR, double* lppd, double* p_waic, hipStream_t st);
 
 }  // namespace dwaic
 }  // namespace mi

@@ -96,6 +96,12 @@ void mi_mcmc_test_set_psis_lds_tail(uint32_t n_doubles);
  * the fit points m, the rows G of a group, the groups, the rows of the last group, the tail route (0 LDS, 1 re-read), LDS bytes of the tail, the pieces of
  * a row's body fold, the values of a piece, the rows per group of the sort, the bytes of the block ll, the workspace bytes. */
 void mi_mcmc_test_psis_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out12);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_loglik_waic (psis == 0) and mi_mcmc_loglik_psis_loo (psis != 0)
+ * (draws_loglik.hpp): the plan of a call under mi_mcmc_test_set_psis_lds_tail and mi_mcmc_test_set_rank_ws_bytes, host arithmetic that needs no device.
+ * layout: MI_LOGLIK_ROWS / MI_LOGLIK_SLAB; mat_host != 0: the matrix is staged in the workspace.  out8: the chunks of 2 048 columns, the fold kernel's
+ * workgroups, the tail length M, the fit points m, the rows per group of the sort, the sort groups, the tail route (0 LDS, 1 re-read), the workspace
+ * bytes; M, m, the rows per group, the groups and the route are 0 for psis == 0. */
+void mi_mcmc_test_loglik_plan(int32_t layout, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int mat_host, int psis, uint64_t* out8);
 #ifdef __cplusplus
 }
 #endif
