@@ -69,3 +69,15 @@ def test_matrix_product_samplers_random_cases(n):
     ragged d / N / chain tiles, step sizes from tiny to absurd, non-finite starts, chain0 / draw0 offsets, runs cut in two (tests/fuzz_gemm.py)"""
     import fuzz_gemm
     assert fuzz_gemm.sweep(n, 9, verbose=False) == 0
+
+
+@pytest.mark.parametrize("n,seed", [(24, 4), pytest.param(80, 107, marks=SLOW)])
+def test_tile_route_random_cases_are_bit_exact(n, seed):
+    """the six kernel families of the tile-target route (include/mi_mcmc_tile_target.hpp) against the oracle driven by the target library's host callback: the twisted
+    Gaussian at NT 1 / 2 / 4 / 8, ragged d and chain tiles, bounds and / or a diagonal precond_mat, step sizes from tiny to absurd, non-finite starts, chain0 / draw0
+    offsets, runs cut in two (tests/fuzz_tile.py; tests/test_tile_route_cpu.py holds the mix of these seeds)"""
+    import fuzz_tile
+    import tile_route
+    if not tile_route.have_toolchain():
+        pytest.skip("no hipcc / libmi_mcmc")
+    assert fuzz_tile.sweep(n, seed, verbose=False)[0] == 0

@@ -7,7 +7,6 @@ target (twisted Gaussian) under hmc, mala and nuts is bit-identical to the oracl
 callback (ref: include/mcmc/hmc.hpp:42-48)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,13 +28,11 @@ class TwistedTile(C.Structure):
 
 
 @pytest.fixture(scope="module")
-def tile_lib(tmp_path_factory):
+def tile_lib():
     if not os.path.exists(HIPCC):
         pytest.skip("no hipcc")
-    out = str(tmp_path_factory.mktemp("utt") / "libuser_tile_target.so")
-    subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-Wall", "-Werror",
-                           "-Wno-unused-function", *os.environ.get("MI_TILE_CFLAGS", "").split(), f"-I{ROOT}/include", "-shared", f"{ROOT}/examples/user_tile_target.hip",
-                           f"-L{ROOT}/mcmc_amd", "-lmi_mcmc", f"-Wl,-rpath,{ROOT}/mcmc_amd", "-o", out])
+    import tile_route                               # (the example is compiled once per process: tests/test_gpu_tile_route_edges.py runs it too)
+    out = tile_route.build("example")
     mcmc_amd.lib()                                  # the engine first: one HIP runtime for torch, the engine and the target library
     lib = C.CDLL(out)
     lib.twisted_host_kernel.restype = C.c_double
