@@ -817,6 +817,90 @@ int mi_mcmc_loglik_psis_loo(const double* loglik, int32_t layout, int32_t mem, u
                             double* summary,       /* HOST, 5 doubles, may be NULL */
                             void* stream);
 
+/* BRIDGE SAMPLING: the log marginal likelihood log Z = log of the integral of K(theta) over R^d -- what Bayes factors and posterior model probabilities are
+ * made of -- from the posterior draws of a slab [n_keep][d][C] and draws of a Gaussian proposal fitted to them (Meng and Wong 1996; Gronau et al. 2017, the
+ * R package bridgesampling), on the device.  Three entries: the proposal (fit, draw, evaluate), the estimate (the iteration and its error terms) and their
+ * composition for the built-in targets.  A user-defined or callback target calls the first, evaluates its own log-kernel on prop_out and on the
+ * iteration part (as examples/user_loglik.hip does for ll), and calls the second.
+ * NOTATION.  n_fit (0: n_keep div 2), 1 <= n_fit < n_keep.  The FIT PART is rows t < n_fit: a prefix slab [n_fit][d][C], K0 = n_fit * C samples.  The
+ * ITERATION PART is rows t >= n_fit: a suffix slab [n_it][d][C], n_it = n_keep - n_fit, N1 = n_it * C, sample j = (t - n_fit) * C + c.  n_prop = N2
+ * (0: N1) proposal draws.  seed: the Philox key.
+ * ALL THREE always block, use the stream's cached workspace (mi_mcmc_release_workspace), stage a host slab (`mem`), and have no CPU path: no device is
+ * MI_ERR_NO_DEVICE; a need beyond the free device memory is MI_ERR_OOM, as is a host without memory for the fit's three d x d matrices (S, L, Pg:
+ * 24 d^2 bytes).  The PRACTICAL range of d is that of a dense precond_mat: the factorisations run on the device up to d = 3 840 (INV) / 7 680 (CHOL_LOWER)
+ * and in O(d^3) loops on the calling thread beyond, minutes at d of ten thousand; d <= 65 536 is the bound of the slab reducers, not a promise of speed.
+ * mi_mcmc_last_kernel() names the bridge kernels.
+ * MI_ERR_BAD_ARG, before any HIP call: a NULL slab, input or target; all outputs NULL; d = 0 or d > 65 536; n_keep < 2; n_fit >= n_keep; K0 < 2 or N1 < 2;
+ * N2 < 2; n_keep, n_chains or N2 beyond 32 bits; tol < 0 or NaN; n_eff < 0 or NaN; a struct_size mismatch; an unknown kind (and, for the target's own
+ * arrays, what mi_mcmc_draws_log_kernel refuses).
+ *
+ * mi_mcmc_bridge_proposal.  DEFINITION (fp64, every operation rounded once, nothing contracted; log: det_math.hpp; LOG_2PI = 1.83787706640934548356):
+ *   A  (mu, S) = mi_mcmc_draws_covariance's mean and cov of the prefix slab [n_fit][d][C]: the same bits.
+ *   B  S holds a non-finite entry: status = 1.  Otherwise L = CHOL_LOWER(S), Pg = INV(S) (mi_mcmc_mat_cholesky_lower's / mi_mcmc_mat_inverse's routines);
+ *      any entry of L or Pg non-finite, or any L_aa <= 0: status = 1 (K0 <= d, a NaN in the fit part).  Otherwise status = 0 and
+ *      ldh = (the sum over a ascending from +0 of log(L_aa)) + (0.5 * (double)d) * LOG_2PI.
+ *      status 1: every value of prop_out, logg_post_out, logg_prop_out, mean_out, cov_out and ldh is NaN; the call returns MI_OK.
+ *   C  z^(i) = the d normals of Philox stream 7 (STREAM_BRIDGE, det_math.hpp) with "chain" i = 0 .. N2 - 1 and draw 0: element 8 b + 4 h + j (j < 4, h < 2)
+ *      is component h of the Box-Muller pair of slot 4 b + j, as for every normal vector of the engine.
+ *      y_a = mu_a + (the fma chain over b = 0 .. a ascending of L_ab * z_b, from +0);  prop_out[a][i] = y_a -- a slab [1][d][N2].
+ *   D  for a column x:  e_a = x_a - mu_a;  w_a = the fma chain over b = 0 .. d - 1 ascending of Pg_ab * e_b, from +0 (row a of Pg AS COMPUTED: symmetry is
+ *      not assumed);  logg(x) = (-0.5 * dot4(e, w)) - ldh, dot4 as defined for mi_mcmc_draws_log_kernel.
+ *      logg_post_out[t - n_fit][c] = logg of column (t, c) of the iteration part;  logg_prop_out[i] = logg of the STORED (rounded) y^(i), not of z.
+ * The products of C and D run on v_mfma_f64_16x16x4_f64 over the stage of mcmc_amd/csrc/draws_product.hpp with the contraction ascending; z is generated
+ * and x centred on the way into LDS; w and L z never reach memory except through prop_out (mcmc_amd/csrc/draws_bridge.hip).  Without prop_out the
+ * proposal is generated and consumed in groups of columns (a multiple of 128; never fewer than 16) whose block [d][g] fits a budget of 2 GiB.  No result depends on the
+ * grouping, a grid, timing or an atomic order.  prop_out ([1][d][N2]), logg_post_out ([n_it][C]) and logg_prop_out ([N2]) are in `mem`; mean_out ([d]),
+ * cov_out ([d * d]) and info (2 doubles: {status, ldh}) are HOST arrays; any may be NULL, not all. */
+int mi_mcmc_bridge_proposal(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t n_fit, uint64_t n_prop, uint64_t seed,
+                            double* prop_out,       /* [1][d][N2] in `mem`, may be NULL */
+                            double* logg_post_out,  /* [n_it][C] in `mem`, may be NULL */
+                            double* logg_prop_out,  /* [N2] in `mem`, may be NULL */
+                            double* mean_out,       /* HOST, [d], may be NULL */
+                            double* cov_out,        /* HOST, [d * d], may be NULL */
+                            double* info,           /* HOST, 2 doubles {status, ldh}, may be NULL */
+                            void* stream);
+
+/* mi_mcmc_bridge_estimate: the iterative bridge estimator from the four log-density arrays, all in `mem`: logp_post, logg_post ([n_it][C]: the target's
+ * log-kernel and the proposal's log-density at the iteration part) and logp_prop, logg_prop ([N2]: the same at the proposal draws).  n_prop 0: N1;
+ * n_eff 0: (double)N1 -- the effective size of the iteration part, where the caller knows it; tol 0: 1e-10; max_iter 0: 1000.
+ * DEFINITION (fp64, every operation rounded once, nothing contracted; exp / log: det_math.hpp; division: IEEE):
+ *   setup      l1_j = logp_post_j - logg_post_j;  l2_i = logp_prop_i - logg_prop_i;  l* = the type-7 median of l1: mi_mcmc_draws_quantiles with p = 0.5 on
+ *              the slab [n_it][1][C], the same bits;  s1 = n_eff / (n_eff + (double)N2);  s2 = (double)N2 / (n_eff + (double)N2);
+ *              a_i = exp(l2_i - l*);  b_j = exp(l1_j - l*)
+ *   SUMP(v)    the sum over the pieces of 16 384 values, ascending from +0, of SUM(piece) -- SUM the 256-slot sum, and the whole the body fold, of
+ *              mi_mcmc_draws_psis_loo
+ *   iteration  r = 1, it = 0; then:  num = SUMP_i(a_i / (s1 * a_i + s2 * r)) / (double)N2;  den = SUMP_j(1 / (s1 * b_j + s2 * r)) / (double)N1;
+ *              r' = num / den;  it = it + 1;  rel = |r' - r| / |r'|;  r = r';  stop with status 3 when r is not finite or not > 0, else with status 0
+ *              when rel <= tol, else with status 2 when it = max_iter
+ *   logml      log(r) + l*
+ *   errors     at the final r:  f1_i = a_i / (s1 * a_i + s2 * r);  f2_j = 1 / (s1 * b_j + s2 * r).  (mean, M2) of each by THE ORDER of mi_mcmc_draws_waic:
+ *              chunks of 2 048, the chunk's first value as shift, 64 slots (S1, S2), tree, chunk moments, merge.
+ *              cv1 = (M2_1 / (double)(N2 - 1)) / ((mean_1 * mean_1) * (double)N2);  cv2 likewise with f2 and N1
+ *   summary    {logml, status, it, rel, l*, cv1, cv2, (double)N2}
+ * f2_out ([n_it][C] in `mem`, may be NULL) = f2: a slab [n_it][1][C] that mi_mcmc_draw_stats takes with d = 1; with its ESS per chain the caller forms
+ * Fruehwirth-Schnatter's relative mean-squared error of the estimate of Z, cv1 + ((double)n_it / ESS) * cv2 (= cv1 + (N1 / (C ESS)) * cv2), whose root
+ * is the approximate standard error of logml.  Non-finite inputs propagate by the IEEE rules through exactly these expressions: l2 = -inf contributes 0,
+ * nothing is filtered.  The pieces and chunks are workgroups; the host adds them in ascending order: no result depends on a grid, timing or an
+ * atomic order.  The numpy statement of all three entries is mcmc_amd/bridge.py. */
+int mi_mcmc_bridge_estimate(const double* logp_post, const double* logg_post, const double* logp_prop, const double* logg_prop, int32_t mem,
+                            uint64_t n_it, uint64_t n_chains, uint64_t n_prop, double n_eff, double tol, uint64_t max_iter,
+                            double* f2_out,   /* [n_it][C] in `mem`, may be NULL */
+                            double* summary,  /* HOST, 8 doubles, may be NULL */
+                            void* stream);
+
+/* mi_mcmc_draws_bridge: the two entries above composed with logp = mi_mcmc_draws_log_kernel's DEFINITION, on the iteration part and on the proposal
+ * draws (generated and consumed in groups, never copied out): the bits are those of making the three calls by hand.  d = target->d; target->prec / X / y
+ * live in target->mem.  Targets: ISO / DIAG / DENSE / LOGISTIC -- their support is R^d.  MI_ERR_UNSUPPORTED: MI_TARGET_NORMAL_MODEL (sigma > 0: a Gaussian
+ * proposal leaves the support) and MI_TARGET_GAUSS_MIXTURE.  status 1 of the proposal: summary = {NaN, 1, NaN, NaN, NaN, NaN, NaN, (double)N2}, f2_out,
+ * mean_out and cov_out NaN, MI_OK. */
+int mi_mcmc_draws_bridge(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, uint64_t n_fit, uint64_t n_prop,
+                         uint64_t seed, double n_eff, double tol, uint64_t max_iter,
+                         double* f2_out,    /* [n_it][C] in `mem`, may be NULL */
+                         double* mean_out,  /* HOST, [d], may be NULL */
+                         double* cov_out,   /* HOST, [d * d], may be NULL */
+                         double* summary,   /* HOST, 8 doubles, may be NULL */
+                         void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

@@ -96,6 +96,7 @@ EXPORTS = [
     "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
     "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic", "mi_mcmc_draws_psis_loo",
     "mi_mcmc_loglik_waic", "mi_mcmc_loglik_psis_loo",
+    "mi_mcmc_bridge_proposal", "mi_mcmc_bridge_estimate", "mi_mcmc_draws_bridge",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -1009,3 +1010,86 @@ def test_loglik_plan(layout, n_rows, n_keep, n_chains, mat_host=True, psis=True)
     lib().mi_mcmc_test_loglik_plan(C.c_int32(int(layout)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
                                    C.c_int(int(bool(mat_host))), C.c_int(int(bool(psis))), o)
     return dict(zip(("n_chunks", "fold_grid", "M", "m", "sort_rows", "sort_groups", "tail_route", "ws_bytes"), (int(v) for v in o)))
+
+
+BRIDGE_SUMMARY = ("logml", "status", "it", "rel", "lstar", "cv1", "cv2", "n_prop")
+
+
+def _bridge_summary(summ):
+    return None if summ is None else dict(zip(BRIDGE_SUMMARY, (float(v) for v in summ)))
+
+
+def bridge_proposal(draws, n_fit=0, n_prop=0, seed=0, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_prop=True, want_logg_post=True,
+                    want_logg_prop=True, want_mean=True, want_cov=True, prop=None, logg_post=None, logg_prop=None):
+    """mi_mcmc_bridge_proposal: the Gaussian proposal of bridge sampling, fitted to rows t < n_fit (0: n_keep // 2) of a slab [n_keep, d, C] -- n_prop (0: as
+    many as the iteration part has samples) draws of it (prop [1, d, N2]), its log-density at the iteration part (logg_post [n_it, C]) and at its own draws
+    (logg_prop [N2]), the fitted mean and cov, status (1: the fit is singular or not finite, every other output NaN) and ldh.  A numpy slab, or a device
+    tensor / pointer with mem=MEM_DEVICE, explicit shape and device tensors `prop`, `logg_post`, `logg_prop` for what is wanted of them.  The call always
+    waits.  include/mi_mcmc.h states every value bit for bit, mcmc_amd.bridge repeats it in numpy.  A target of the caller's own evaluates its log-kernel on
+    prop and on the iteration part and hands the four arrays to bridge_estimate.  Returns a dict; what was not asked for is None."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    nf = int(n_fit) if n_fit else n_keep // 2
+    n_it = n_keep - nf
+    N2 = int(n_prop) if n_prop else n_it * n_chains
+    if mem == MEM_HOST:
+        prop = np.zeros((1, d, N2)) if want_prop else None
+        logg_post = np.zeros((max(n_it, 0), n_chains)) if want_logg_post else None
+        logg_prop = np.zeros(N2) if want_logg_prop else None
+    mean = np.zeros(d) if want_mean else None
+    cov = np.zeros((d, d)) if want_cov else None
+    info = np.zeros(2)
+    _check(lib().mi_mcmc_bridge_proposal(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint64(int(n_fit)),
+                                         C.c_uint64(int(n_prop)), C.c_uint64(int(seed)), C.c_void_p(_ptr(prop)), C.c_void_p(_ptr(logg_post)), C.c_void_p(_ptr(logg_prop)),
+                                         C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(info.ctypes.data), C.c_void_p(stream or 0)))
+    return dict(prop=prop, logg_post=logg_post, logg_prop=logg_prop, mean=mean, cov=cov, status=int(info[0]), ldh=float(info[1]))
+
+
+def bridge_estimate(logp_post, logg_post, logp_prop, logg_prop, n_it=None, n_chains=None, n_prop=0, n_eff=0.0, tol=0.0, max_iter=0, mem=MEM_HOST, stream=None,
+                    want_f2=True, f2=None):
+    """mi_mcmc_bridge_estimate: the iterative bridge-sampling estimate of the log marginal likelihood from the target's log-kernel (logp) and the proposal's
+    log-density (logg) at the iteration part ([n_it, C]) and at the proposal draws ([N2]) -- numpy arrays, or device tensors / pointers with mem=MEM_DEVICE,
+    explicit n_it, n_chains and n_prop and a device `f2` where wanted.  n_eff 0: N1; tol 0: 1e-10; max_iter 0: 1000.  The call always waits.  Returns a dict
+    of f2 ([n_it, C]: as [n_it, 1, C] a slab that draw_stats takes) and summary (a dict of logml, status -- 0 converged, 2 max_iter, 3 r not positive and
+    finite --, it, rel, lstar, cv1, cv2, n_prop); the relative mean-squared error of the estimate is cv1 + (n_it / ESS) * cv2 with draw_stats' ESS of f2."""
+    if mem == MEM_HOST:
+        logp_post, logg_post = (np.ascontiguousarray(a, dtype=np.float64) for a in (logp_post, logg_post))
+        logp_prop, logg_prop = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (logp_prop, logg_prop))
+        if logp_post.ndim != 2 or logg_post.shape != logp_post.shape or logg_prop.shape != logp_prop.shape:
+            raise ValueError("logp_post and logg_post are [n_it, C], logp_prop and logg_prop [N2]")
+        n_it, n_chains = logp_post.shape
+        n_prop = logp_prop.size
+        f2 = np.zeros((n_it, n_chains)) if want_f2 else None
+    summ = np.zeros(8)
+    _check(lib().mi_mcmc_bridge_estimate(C.c_void_p(_ptr(logp_post)), C.c_void_p(_ptr(logg_post)), C.c_void_p(_ptr(logp_prop)), C.c_void_p(_ptr(logg_prop)), C.c_int32(mem),
+                                         C.c_uint64(int(n_it)), C.c_uint64(int(n_chains)), C.c_uint64(int(n_prop)), C.c_double(float(n_eff)), C.c_double(float(tol)),
+                                         C.c_uint64(int(max_iter)), C.c_void_p(_ptr(f2)), C.c_void_p(summ.ctypes.data), C.c_void_p(stream or 0)))
+    return dict(f2=f2, summary=_bridge_summary(summ))
+
+
+def draws_bridge(target, draws, n_fit=0, n_prop=0, seed=0, n_eff=0.0, tol=0.0, max_iter=0, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_f2=True,
+                 want_mean=True, want_cov=True, f2=None):
+    """mi_mcmc_draws_bridge: the log marginal likelihood log of the integral of the target's kernel by bridge sampling with a Gaussian proposal, from a slab
+    [n_keep, d, C] of posterior draws under `target` (make_target: ISO, DIAG, DENSE or LOGISTIC), on the device -- bridge_proposal, draws_log_kernel on the
+    iteration part and on the proposal draws, and bridge_estimate composed, the same bits.  A numpy slab, or a device tensor / pointer with mem=MEM_DEVICE,
+    explicit n_keep and n_chains and a device `f2` where wanted.  Returns a dict of f2, mean, cov and summary (bridge_estimate's; status 1: the fit is
+    singular or not finite)."""
+    d = int(target.d)
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        n_keep, d_slab, n_chains = draws.shape
+        if d_slab != d:
+            raise ValueError(f"the slab has d = {d_slab}, the target d = {d}")
+        nf = int(n_fit) if n_fit else n_keep // 2
+        f2 = np.zeros((max(n_keep - nf, 0), n_chains)) if want_f2 else None
+    mean = np.zeros(d) if want_mean else None
+    cov = np.zeros((d, d)) if want_cov else None
+    summ = np.zeros(8)
+    _check(lib().mi_mcmc_draws_bridge(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)), C.c_uint64(int(n_fit)),
+                                      C.c_uint64(int(n_prop)), C.c_uint64(int(seed)), C.c_double(float(n_eff)), C.c_double(float(tol)), C.c_uint64(int(max_iter)),
+                                      C.c_void_p(_ptr(f2)), C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(summ.ctypes.data), C.c_void_p(stream or 0)))
+    return dict(f2=f2, mean=mean, cov=cov, summary=_bridge_summary(summ))
+
+
+def test_set_bridge_prop_bytes(n_bytes):
+    """mi_mcmc_test_set_bridge_prop_bytes (TEST HOOK, mi_mcmc_probes.h): the budget of one group of proposal columns of bridge sampling (0 = the real one)."""
+    lib().mi_mcmc_test_set_bridge_prop_bytes(C.c_uint64(int(n_bytes)))

@@ -1,5 +1,5 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
-// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip and draws_loglik.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip and draws_bridge.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <vector>
 
 #include "host_common.hpp"
@@ -21,6 +22,7 @@
 #include "draws_waic.hpp"
 #include "draws_psis.hpp"
 #include "draws_loglik.hpp"
+#include "draws_bridge.hpp"
 
 using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
@@ -974,6 +976,447 @@ int mi_mcmc_loglik_psis_loo(const double* loglik, int32_t layout, int32_t mem, u
         psis_summary(h.data(), h.data() + n_rows, h.data() + 2 * n_rows, n_rows, summary);
     }
     HIP_TRY(hipStreamSynchronize(st));                   // always blocking: the sorts have waited already, and the workspace is read until here
+    return MI_OK;
+}
+
+// ---- bridge sampling (draws_bridge.hip; the arithmetic: include/mi_mcmc.h) ----
+// test hook, declared in mi_mcmc_probes.h: the budget of one group of proposal columns
+static std::atomic<uint64_t> g_bridge_prop_bytes{0};
+void mi_mcmc_test_set_bridge_prop_bytes(uint64_t bytes) { g_bridge_prop_bytes.store(bytes, std::memory_order_relaxed); }
+
+extern "C++" {
+namespace {
+
+using mi::dprod::align256;
+const double BRIDGE_NAN = std::nan("");
+
+// steps A and B of mi_mcmc_bridge_proposal, on the host once the pooled moments are back
+struct BridgeFit {
+    std::vector<double> mu, S, L, Pg;
+    double ldh = 0.0;
+    int status = 0;
+};
+
+bool all_finite(const std::vector<double>& v)
+{
+    for (double x : v)
+        if (!std::isfinite(x)) return false;
+    return true;
+}
+
+// (mu, S) of the prefix slab [n_fit][d][C] by the covariance reducer under a lease of its own (the routines of INV / CHOL_LOWER may use the device), then B
+int bridge_fit(const double* x, uint64_t n_fit, uint64_t d, uint64_t C, hipStream_t st, BridgeFit& f)
+try {
+    f.mu.assign(d, 0.0);
+    f.S.assign(d * d, 0.0);
+    {
+        const mi::dcov::CovPlan plan = mi::dcov::cov_plan(n_fit, d, C, true);
+        WsLease ws;
+        int rc = ws_get(st, plan.bytes, ws);
+        if (rc) return rc;
+        HIP_TRY((hipError_t)mi::dcov::cov_run(x, d, C, plan, ws.p, true, st));
+        HIP_TRY(hipMemcpyAsync(f.mu.data(), ws.as<double>() + plan.o_mean, d * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(f.S.data(), ws.as<double>() + plan.o_cov, d * d * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    f.status = 1;
+    f.ldh = BRIDGE_NAN;
+    if (!all_finite(f.S)) return MI_OK;
+    f.L.assign(d * d, 0.0);
+    f.Pg.assign(d * d, 0.0);
+    int rc = mi_mcmc_mat_cholesky_lower(f.S.data(), d, f.L.data());
+    if (rc) return rc;
+    if ((rc = mi_mcmc_mat_inverse(f.S.data(), d, f.Pg.data()))) return rc;
+    if (!all_finite(f.L) || !all_finite(f.Pg)) return MI_OK;
+    double s = 0.0;
+    for (uint64_t a = 0; a < d; ++a) {
+        const double laa = f.L[a * d + a];
+        if (!(laa > 0.0)) return MI_OK;
+        s = s + mi::det_log(laa);
+    }
+    for (uint64_t a = 0; a < d; ++a)                   // the chain over b = 0 .. a: what lies above the diagonal is zero
+        for (uint64_t b = a + 1; b < d; ++b) f.L[a * d + b] = 0.0;
+    const double half_d = 0.5 * (double)d;
+    const double c = half_d * mi::dprod::LOG_2PI;
+    f.ldh = s + c;
+    f.status = 0;
+    return MI_OK;
+} catch (const std::bad_alloc&) {                      // S, L and Pg are d x d doubles each on the host
+    return fail(MI_ERR_OOM, "bridge sampling: the host has no memory for the %llu x %llu matrices of the fit", (unsigned long long)d, (unsigned long long)d);
+}
+
+// The workspace of steps C and D: the two packed matrices, mu, one d x d upload area, and the block of proposal columns ([d][N2] where the caller wants
+// prop_out, else one group)
+struct BridgePropWs {
+    mi::dbridge::MatPlan mp;
+    uint64_t g = 0;                                    // columns of a group
+    size_t o_packL = 0, o_packP = 0, o_mu = 0, o_tmp = 0, o_y = 0, bytes = 0;
+};
+BridgePropWs bridge_prop_ws(uint64_t d, uint64_t N2, bool whole, bool y_in_ws)
+{
+    BridgePropWs w;
+    w.mp = mi::dbridge::mat_plan(d);
+    w.g = whole ? N2 : std::min<uint64_t>(N2, mi::dbridge::group_cols(d, N2, g_bridge_prop_bytes.load(std::memory_order_relaxed)));
+    w.o_packL = 0;
+    w.o_packP = w.o_packL + w.mp.pack_bytes;
+    w.o_mu = w.o_packP + w.mp.pack_bytes;
+    w.o_tmp = w.o_mu + align256(d * 8);
+    w.o_y = w.o_tmp + align256(d * d * 8);
+    w.bytes = w.o_y + (y_in_ws ? align256((size_t)d * w.g * 8) : 0);
+    return w;
+}
+
+// Steps C and D of a fit with status 0, enqueued on st.  suffix: the iteration part [n_it][d][C]; y_whole: where the whole block [d][N2] goes (the caller's
+// prop_out or its staged image), or NULL: groups in the workspace.  logg_post / logg_prop (device, may be NULL).  per_group(y, col0, g): what else
+// consumes a group, a slab [1][d][g] (may be empty)
+template <class F>
+int bridge_prop_device(const BridgeFit& f, const double* suffix, uint64_t n_it, uint64_t d, uint64_t C, uint64_t N2, uint64_t seed, char* W, const BridgePropWs& w,
+                       double* y_whole, double* logg_post, double* logg_prop, F per_group, hipStream_t st)
+{
+    double* const packL = reinterpret_cast<double*>(W + w.o_packL);
+    double* const packP = reinterpret_cast<double*>(W + w.o_packP);
+    double* const mu = reinterpret_cast<double*>(W + w.o_mu);
+    double* const tmp = reinterpret_cast<double*>(W + w.o_tmp);
+    HIP_TRY(hipMemcpyAsync(mu, f.mu.data(), d * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tmp, f.L.data(), d * d * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY((hipError_t)mi::dbridge::pack_run(w.mp, tmp, packL, st));
+    HIP_TRY(hipMemcpyAsync(tmp, f.Pg.data(), d * d * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY((hipError_t)mi::dbridge::pack_run(w.mp, tmp, packP, st));
+    mi::host::last_kernel() = "bridge_propose_kernel, bridge_logg_kernel";
+    if (logg_post) HIP_TRY((hipError_t)mi::dbridge::logg_run(w.mp, packP, mu, f.ldh, suffix, n_it, C, logg_post, st));
+    for (uint64_t col0 = 0; col0 < N2; col0 += w.g) {
+        const uint64_t g = std::min<uint64_t>(w.g, N2 - col0);
+        double* const y = y_whole ? y_whole : reinterpret_cast<double*>(W + w.o_y);      // (y_whole: one group, g = N2)
+        HIP_TRY((hipError_t)mi::dbridge::propose_run(w.mp, packL, mu, seed, col0, g, g, y, st));
+        if (logg_prop) HIP_TRY((hipError_t)mi::dbridge::logg_run(w.mp, packP, mu, f.ldh, y, 1, g, logg_prop + col0, st));
+        const int rc = per_group(y, col0, g);
+        if (rc) return rc;
+    }
+    return MI_OK;
+}
+
+// The checks the two slab entries of bridge sampling share; they need no device.  *n_fit, *N2: 0 on entry is the default
+int bridge_shape_check(const char* who, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t* n_fit, uint64_t* N2)
+{
+    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (d > mi::dbridge::BRIDGE_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::dbridge::BRIDGE_MAX_D);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL || *N2 > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains / n_prop do not fit 32 bits", who);
+    if (n_keep < 2) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, at least 2 draws are needed (a fit part and an iteration part)", who, (unsigned long long)n_keep);
+    if (*n_fit == 0) *n_fit = n_keep / 2;
+    if (*n_fit >= n_keep) return fail(MI_ERR_BAD_ARG, "%s: n_fit = %llu is not below n_keep = %llu", who, (unsigned long long)*n_fit, (unsigned long long)n_keep);
+    const uint64_t K0 = *n_fit * n_chains, N1 = (n_keep - *n_fit) * n_chains;
+    if (K0 < 2 || N1 < 2) return fail(MI_ERR_BAD_ARG, "%s: K0 = %llu fit samples, N1 = %llu iteration samples: at least 2 of each are needed", who, (unsigned long long)K0, (unsigned long long)N1);
+    if (N1 > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: N1 = %llu iteration samples, must be below 2^32", who, (unsigned long long)N1);
+    if (*N2 == 0) *N2 = N1;
+    if (*N2 < 2) return fail(MI_ERR_BAD_ARG, "%s: n_prop = %llu, at least 2 proposal draws are needed", who, (unsigned long long)*N2);
+    return MI_OK;
+}
+
+int bridge_param_check(const char* who, double n_eff, double tol)
+{
+    if (!(tol >= 0.0)) return fail(MI_ERR_BAD_ARG, "%s: tol = %g is negative or NaN", who, tol);
+    if (!(n_eff >= 0.0)) return fail(MI_ERR_BAD_ARG, "%s: n_eff = %g is negative or NaN", who, n_eff);
+    return MI_OK;
+}
+
+// The workspace of the estimate: l1 -> b [N1], l2 -> a [N2], the selection's own, the pieces' sums, the chunks' (shift, S1, S2)
+struct BridgeEstWs {
+    mi::dsel::SelPlan sel;
+    size_t o_b = 0, o_a = 0, o_sel = 0, o_part = 0, o_stat = 0, bytes = 0;
+};
+BridgeEstWs bridge_est_ws(uint64_t n_it, uint64_t C, uint64_t N2)
+{
+    BridgeEstWs w;
+    const uint64_t N1 = n_it * C;
+    w.sel = mi::dsel::sel_plan(n_it, 1, C, 2);
+    w.o_b = 0;
+    w.o_a = w.o_b + align256(N1 * 8);
+    w.o_sel = w.o_a + align256(N2 * 8);
+    w.o_part = w.o_sel + align256(w.sel.bytes);
+    w.o_stat = w.o_part + align256((mi::dbridge::n_pieces(N1) + mi::dbridge::n_pieces(N2)) * 8);
+    w.bytes = w.o_stat + align256((mi::dbridge::n_chunks(N1) + mi::dbridge::n_chunks(N2)) * 24);
+    return w;
+}
+
+// (mean, M2) of n values from their chunks' (shift, S1, S2): the chunk moments and the merge of mi_mcmc_draws_waic (nothing is fused)
+void bridge_merge(const double* stat, uint64_t n, double* mean_out, double* M2_out)
+{
+    double cnt = 0.0, mean = 0.0, M2 = 0.0;
+    const uint64_t Q = mi::dbridge::n_chunks(n);
+    for (uint64_t b = 0; b < Q; ++b) {
+        const double nb = (double)std::min<uint64_t>(mi::dbridge::BRIDGE_CHUNK, n - b * mi::dbridge::BRIDGE_CHUNK);
+        const double sh = stat[3 * b], S1 = stat[3 * b + 1], S2 = stat[3 * b + 2];
+        const double q1 = S1 / nb;
+        const double mb = sh + q1;
+        const double sq = S1 * S1;
+        const double q2 = sq / nb;
+        const double M2b = S2 - q2;
+        if (b == 0) { cnt = nb; mean = mb; M2 = M2b; continue; }
+        const double delta = mb - mean;
+        const double nn = cnt + nb;
+        const double wgt = nb / nn;
+        const double step = delta * wgt;
+        mean = mean + step;
+        const double both = M2 + M2b;
+        const double d2 = delta * delta;
+        const double prod = cnt * nb;
+        const double frac = prod / nn;
+        const double corr = d2 * frac;
+        M2 = both + corr;
+        cnt = nn;
+    }
+    *mean_out = mean;
+    *M2_out = M2;
+}
+
+// The estimate from four device arrays; f2 (device, may be NULL); summary: 8 doubles on the host.  Blocks: the iteration lives on the host
+int bridge_estimate_device(const double* lp1, const double* lg1, const double* lp2, const double* lg2, uint64_t n_it, uint64_t C, uint64_t N2, double n_eff, double tol,
+                           uint64_t max_iter, char* W, const BridgeEstWs& w, double* f2, double* summary, hipStream_t st)
+{
+    const uint64_t N1 = n_it * C;
+    double* const b = reinterpret_cast<double*>(W + w.o_b);
+    double* const a = reinterpret_cast<double*>(W + w.o_a);
+    double* const part = reinterpret_cast<double*>(W + w.o_part);
+    double* const stat = reinterpret_cast<double*>(W + w.o_stat);
+    if (n_eff == 0.0) n_eff = (double)N1;
+    if (tol == 0.0) tol = 1e-10;
+    if (max_iter == 0) max_iter = 1000;
+    mi::host::last_kernel() = "bridge_pieces_kernel, bridge_moments_kernel";
+    HIP_TRY((hipError_t)mi::dbridge::diff_run(lp1, lg1, N1, b, st));
+    HIP_TRY((hipError_t)mi::dbridge::diff_run(lp2, lg2, N2, a, st));
+    // l*: the two order statistics of the type-7 median of the slab [n_it][1][C]
+    mi::dsel::SelRanks ranks{};
+    double g = 0.0, os[2];
+    type7_ranks(N1, 0.5, &ranks.r[0], &ranks.r[1], &g);
+    HIP_TRY((hipError_t)mi::dsel::sel_run(b, n_it, 1, C, ranks, 2, w.sel, W + w.o_sel, st));
+    HIP_TRY(hipMemcpyAsync(os, W + w.o_sel + w.sel.o_out, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const double lstar = type7_value(os[0], os[1], g);
+    HIP_TRY((hipError_t)mi::dbridge::exp_shift_run(b, N1, lstar, st));
+    HIP_TRY((hipError_t)mi::dbridge::exp_shift_run(a, N2, lstar, st));
+    const double n2 = (double)N2, n1 = (double)N1;
+    const double tot = n_eff + n2;
+    const double s1 = n_eff / tot, s2 = n2 / tot;
+    const uint64_t P2 = mi::dbridge::n_pieces(N2), P1 = mi::dbridge::n_pieces(N1);
+    std::vector<double> ph(P2 + P1);
+    double r = 1.0, rel = BRIDGE_NAN;
+    uint64_t it = 0;
+    int status = 0;
+    for (;;) {
+        HIP_TRY((hipError_t)mi::dbridge::pieces_run(a, N2, b, N1, s1, s2, r, part, st));
+        HIP_TRY(hipMemcpyAsync(ph.data(), part, ph.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        double sa = 0.0, sb = 0.0;
+        for (uint64_t p = 0; p < P2; ++p) sa = sa + ph[p];
+        for (uint64_t p = 0; p < P1; ++p) sb = sb + ph[P2 + p];
+        const double num = sa / n2, den = sb / n1;
+        const double rn = num / den;
+        ++it;
+        const double diff = rn - r;
+        rel = std::fabs(diff) / std::fabs(rn);
+        r = rn;
+        if (!(std::isfinite(r) && r > 0.0)) { status = 3; break; }
+        if (rel <= tol) { status = 0; break; }
+        if (it == max_iter) { status = 2; break; }
+    }
+    HIP_TRY((hipError_t)mi::dbridge::moments_run(a, N2, b, N1, s1, s2, r, stat, f2, st));
+    const uint64_t Q2 = mi::dbridge::n_chunks(N2), Q1 = mi::dbridge::n_chunks(N1);
+    std::vector<double> sh((Q2 + Q1) * 3);
+    HIP_TRY(hipMemcpyAsync(sh.data(), stat, sh.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    double m1, M21, m2, M22;
+    bridge_merge(sh.data(), N2, &m1, &M21);
+    bridge_merge(sh.data() + 3 * Q2, N1, &m2, &M22);
+    const double v1 = M21 / (double)(N2 - 1), v2 = M22 / (double)(N1 - 1);
+    const double mm1 = m1 * m1, mm2 = m2 * m2;
+    const double d1 = mm1 * n2, d2 = mm2 * n1;
+    if (summary) {
+        summary[0] = mi::det_log(r) + lstar;
+        summary[1] = (double)status; summary[2] = (double)it; summary[3] = rel; summary[4] = lstar;
+        summary[5] = v1 / d1; summary[6] = v2 / d2; summary[7] = n2;
+    }
+    return MI_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mi_mcmc_bridge_proposal(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t n_fit, uint64_t n_prop, uint64_t seed,
+                            double* prop_out, double* logg_post_out, double* logg_prop_out, double* mean_out, double* cov_out, double* info, void* stream)
+{
+    const char* who = "bridge_proposal";
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (!prop_out && !logg_post_out && !logg_prop_out && !mean_out && !cov_out && !info) return fail(MI_ERR_BAD_ARG, "%s: all six outputs are NULL, nothing is asked for", who);
+    uint64_t N2 = n_prop;
+    int rc = bridge_shape_check(who, n_keep, d, n_chains, &n_fit, &N2);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t C = n_chains, n_it = n_keep - n_fit, N1 = n_it * C;
+    const bool host = mem == MI_MEM_HOST;
+    DevBuf staged;
+    const double* x = nullptr;
+    if ((rc = stage_slab(draws_kdc, mem, n_keep, d, C, st, staged, &x))) return rc;
+    BridgeFit f;
+    if ((rc = bridge_fit(x, n_fit, d, C, st, f))) return rc;
+    const bool ok = f.status == 0;
+    if (mean_out) for (uint64_t a = 0; a < d; ++a) mean_out[a] = ok ? f.mu[a] : BRIDGE_NAN;
+    if (cov_out) for (uint64_t a = 0; a < d * d; ++a) cov_out[a] = ok ? f.S[a] : BRIDGE_NAN;
+    if (info) { info[0] = (double)f.status; info[1] = f.ldh; }
+    if (!prop_out && !logg_post_out && !logg_prop_out) { HIP_TRY(hipStreamSynchronize(st)); return MI_OK; }
+    if (!ok) {
+        if (host) {
+            if (prop_out) std::fill(prop_out, prop_out + d * N2, BRIDGE_NAN);
+            if (logg_post_out) std::fill(logg_post_out, logg_post_out + N1, BRIDGE_NAN);
+            if (logg_prop_out) std::fill(logg_prop_out, logg_prop_out + N2, BRIDGE_NAN);
+        } else {
+            if (prop_out) HIP_TRY((hipError_t)mi::dbridge::fill_nan_run(prop_out, d * N2, st));
+            if (logg_post_out) HIP_TRY((hipError_t)mi::dbridge::fill_nan_run(logg_post_out, N1, st));
+            if (logg_prop_out) HIP_TRY((hipError_t)mi::dbridge::fill_nan_run(logg_prop_out, N2, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+    const bool whole = prop_out != nullptr;
+    const BridgePropWs w = bridge_prop_ws(d, N2, whole, !whole || host);
+    // behind the proposal's own areas: the staged results of a host call
+    const size_t o_lg1 = w.bytes, o_lg2 = o_lg1 + (host && logg_post_out ? align256(N1 * 8) : 0);
+    const size_t bytes = o_lg2 + (host && logg_prop_out ? align256(N2 * 8) : 0);
+    WsLease ws;
+    if ((rc = ws_get(st, bytes, ws))) return rc;
+    char* W = ws.as<char>();
+    double* const y_whole = !whole ? nullptr : (host ? reinterpret_cast<double*>(W + w.o_y) : prop_out);
+    double* const lg1 = !logg_post_out ? nullptr : (host ? reinterpret_cast<double*>(W + o_lg1) : logg_post_out);
+    double* const lg2 = !logg_prop_out ? nullptr : (host ? reinterpret_cast<double*>(W + o_lg2) : logg_prop_out);
+    rc = bridge_prop_device(f, x + n_fit * d * C, n_it, d, C, N2, seed, W, w, y_whole, lg1, lg2, [](const double*, uint64_t, uint64_t) { return (int)MI_OK; }, st);
+    if (rc) return rc;
+    if (host) {
+        if (prop_out) HIP_TRY(hipMemcpyAsync(prop_out, y_whole, d * N2 * 8, hipMemcpyDeviceToHost, st));
+        if (logg_post_out) HIP_TRY(hipMemcpyAsync(logg_post_out, lg1, N1 * 8, hipMemcpyDeviceToHost, st));
+        if (logg_prop_out) HIP_TRY(hipMemcpyAsync(logg_prop_out, lg2, N2 * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));                   // always blocking: the fit's host arrays, the staged slab and the workspace are ours
+    return MI_OK;
+}
+
+int mi_mcmc_bridge_estimate(const double* logp_post, const double* logg_post, const double* logp_prop, const double* logg_prop, int32_t mem, uint64_t n_it,
+                            uint64_t n_chains, uint64_t n_prop, double n_eff, double tol, uint64_t max_iter, double* f2_out, double* summary, void* stream)
+{
+    const char* who = "bridge_estimate";
+    if (!logp_post || !logg_post || !logp_prop || !logg_prop) return fail(MI_ERR_BAD_ARG, "%s: null input", who);
+    if (!f2_out && !summary) return fail(MI_ERR_BAD_ARG, "%s: f2_out and summary are both NULL, nothing is asked for", who);
+    if (n_it > 0xffffffffULL || n_chains > 0xffffffffULL || n_prop > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_it / n_chains / n_prop do not fit 32 bits", who);
+    const uint64_t C = n_chains, N1 = n_it * C, N2 = n_prop ? n_prop : N1;
+    if (N1 < 2) return fail(MI_ERR_BAD_ARG, "%s: N1 = n_it * n_chains = %llu, at least 2 samples are needed", who, (unsigned long long)N1);
+    if (N1 > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: N1 = %llu iteration samples, must be below 2^32", who, (unsigned long long)N1);
+    if (N2 < 2) return fail(MI_ERR_BAD_ARG, "%s: n_prop = %llu, at least 2 proposal draws are needed", who, (unsigned long long)N2);
+    int rc = bridge_param_check(who, n_eff, tol);
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool host = mem == MI_MEM_HOST;
+    const BridgeEstWs w = bridge_est_ws(n_it, C, N2);
+    // behind the estimate's own areas: the staged inputs and f2 of a host call
+    const size_t a1 = align256(N1 * 8), a2 = align256(N2 * 8);
+    const size_t o_in = w.bytes, o_f2 = o_in + (host ? 2 * a1 + 2 * a2 : 0);
+    const size_t bytes = o_f2 + (host && f2_out ? a1 : 0);
+    WsLease ws;
+    if ((rc = ws_get(st, bytes, ws))) return rc;
+    char* W = ws.as<char>();
+    const double *lp1 = logp_post, *lg1 = logg_post, *lp2 = logp_prop, *lg2 = logg_prop;
+    if (host) {
+        double* in = reinterpret_cast<double*>(W + o_in);
+        HIP_TRY(hipMemcpyAsync(in, logp_post, N1 * 8, hipMemcpyHostToDevice, st)); lp1 = in; in += a1 / 8;
+        HIP_TRY(hipMemcpyAsync(in, logg_post, N1 * 8, hipMemcpyHostToDevice, st)); lg1 = in; in += a1 / 8;
+        HIP_TRY(hipMemcpyAsync(in, logp_prop, N2 * 8, hipMemcpyHostToDevice, st)); lp2 = in; in += a2 / 8;
+        HIP_TRY(hipMemcpyAsync(in, logg_prop, N2 * 8, hipMemcpyHostToDevice, st)); lg2 = in;
+    }
+    double* const f2 = !f2_out ? nullptr : (host ? reinterpret_cast<double*>(W + o_f2) : f2_out);
+    double sum8[8];
+    if ((rc = bridge_estimate_device(lp1, lg1, lp2, lg2, n_it, C, N2, n_eff, tol, max_iter, W, w, f2, sum8, st))) return rc;
+    if (summary) std::memcpy(summary, sum8, sizeof sum8);
+    if (host && f2_out) HIP_TRY(hipMemcpyAsync(f2_out, f2, N1 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MI_OK;
+}
+
+int mi_mcmc_draws_bridge(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, uint64_t n_fit, uint64_t n_prop,
+                         uint64_t seed, double n_eff, double tol, uint64_t max_iter, double* f2_out, double* mean_out, double* cov_out, double* summary, void* stream)
+{
+    const char* who = "draws_bridge";
+    const bool any_out = f2_out || mean_out || cov_out || summary;
+    int rc = target_slab_check(who, target, draws_kdc, n_keep, n_chains, any_out ? nullptr : "f2_out, mean_out, cov_out and summary are all NULL, nothing is asked for", 1,
+                               mi::dbridge::BRIDGE_MAX_D);
+    if (rc) return rc;
+    uint64_t N2 = n_prop;
+    const uint64_t d = target->d, C = n_chains;
+    if ((rc = bridge_shape_check(who, n_keep, d, C, &n_fit, &N2))) return rc;
+    if ((rc = bridge_param_check(who, n_eff, tol))) return rc;
+    switch (target->kind) {
+    case MI_TARGET_GAUSS_ISO: case MI_TARGET_LOGISTIC: break;
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+        if (!target->prec) return fail(MI_ERR_BAD_ARG, "%s: target.prec is NULL", who);
+        break;
+    case MI_TARGET_NORMAL_MODEL:
+        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_NORMAL_MODEL has sigma > 0: a Gaussian proposal leaves its support", who);
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_GAUSS_MIXTURE is not implemented by this reducer", who);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, target->kind);
+    }
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t n_it = n_keep - n_fit, N1 = n_it * C;
+    if (target->kind == MI_TARGET_LOGISTIC && target->n_rows > (1ULL << 38)) return fail(MI_ERR_OOM, "%s: n_rows = %llu do not fit the device memory", who, (unsigned long long)target->n_rows);
+    const bool host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
+    DevBuf staged;
+    const double* x = nullptr;
+    if ((rc = stage_slab(draws_kdc, mem, n_keep, d, C, st, staged, &x))) return rc;
+    BridgeFit f;
+    if ((rc = bridge_fit(x, n_fit, d, C, st, f))) return rc;
+    const bool ok = f.status == 0;
+    if (mean_out) for (uint64_t a = 0; a < d; ++a) mean_out[a] = ok ? f.mu[a] : BRIDGE_NAN;
+    if (cov_out) for (uint64_t a = 0; a < d * d; ++a) cov_out[a] = ok ? f.S[a] : BRIDGE_NAN;
+    if (!ok) {
+        if (summary) { for (int a = 0; a < 8; ++a) summary[a] = BRIDGE_NAN; summary[1] = 1.0; summary[7] = (double)N2; }
+        if (f2_out && host) std::fill(f2_out, f2_out + N1, BRIDGE_NAN);
+        if (f2_out && !host) HIP_TRY((hipError_t)mi::dbridge::fill_nan_run(f2_out, N1, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return MI_OK;
+    }
+    // the workspace: the proposal's, the estimate's, the log-kernel's packed matrix and staged target (its plan with nothing else staged), the four arrays, f2
+    const BridgePropWs pw = bridge_prop_ws(d, N2, false, true);
+    const BridgeEstWs ew = bridge_est_ws(n_it, C, N2);
+    const mi::dlogk::LogkPlan lk = mi::dlogk::logk_plan(target->kind, d, target->n_rows, n_it, C, false, target_host);
+    const size_t a1 = align256(N1 * 8), a2 = align256(N2 * 8);
+    const size_t o_est = pw.bytes, o_lk = o_est + ew.bytes, o_arr = o_lk + align256(lk.bytes), o_f2 = o_arr + 2 * a1 + 2 * a2;
+    const size_t bytes = o_f2 + (host && f2_out ? a1 : 0);
+    WsLease ws;
+    if ((rc = ws_get(st, bytes, ws))) return rc;
+    char* W = ws.as<char>();
+    const double *mat = target->kind == MI_TARGET_LOGISTIC ? target->X : target->prec, *y = target->y, *xs = x;
+    if ((rc = stage_target_slab(W + o_lk, lk.o_mat, lk.o_y, lk.o_slab, lk.mat_doubles, lk.y_doubles, target_host, false, 0, st, &xs, &mat, &y))) return rc;
+    double* const lp1 = reinterpret_cast<double*>(W + o_arr);
+    double* const lg1 = lp1 + a1 / 8;
+    double* const lp2 = lg1 + a1 / 8;
+    double* const lg2 = lp2 + a2 / 8;
+    const double* suffix = x + n_fit * d * C;
+    HIP_TRY((hipError_t)mi::dlogk::logk_pack(lk, mat, W + o_lk, st));                       // once: the iteration part and every proposal group read the same packed matrix
+    HIP_TRY((hipError_t)mi::dlogk::logk_run_packed(lk, suffix, mat, y, W + o_lk, lp1, st));
+    auto logp_group = [&](const double* yg, uint64_t col0, uint64_t g) -> int {
+        const mi::dlogk::LogkPlan gp = mi::dlogk::logk_plan(target->kind, d, target->n_rows, 1, g, false, target_host);      // (the areas of lk: the same d and rows)
+        HIP_TRY((hipError_t)mi::dlogk::logk_run_packed(gp, yg, mat, y, W + o_lk, lp2 + col0, st));
+        return MI_OK;
+    };
+    if ((rc = bridge_prop_device(f, suffix, n_it, d, C, N2, seed, W, pw, nullptr, lg1, lg2, logp_group, st))) return rc;
+    double* const f2 = !f2_out ? nullptr : (host ? reinterpret_cast<double*>(W + o_f2) : f2_out);
+    double sum8[8];
+    if ((rc = bridge_estimate_device(lp1, lg1, lp2, lg2, n_it, C, N2, n_eff, tol, max_iter, W + o_est, ew, f2, sum8, st))) return rc;
+    mi::host::last_kernel() = "bridge_propose_kernel, bridge_logg_kernel, bridge_pieces_kernel, bridge_moments_kernel";
+    if (summary) std::memcpy(summary, sum8, sizeof sum8);
+    if (host && f2_out) HIP_TRY(hipMemcpyAsync(f2_out, f2, N1 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
 

@@ -289,10 +289,23 @@ int logk_run(const LogkPlan& p, const double* x, const double* mat, const double
         else hipLaunchKernelGGL(logk_elem_kernel<LOGK_NORMAL_MODEL>, g, b, 0, st, x, p.d, p.C, p.K, mat, y, p.n_rows, out);
         return (int)hipGetLastError();
     }
+    const int e = logk_pack(p, mat, ws, st);
+    if (e) return e;
+    return logk_run_packed(p, x, mat, y, ws, out, st);
+}
+
+int logk_pack(const LogkPlan& p, const double* mat, void* ws, hipStream_t st)
+{
+    if (p.route != LOGK_ROUTE_PRODUCT) return 0;
+    double* At = reinterpret_cast<double*>(static_cast<char*>(ws) + p.o_pack);
+    return dprod::pack_transposed(mat, p.kind == LOGK_DENSE ? p.d : p.n_rows, p.d, p.Kp, p.ldA, p.pack_grid, At, st);
+}
+
+int logk_run_packed(const LogkPlan& p, const double* x, const double* mat, const double* y, void* ws, double* out, hipStream_t st)
+{
+    if (p.route == LOGK_ROUTE_ELEMENTWISE) return logk_run(p, x, mat, y, ws, out, st);
     double* At = reinterpret_cast<double*>(static_cast<char*>(ws) + p.o_pack);
     const uint64_t rows = p.kind == LOGK_DENSE ? p.d : p.n_rows;
-    const int e = dprod::pack_transposed(mat, rows, p.d, p.Kp, p.ldA, p.pack_grid, At, st);
-    if (e) return e;
     ProdParams prm;
     prm.At = At;
     prm.x = x;

@@ -41,6 +41,10 @@ LogkPlan logk_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
 // enqueues the kernels on `st`.  x, mat (prec / X), y, out: device memory; ws: the workspace (the packed matrix goes to ws + plan.o_pack).
 // Returns a hipError_t as int (0 = enqueued)
 int logk_run(const LogkPlan& plan, const double* x, const double* mat, const double* y, void* ws, double* out, hipStream_t st);
+// the two halves of logk_run for a caller that evaluates several slabs under one target (the plans of one (kind, d, n_rows) share Kp, ldA and o_pack):
+// the pack of the matrix into ws + plan.o_pack (nothing on the elementwise route), and the evaluation of a slab over a matrix packed before
+int logk_pack(const LogkPlan& plan, const double* mat, void* ws, hipStream_t st);
+int logk_run_packed(const LogkPlan& plan, const double* x, const double* mat, const double* y, void* ws, double* out, hipStream_t st);
 
 }  // namespace dlogk
 }  // namespace mi

@@ -102,6 +102,11 @@ void mi_mcmc_test_psis_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t 
  * workgroups, the tail length M, the fit points m, the rows per group of the sort, the sort groups, the tail route (0 LDS, 1 re-read), the workspace
  * bytes; M, m, the rows per group, the groups and the route are 0 for psis == 0. */
 void mi_mcmc_test_loglik_plan(int32_t layout, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int mat_host, int psis, uint64_t* out8);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_bridge_proposal without prop_out and mi_mcmc_draws_bridge (draws_bridge.hpp):
+ * the budget of the block [d][g] of one group of proposal columns in bytes (0, or more than the real budget of 2 GiB = the real budget; a group never has
+ * fewer than 16 columns), so that a test of a few hundred proposal draws runs the loop over groups that a call of gigabytes runs.  Process-wide.
+ * Results do not depend on it. */
+void mi_mcmc_test_set_bridge_prop_bytes(uint64_t bytes);
 #ifdef __cplusplus
 }
 #endif
