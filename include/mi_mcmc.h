@@ -901,6 +901,56 @@ int mi_mcmc_draws_bridge(const mi_target* target, const double* draws_kdc, int32
                          double* summary,   /* HOST, 8 doubles, may be NULL */
                          void* stream);
 
+/* Posterior predictive checks of a slab [n_keep][d][C] (in `mem`; a host slab is staged) under MI_TARGET_LOGISTIC, on the device: at every row r of
+ * target->X and every sample k the success probability p[r][k] and a replicated outcome yrep[r][k] drawn from it, folded BOTH ways -- per row over the
+ * draws (the posterior mean and variance of P(y = 1 | x_r) and the frequency of replicated successes) and per draw over the rows (the test statistic
+ * "number of successes" and the log-likelihood of the replicate and of the observed y), and the posterior predictive p-values of the two (Gelman, Meng
+ * and Stern 1996).  target->X (n_rows x d) / y live in target->mem; X need not be the matrix the chains were sampled on -- held-out rows or a grid of
+ * new covariates will do -- and target->y may be NULL (prediction at covariates with no outcomes): then ll_obs_out and summary must be NULL.
+ * kernel_hint is ignored.  Every output may be NULL; the per-row outputs and the per-draw outputs come from two kernels and only what is asked for is
+ * launched.  Row r of prob_out is a slab [n_keep][1][C] that mi_mcmc_draw_stats, mi_mcmc_draws_quantiles, ... take as it is; so are t_rep_out,
+ * ll_rep_out and ll_obs_out.  A device slab with summary == NULL: the call returns after enqueueing on `stream` (with a target in host memory: once its
+ * arrays have been read).  A device slab with summary, or a host slab: blocking.  Workspace, MI_ERR_NO_DEVICE and MI_ERR_OOM: as mi_mcmc_draws_waic.
+ * MI_ERR_BAD_ARG, before any HIP call: as mi_mcmc_draws_waic (a NULL target or slab; a struct_size mismatch; d 0; n_keep or n_chains beyond 32 bits;
+ * K = n_keep * n_chains < 2; d > 65 536; LOGISTIC without X or with n_rows = 0; an unknown kind), and: all nine outputs NULL; y NULL together with
+ * ll_obs_out or summary; n_rows >= 2^32 (the row index is a slot of the generator).
+ * MI_ERR_UNSUPPORTED: MI_TARGET_NORMAL_MODEL -- left out ON PURPOSE for now: its replicates are normals on an element-wise route, a follow-up; ISO / DIAG /
+ * DENSE / GAUSS_MIXTURE -- they carry no observations.
+ * DEFINITION (fp64, every operation rounded once, nothing contracted; exp / log / sigmoid / softplus, the Philox block rng_block and u01: det_math.hpp).
+ * K = n_keep * C; sample k = t * C + c is column (t, c), x its d values.
+ *   eta[r][k]     the fma chain over j ascending of X_rj * x_j, from +0  -- the bits of mi_mcmc_draws_waic
+ *   p[r][k]       sigmoid(eta):  eta >= 0 ? 1 / (1 + exp(-eta)) : e / (1 + e) with e = exp(eta)
+ *   u[r][k]       u01(w.x, w.y), w = rng_block(seed, chain = k, draw = 0, slot = r, STREAM_PREDICT = 8); w.z and w.w are unused
+ *   yrep[r][k]    (u < p) ? 1.0 : 0.0  -- a NaN p gives 0
+ *   prob_out[r][t][c] = p[r][k];   yrep_out[r][t][c] = yrep[r][k]
+ * PER ROW, over the draws: the section THE ORDER of mi_mcmc_draws_waic, word for word -- chunks of 2048, the chunk's first column as shift, 64 slots,
+ * tree, chunk moments, merge -- with p where ll stood:  sh_b = p[r][2048 b];  v = p - sh_b;  S1 = S1 + v;  S2 = S2 + v * v;  A = A + yrep  (where
+ * A + exp(ll) stood: a sum of zeros and ones, exact in any order).
+ *   p_mean_r = mean;   p_var_r = M2 / (double)(K - 1);   rep_freq_r = A / (double)K
+ * PER DRAW, over the rows: sum4 of mi_mcmc_draws_log_kernel -- four chains q[r % 4], r ascending, each from +0, the result (q0 + q2) + (q1 + q3):
+ *   t_rep_k  = sum4_r(yrep[r][k])                                   the number of replicated successes, an exact integer
+ *   ll_rep_k = sum4_r(yrep[r][k] * eta - softplus(eta))             term_r of mi_mcmc_draws_log_kernel with the replicate as its y
+ *   ll_obs_k = sum4_r(y_r * eta - softplus(eta))                    the bits of the ll part of mi_mcmc_draws_log_kernel's LOGISTIC value
+ * SUMMARY = {t_obs, ppp_t, ppp_dev, t_rep_mean}:  t_obs = the plain sum of y_r over r ascending from +0;  ppp_t = (double)#{k : t_rep_k >= t_obs} /
+ * (double)K;  ppp_dev = (double)#{k : ll_rep_k <= ll_obs_k} / (double)K -- the draws whose replicated deviance is at least the realised one;
+ * t_rep_mean = (double)(sum_k t_rep_k) / (double)K.  The two counts and the integer sum are exact, so their order is free; a comparison with a NaN
+ * counts as false.
+ * Both products run on v_mfma_f64_16x16x4_f64 with the contraction ascending (mcmc_amd/csrc/draws_predict.hip); both kernels form yrep[r][k] from the
+ * same (seed, r, k, bits of eta), so t_rep_out[t][c] is the sum over r of yrep_out[r][t][c], and rep_freq_out[r] the sum over (t, c) divided by K, exactly.
+ * Non-finite draws propagate by the IEEE rules through exactly these expressions, in their own column and nowhere else; the result depends on no
+ * device, grid, timing or atomic order.  The numpy statement is mcmc_amd/predict.py. */
+int mi_mcmc_draws_predict(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, uint64_t seed,
+                          double* p_mean_out,    /* [n_rows] in `mem`, may be NULL */
+                          double* p_var_out,     /* [n_rows] in `mem`, may be NULL */
+                          double* rep_freq_out,  /* [n_rows] in `mem`, may be NULL */
+                          double* prob_out,      /* [n_rows][n_keep][C] in `mem`, may be NULL: row r is a slab [n_keep][1][C] */
+                          double* yrep_out,      /* [n_rows][n_keep][C] in `mem`, 0.0 / 1.0, may be NULL */
+                          double* t_rep_out,     /* [n_keep][C] in `mem`, may be NULL: a slab [n_keep][1][C] */
+                          double* ll_rep_out,    /* [n_keep][C] in `mem`, may be NULL */
+                          double* ll_obs_out,    /* [n_keep][C] in `mem`, may be NULL; needs target->y */
+                          double* summary,       /* HOST, 4 doubles, may be NULL; needs target->y */
+                          void* stream);
+
 /* (The diagnostics the GPU tests and the measurement tools use -- mi_probe_* -- are not part of this library: they live in
  * libmi_mcmc_probes.so, declared in mcmc_amd/csrc/mi_mcmc_probes.h.) */
 

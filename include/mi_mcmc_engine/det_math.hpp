@@ -263,7 +263,8 @@ MI_HD double u01(uint32_t lo, uint32_t hi)
 enum : uint32_t { STREAM_NORMAL = 0u, STREAM_UNIFORM = 1u, STREAM_INIT = 2u,
                   STREAM_DE_INIT = 3u, STREAM_DE = 4u,     // mcmc::de (de.hpp): the initial population / the generations (mi_mcmc.h)
                   STREAM_AEES_NORMAL = 5u, STREAM_AEES = 6u,    // mcmc::aees (aees.hpp): the MH steps' normals / the uniforms (mi_mcmc.h)
-                  STREAM_BRIDGE = 7u };                         // bridge sampling (draws_bridge.hip): the proposal's normals, "chain" = the proposal column, draw 0
+                  STREAM_BRIDGE = 7u,                           // bridge sampling (draws_bridge.hip): the proposal's normals, "chain" = the proposal column, draw 0
+                  STREAM_PREDICT = 8u };                        // posterior predictive replicates (draws_predict.hip): "chain" = the slab's column k, draw 0, slot = the data row
 
 // counter = (chain lo32, draw, slot, stream | chain hi bits << 8), key = seed
 MI_HD u32x4 rng_block(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t slot, uint32_t stream)

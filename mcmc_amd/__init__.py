@@ -97,6 +97,7 @@ EXPORTS = [
     "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic", "mi_mcmc_draws_psis_loo",
     "mi_mcmc_loglik_waic", "mi_mcmc_loglik_psis_loo",
     "mi_mcmc_bridge_proposal", "mi_mcmc_bridge_estimate", "mi_mcmc_draws_bridge",
+    "mi_mcmc_draws_predict",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -276,7 +277,7 @@ def rmhmc_callback(initial_vals, kernel_fn, kernel_data, tensor_fn, tensor_data,
 
 def test_set_grid_cap(max_workgroups):
     """mi_mcmc_test_set_grid_cap (TEST HOOK, mi_mcmc_probes.h): cap the persistent grids of the dynamic-hand-out NUTS kernels and the grid-stride grids of the
-    matrix-product route; 0 = none."""
+    matrix-product route and of draws_predict (its pack and counting kernels); 0 = none."""
     lib().mi_mcmc_test_set_grid_cap(C.c_uint32(int(max_workgroups)))
 
 
@@ -903,6 +904,44 @@ def test_waic_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     lib().mi_mcmc_test_waic_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
                                  C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), C.c_int(int(bool(want_loglik))), o)
     return dict(zip(("route", "chunk", "n_chunks", "grid", "block", "lds_bytes", "ldR", "Kp", "merge_grid", "ws_bytes"), (int(v) for v in o)))
+
+
+def draws_predict(target, draws, seed=0, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_p_mean=True, want_p_var=True, want_rep_freq=True,
+                  want_prob=False, want_yrep=False, want_t_rep=True, want_ll_rep=True, want_ll_obs=None, want_summary=None,
+                  p_mean=None, p_var=None, rep_freq=None, prob=None, yrep=None, t_rep=None, ll_rep=None, ll_obs=None):
+    """mi_mcmc_draws_predict: posterior predictive checks of a slab [n_keep, d, C] under a LOGISTIC `target` (make_target; X are the rows to predict at --
+    held-out data or a grid will do --, y may be None).  Per row r: p_mean[r], p_var[r], the posterior mean and variance of P(y = 1 | x_r), and rep_freq[r],
+    the frequency of replicated successes; on request prob[r, t, c] and the replicates yrep[r, t, c] (0.0 / 1.0) drawn with `seed`.  Per draw: t_rep[t, c]
+    (replicated successes), ll_rep[t, c] and, with y, ll_obs[t, c]; summary = (t_obs, ppp_t, ppp_dev, t_rep_mean), with y.  want_ll_obs / want_summary
+    default to whether the target has y.  A numpy slab, a 2-D [d, C] array being the case n_keep = 1; or a device tensor / pointer with mem=MEM_DEVICE,
+    explicit n_keep and n_chains and device tensors for what is wanted of the eight arrays (written on `stream`; the call waits only where the summary
+    is wanted).  include/mi_mcmc.h states every value bit for bit, mcmc_amd.predict repeats it in numpy.  Returns a dict; what was not asked for is None."""
+    d, n_rows = int(target.d), int(target.n_rows)
+    has_y = bool(target.y)
+    want_ll_obs = has_y if want_ll_obs is None else want_ll_obs
+    want_summary = has_y if want_summary is None else want_summary
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 2:
+            draws = draws[None]
+        n_keep, d_slab, n_chains = draws.shape
+        if d_slab != d:
+            raise ValueError(f"the slab has d = {d_slab}, the target d = {d}")
+        n, Cn = int(n_keep), int(n_chains)
+        p_mean = np.zeros(n_rows) if want_p_mean else None
+        p_var = np.zeros(n_rows) if want_p_var else None
+        rep_freq = np.zeros(n_rows) if want_rep_freq else None
+        prob = np.zeros((n_rows, n, Cn)) if want_prob else None
+        yrep = np.zeros((n_rows, n, Cn)) if want_yrep else None
+        t_rep = np.zeros((n, Cn)) if want_t_rep else None
+        ll_rep = np.zeros((n, Cn)) if want_ll_rep else None
+        ll_obs = np.zeros((n, Cn)) if want_ll_obs else None
+    summ = np.zeros(4) if want_summary else None
+    outs = (p_mean, p_var, rep_freq, prob, yrep, t_rep, ll_rep, ll_obs)
+    _check(lib().mi_mcmc_draws_predict(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
+                                       C.c_uint64(int(seed)), *[C.c_void_p(_ptr(o)) for o in outs], C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    summary = None if summ is None else dict(zip(("t_obs", "ppp_t", "ppp_dev", "t_rep_mean"), (float(v) for v in summ)))
+    return dict(p_mean=p_mean, p_var=p_var, rep_freq=rep_freq, prob=prob, yrep=yrep, t_rep=t_rep, ll_rep=ll_rep, ll_obs=ll_obs, summary=summary)
 
 
 def draws_psis_loo(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stream=None, want_elpd_loo=True, want_pareto_k=True, want_lppd=True, want_summary=True,

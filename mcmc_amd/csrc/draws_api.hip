@@ -1,5 +1,5 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
-// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip and draws_bridge.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip, draws_bridge.hip and draws_predict.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,8 @@
 #include "draws_psis.hpp"
 #include "draws_loglik.hpp"
 #include "draws_bridge.hpp"
+#include "draws_predict.hpp"
+#include "launch_common.hpp"
 
 using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
@@ -585,11 +587,12 @@ int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
     return MI_OK;
 }
 
-// The checks that mi_mcmc_draws_log_kernel, mi_mcmc_draws_waic and mi_mcmc_draws_psis_loo share, in the order in which a call that fails several reports them; they need no
+// The checks that mi_mcmc_draws_log_kernel, mi_mcmc_draws_waic, mi_mcmc_draws_psis_loo and mi_mcmc_draws_predict share, in the order in which a call that fails several reports them; they need no
 // device.  nothing_asked: NULL, or what to say of the call's outputs; the call needs at least min_K samples.  The two targets that carry
-// observations are checked here; what an entry point makes of the other kinds is its own, after this
+// observations are checked here (logistic_y_optional: a logistic target may come without y -- mi_mcmc_draws_predict at new covariates); what an entry
+// point makes of the other kinds is its own, after this
 static int target_slab_check(const char* who, const mi_target* t, const double* draws_kdc, uint64_t n_keep, uint64_t n_chains, const char* nothing_asked,
-                             uint64_t min_K, uint64_t max_d)
+                             uint64_t min_K, uint64_t max_d, bool logistic_y_optional = false)
 {
     if (!t) return fail(MI_ERR_BAD_ARG, "%s: null target", who);
     if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
@@ -604,7 +607,9 @@ static int target_slab_check(const char* who, const mi_target* t, const double* 
         return fail(MI_ERR_BAD_ARG, "%s: K = n_keep * n_chains = %llu, at least %s needed", who, (unsigned long long)(n_keep * n_chains), need);
     }
     if (t->d > max_d) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)t->d, (unsigned long long)max_d);
-    if (t->kind == MI_TARGET_LOGISTIC && (!t->X || !t->y || t->n_rows == 0)) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
+    if (t->kind == MI_TARGET_LOGISTIC && logistic_y_optional) {
+        if (!t->X || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X and n_rows > 0", who);
+    } else if (t->kind == MI_TARGET_LOGISTIC && (!t->X || !t->y || t->n_rows == 0)) return fail(MI_ERR_BAD_ARG, "%s: the logistic target needs X, y and n_rows > 0", who);
     if (t->kind == MI_TARGET_NORMAL_MODEL) {
         if (t->d != 2) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL has d = 2 (mu, sigma), not %llu", who, (unsigned long long)t->d);
         if (!t->y || t->n_rows == 0) return fail(MI_ERR_BAD_ARG, "%s: MI_TARGET_NORMAL_MODEL needs its observations in y and n_rows > 0", who);
@@ -1417,6 +1422,92 @@ int mi_mcmc_draws_bridge(const mi_target* target, const double* draws_kdc, int32
     if (summary) std::memcpy(summary, sum8, sizeof sum8);
     if (host && f2_out) HIP_TRY(hipMemcpyAsync(f2_out, f2, N1 * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return MI_OK;
+}
+
+// Posterior predictive checks of a slab [n_keep][d][C] under the logistic target (draws_predict.hip; the arithmetic: include/mi_mcmc.h).  The slab and the
+// target's arrays are staged into the workspace by the plan, as mi_mcmc_draws_waic stages them.
+int mi_mcmc_draws_predict(const mi_target* target, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t n_chains, uint64_t seed, double* p_mean_out,
+                          double* p_var_out, double* rep_freq_out, double* prob_out, double* yrep_out, double* t_rep_out, double* ll_rep_out, double* ll_obs_out,
+                          double* summary, void* stream)
+{
+    const char* who = "draws_predict";
+    const bool any_out = p_mean_out || p_var_out || rep_freq_out || prob_out || yrep_out || t_rep_out || ll_rep_out || ll_obs_out || summary;
+    int rc = target_slab_check(who, target, draws_kdc, n_keep, n_chains, any_out ? nullptr : "all nine outputs are NULL, nothing is asked for", 2, mi::dpred::PRED_MAX_D, true);
+    if (rc) return rc;
+    switch (target->kind) {
+    case MI_TARGET_LOGISTIC: break;
+    case MI_TARGET_NORMAL_MODEL:
+        return fail(MI_ERR_UNSUPPORTED, "%s: MI_TARGET_NORMAL_MODEL replicates are not implemented by this reducer", who);
+    case MI_TARGET_GAUSS_ISO:
+    case MI_TARGET_GAUSS_DIAG:
+    case MI_TARGET_GAUSS_DENSE:
+    case MI_TARGET_GAUSS_MIXTURE:
+        return fail(MI_ERR_UNSUPPORTED, "%s: target kind %d has no observations: nothing to predict or replicate", who, target->kind);
+    default:
+        return fail(MI_ERR_BAD_ARG, "%s: unknown target kind %d", who, target->kind);
+    }
+    if (!target->y && (ll_obs_out || summary)) return fail(MI_ERR_BAD_ARG, "%s: ll_obs_out and summary need the observations target.y", who);
+    if (target->n_rows > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_rows = %llu does not fit 32 bits (the row is a slot of the generator)", who, (unsigned long long)target->n_rows);
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d, K = n_keep * n_chains, n_rows = target->n_rows;
+    const bool slab_host = mem == MI_MEM_HOST, target_host = target->mem == MI_MEM_HOST;
+    // what keeps the grids, every byte count and the sum of the replicated successes inside their types: beyond any device
+    if (K > (1ULL << 38) || K > (1ULL << 62) / n_rows) return fail(MI_ERR_OOM, "%s: K = %llu columns x n_rows = %llu do not fit the device memory", who, (unsigned long long)K, (unsigned long long)n_rows);
+    mi::dpred::PredictWants w;
+    w.row_stats = p_mean_out || p_var_out || rep_freq_out;
+    w.prob = prob_out != nullptr;
+    w.yrep = yrep_out != nullptr;
+    w.col_stats = t_rep_out || ll_rep_out || ll_obs_out;
+    w.summary = summary != nullptr;
+    const mi::dpred::PredictPlan plan = mi::dpred::predict_plan(d, n_rows, n_keep, n_chains, slab_host, target_host, target->y != nullptr, w, mi::test_grid_cap_now());
+    if ((plan.rows && plan.rows_grid >= (1ULL << 31)) || (plan.cols && plan.cols_grid >= (1ULL << 31)))
+        return fail(MI_ERR_OOM, "%s: %llu chunks x %llu rows do not fit the device memory", who, (unsigned long long)plan.n_chunks, (unsigned long long)n_rows);
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    const double *x = draws_kdc, *mat = target->X, *y = target->y;
+    if ((rc = stage_target_slab(W, plan.o_mat, plan.o_y, plan.o_slab, plan.mat_doubles, plan.y_doubles, target_host, slab_host, K * d, st, &x, &mat, &y))) return rc;
+    double* prob = (slab_host && prob_out) ? reinterpret_cast<double*>(W + plan.o_prob) : prob_out;
+    double* yrep = (slab_host && yrep_out) ? reinterpret_cast<double*>(W + plan.o_yrep) : yrep_out;
+    HIP_TRY((hipError_t)mi::dpred::predict_run(plan, x, mat, y, seed, W, prob, yrep, st));
+    mi::host::last_kernel() = plan.rows && plan.cols ? "predict_rows_kernel, predict_cols_kernel" : (plan.rows ? "predict_rows_kernel" : "predict_cols_kernel");
+    const hipMemcpyKind back = slab_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    double* const row_out[3] = {p_mean_out, p_var_out, rep_freq_out};
+    for (int i = 0; i < 3; ++i)
+        if (row_out[i]) HIP_TRY(hipMemcpyAsync(row_out[i], W + plan.o_rowout + (size_t)i * plan.ldR * 8, n_rows * 8, back, st));
+    double* const col_out[3] = {t_rep_out, ll_rep_out, ll_obs_out};
+    for (int i = 0; i < 3; ++i)
+        if (col_out[i]) HIP_TRY(hipMemcpyAsync(col_out[i], W + plan.o_colout + (size_t)i * K * 8, K * 8, back, st));
+    if (slab_host && prob_out) HIP_TRY(hipMemcpyAsync(prob_out, prob, K * n_rows * 8, hipMemcpyDeviceToHost, st));
+    if (slab_host && yrep_out) HIP_TRY(hipMemcpyAsync(yrep_out, yrep, K * n_rows * 8, hipMemcpyDeviceToHost, st));
+    if (summary) {
+        // t_obs on the host, from the caller's y or a copy of it; the counts over the columns on the device, one piece per workgroup
+        std::vector<double> y_copy;
+        const double* yh = target->y;
+        if (!target_host) {
+            y_copy.resize(n_rows);
+            HIP_TRY(hipMemcpyAsync(y_copy.data(), target->y, n_rows * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            yh = y_copy.data();
+        }
+        double t_obs = 0.0;
+        for (uint64_t r = 0; r < n_rows; ++r) t_obs = t_obs + yh[r];
+        HIP_TRY((hipError_t)mi::dpred::predict_count(plan, t_obs, W, st));
+        std::vector<uint64_t> pieces(3 * plan.count_grid);
+        HIP_TRY(hipMemcpyAsync(pieces.data(), W + plan.o_pieces, pieces.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));               // blocking: summary is written on the host
+        uint64_t n_t = 0, n_dev = 0, sum_t = 0;
+        for (uint64_t g = 0; g < plan.count_grid; ++g) { n_t += pieces[3 * g]; n_dev += pieces[3 * g + 1]; sum_t += pieces[3 * g + 2]; }
+        summary[0] = t_obs;
+        summary[1] = (double)n_t / (double)K;
+        summary[2] = (double)n_dev / (double)K;
+        summary[3] = (double)sum_t / (double)K;
+    } else if (slab_host || target_host) {
+        HIP_TRY(hipStreamSynchronize(st));               // the outputs are the caller's host arrays / the target's host arrays have been read
+    }
     return MI_OK;
 }
 

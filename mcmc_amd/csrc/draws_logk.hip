@@ -98,12 +98,7 @@ LogkPlan logk_plan(int kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint6
 
 namespace {
 
-// (q0 + q2) + (q1 + q3) of the four lane groups' values of column lane & 15, in every lane
-__device__ __forceinline__ double combine4(double q, int c16)
-{
-    const double q0 = __shfl(q, c16), q1 = __shfl(q, c16 + 16), q2 = __shfl(q, c16 + 32), q3 = __shfl(q, c16 + 48);
-    return (q0 + q2) + (q1 + q3);
-}
+using dprod::combine4;     // (q0 + q2) + (q1 + q3) of the four lane groups (draws_product.hpp)
 
 template <int KIND>
 __global__ __launch_bounds__(256) void logk_elem_kernel(const double* __restrict__ x, uint64_t d, uint64_t C, uint64_t K, const double* __restrict__ prec,

@@ -1,4 +1,4 @@
-// draws_product.hpp -- the product stage that draws_logk.hip and draws_waic.hip share: X . Theta (or P . Theta) of a matrix and the K = n_keep * C columns of a
+// draws_product.hpp -- the product stage that draws_logk.hip, draws_waic.hip and draws_predict.hip share: X . Theta (or P . Theta) of a matrix and the K = n_keep * C columns of a
 // draws slab [n_keep][d][C], which the first folds over the rows and the second over the columns.  The matrix is packed once per call, TRANSPOSED and
 // zero-padded, as At [Kp][ld] -- At[j][i] = M[i][j]: a row of At holds, for one contraction index j, the 128 output rows of a tile contiguously.  A staged
 // step is 16 contraction entries: rows 0..15 of a stage are At's 16 rows of the tile, by 16-byte direct-to-LDS loads (issue_a below, as gemm_step_kernel
@@ -111,6 +111,23 @@ __device__ __forceinline__ void mfma_step(const double* As, const double* Bs, do
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) acc[ti][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ti], b[ni], acc[ti][ni], 0, 0, 0);
     }
+}
+
+// v + the values of the lanes c16 ^ 8, ^ 4, ^ 2, ^ 1 in turn: the tree ((0..7) + (8..15)), ... of the 16 column lanes, in every lane
+__device__ __forceinline__ double tree16(double v)
+{
+    v = v + __shfl_xor(v, 8);
+    v = v + __shfl_xor(v, 4);
+    v = v + __shfl_xor(v, 2);
+    v = v + __shfl_xor(v, 1);
+    return v;
+}
+
+// (q0 + q2) + (q1 + q3) of the four lane groups' values of column lane & 15, in every lane
+__device__ __forceinline__ double combine4(double q, int c16)
+{
+    const double q0 = __shfl(q, c16), q1 = __shfl(q, c16 + 16), q2 = __shfl(q, c16 + 32), q3 = __shfl(q, c16 + 48);
+    return (q0 + q2) + (q1 + q3);
 }
 
 }  // namespace dprod

@@ -100,15 +100,7 @@ struct ProdParams {
     uint32_t nkb, n_row_tiles;      // Kp / 16, ldR / 128
 };
 
-// v + the values of the lanes c16 ^ 8, ^ 4, ^ 2, ^ 1 in turn: the tree ((0..7) + (8..15)), ... of the 16 column lanes, in every lane
-__device__ __forceinline__ double tree16(double v)
-{
-    v = v + __shfl_xor(v, 8);
-    v = v + __shfl_xor(v, 4);
-    v = v + __shfl_xor(v, 2);
-    v = v + __shfl_xor(v, 1);
-    return v;
-}
+using dprod::tree16;       // the tree of the 16 column lanes (draws_product.hpp)
 
 __global__ MI_NO_DS_MERGE __launch_bounds__(512) void waic_product_kernel(const ProdParams prm)
 {

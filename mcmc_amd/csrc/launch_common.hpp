@@ -13,6 +13,8 @@ void note_kernel(const char* fmt, ...);
 // the second and later passes of its loop, which otherwise only d K x chains > 16.7 M elements reach.  Kernels that index by workgroup
 // id (the step kernel, the class-wise, normals and prepare kernels) are never capped.  Process-wide; results never depend on it.
 uint64_t test_grid_cap();
+// the cap as it stands now, for a call that is no sampler call and takes no snapshot (draws_api.hip: read once per call, into the plan)
+uint64_t test_grid_cap_now();
 inline uint64_t cap_grid(uint64_t n_wg) { const uint64_t c = test_grid_cap(); return (c != 0 && c < n_wg) ? c : n_wg; }
 }  // namespace mi
 

@@ -138,6 +138,7 @@ void note_kernel(const char* fmt, ...)
 // (sized with one grid, launched with a larger one, the kernel would write point records out of bounds).
 namespace { std::atomic<uint64_t> g_test_grid_cap{0}; thread_local uint64_t t_grid_cap = 0; }
 uint64_t test_grid_cap() { return t_grid_cap; }
+uint64_t test_grid_cap_now() { return g_test_grid_cap.load(std::memory_order_relaxed); }
 namespace { void snapshot_grid_cap() { t_grid_cap = g_test_grid_cap.load(std::memory_order_relaxed); } }
 }  // namespace mi
 

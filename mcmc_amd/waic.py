@@ -75,8 +75,9 @@ def _tree64(u):
     return (u[..., 0] + u[..., 1]) + (u[..., 2] + u[..., 3])
 
 
-def chunk_partials(ll_chunk, math=NUMPY_MATH):
-    """(shift, A, S1, S2), each [n_rows], of one chunk ll_chunk [n_rows, n_b] (n_b <= CHUNK)."""
+def chunk_partials(ll_chunk, math=NUMPY_MATH, third=None):
+    """(shift, A, S1, S2), each [n_rows], of one chunk ll_chunk [n_rows, n_b] (n_b <= CHUNK).  third: None, or the [n_rows, n_b] values that A sums
+    in place of exp(ll) (mcmc_amd.predict: the replicates), in the same slots, order and tree."""
     R, nb = ll_chunk.shape
     sh = ll_chunk[:, 0].copy()
     o = np.arange(nb)
@@ -89,7 +90,11 @@ def chunk_partials(ll_chunk, math=NUMPY_MATH):
     grid[:, q, s] = ll_chunk
     have[q, s] = True
     with np.errstate(over="ignore", invalid="ignore"):
-        ex = np.asarray(_m(math, "exp")(np.ascontiguousarray(grid).ravel())).reshape(grid.shape)
+        if third is None:
+            ex = np.asarray(_m(math, "exp")(np.ascontiguousarray(grid).ravel())).reshape(grid.shape)
+        else:
+            ex = np.zeros((R, nq, SLOTS))
+            ex[:, q, s] = third
         S1 = np.zeros((R, SLOTS))
         S2 = np.zeros((R, SLOTS))
         A = np.zeros((R, SLOTS))
