@@ -554,12 +554,41 @@ int mi_mcmc_draws_to_chain_major_device(const double* draws_kdc_dev, uint64_t n_
  *                          straight from HBM, then passes of 32 and of 48 lags over the dimensions whose sum has not met its first
  *                          non-positive pair yet (a slowly mixing series goes through every pass);
  *   n_keep > 160           (the reference's default is 1 000 kept draws) lags 0..127 from a kernel that streams the series through LDS; the
- *                          acov rows beyond hold NaN and Geyer's sum runs over the computed lags.
+ *                          acov rows beyond hold NaN and Geyer's sum runs over the computed lags (every lag of a long series, and whether
+ *                          the sum ended: mi_mcmc_draw_stats_lags below).
  * Accuracy: every output is that of exact arithmetic on the slab to within a few (n_keep + C) units of roundoff of its own terms -- R-hat to a
  * relative (n_keep + C + 64) 2^-52 as long as the spread of the chain means stays below 1e6 within-chain standard deviations, whatever the
  * means themselves are (DESIGN.md states the bounds; tests/draw_stats_ref.py derives them).  Blocking. */
 int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
                        double* mean, double* acov, double* rhat, double* ess, void* stream);
+
+/* The same reducers with EVERY lag of a series of any length, up to a window the caller sets, on the fp64 matrix cores (mcmc_amd/csrc/draw_stats_lags.hpp,
+ * draws_lags.hip): K = min(max_lag, n_keep - 1), MI_STATS_ALL_LAGS for every lag.  Outputs are HOST arrays, any of them may be NULL (all NULL:
+ * MI_ERR_BAD_ARG):
+ *   mean [d], rhat [d]   as mi_mcmc_draw_stats defines them
+ *   acov [K + 1][d]      exactly K + 1 rows, acov_k = sum_c sum_{t < n - k} v_t v_{t+k} / (C (n - k)); no row is NaN unless the data are non-finite
+ *   ess  [d]             Geyer's initial positive sequence (mcmc_amd/ess.py's loop) over the lags [0, K]: n_keep when n_keep < 4; otherwise
+ *                        rho = acov / acov_0 (acov_0 <= 0: / 1), tau = -1 + 2 sum of the adjacent pairs rho_t + rho_{t+1}, t = 0, 2, .. while t + 1 <= K,
+ *                        stopping before the first pair <= 0; n / max(tau, 1 / n) if tau > 0, else n; at most 10 n
+ *   ended [d]            1: the sum met its non-positive pair inside the window, or K = n_keep - 1, or n_keep < 4 -- more lags would not change ess;
+ *                        0: the window cut the sum.
+ * Any n_keep >= 1 is served.  MI_ERR_BAD_ARG before any HIP call: a NULL slab, a zero size, n_keep or n_chains beyond 32 bits, d > 65 536; no device:
+ * MI_ERR_NO_DEVICE; what does not fit: MI_ERR_OOM.  A host slab is staged.  Blocking.  Device memory: a buffer of the call's own.
+ * HOW.  The lags are diagonal sums of the Gram matrix of the centred series over the chains; one 16 x 16 accumulator of v_mfma_f64_16x16x4_f64 per
+ * block offset delta (rows 16 tb.. against rows 16 (tb + delta)..) holds the lags 16 delta - 15 .. 16 delta + 15, so lags 0 .. K need the offsets
+ * [0, ND), ND = floor((K + 15) / 16) + 1.  BAND SCHEDULE, a function of (n_keep, K) alone: offsets [0, 8), [8, 16), then [16, 32), [32, 48), .. in
+ * bands of 16, the last one cut at ND; one launch per band; after the band [a, b) the lags 0 .. 16 (b - 1) are complete (a lag 16 q + r, r > 0, is
+ * the sum of its part from offset q and its part from offset q + 1, in that order).  With acov == NULL a further band runs only over the dimensions
+ * whose sum has not ended inside the completed lags; with acov every band runs over every dimension.
+ * DETERMINISM.  Every output is a function of the slab and (n_keep, d, C, K) alone: inside a workgroup the partial accumulators are added in a fixed
+ * order, the host adds the G = max(1, min(64, ceil(C / 16), 2^18 / d)) chain groups in ascending order; no atomics.  The bits of mean, rhat, ess,
+ * ended and of every acov_k do not depend on which outputs are NULL nor on which other dimensions are still open.
+ * Non-finite samples propagate by the IEEE rules within their own dimension only.  The numpy statement is mcmc_amd/acov.py. */
+#define MI_STATS_ALL_LAGS 0xffffffffu
+int mi_mcmc_draw_stats_lags(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                            uint32_t max_lag,
+                            double* mean /*[d]*/, double* acov /*[K+1][d]*/, double* rhat /*[d]*/, double* ess /*[d]*/,
+                            uint8_t* ended /*[d]*/, void* stream);
 
 /* Pooled mean and covariance of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: the samples are the K = n_keep * C
  * columns, ordered k = t * C + c.  The chains' current state mi_chains.theta ([d][C]) is the case n_keep = 1.  Outputs are HOST arrays, one
@@ -658,6 +687,13 @@ int mi_mcmc_draws_rank_transform(const double* draws_kdc, int32_t mem, uint64_t 
 int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
                               double* rhat, double* rhat_bulk, double* rhat_tail, double* ess_bulk, double* ess_tail, /* host [d], any may be NULL */
                               void* stream);
+/* mi_mcmc_draw_stats_ranked with mi_mcmc_draw_stats_lags as the reducer of the composed slabs: K = min(max_lag, h - 1), h = floor(n_keep / 2), so the
+ * bulk-ESS and tail-ESS of half-chains longer than 160 draws use every lag.  Argument checks: those of mi_mcmc_draw_stats_ranked (all six outputs
+ * NULL: MI_ERR_BAD_ARG).  ended [d] (host, may be NULL): 1 only if all three ESS sums of the dimension ended -- bulk, the q05 and the q95 indicator. */
+int mi_mcmc_draw_stats_ranked_lags(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                                   uint32_t max_lag,
+                                   double* rhat, double* rhat_bulk, double* rhat_tail, double* ess_bulk, double* ess_tail,
+                                   uint8_t* ended /*[d]*/, void* stream);
 int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z);   /* host arrays, host arithmetic, needs no device */
 
 /* The log-posterior trace of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: out[t][c] = log K(x[t][:][c]), the target's own

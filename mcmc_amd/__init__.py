@@ -98,6 +98,7 @@ EXPORTS = [
     "mi_mcmc_loglik_waic", "mi_mcmc_loglik_psis_loo",
     "mi_mcmc_bridge_proposal", "mi_mcmc_bridge_estimate", "mi_mcmc_draws_bridge",
     "mi_mcmc_draws_predict",
+    "mi_mcmc_draw_stats_lags", "mi_mcmc_draw_stats_ranked_lags",
 ]
 # test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
 PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
@@ -741,6 +742,38 @@ def test_draw_stats_last():
     return dict(zip(("route", "NB", "G", "tiles", "window_launches", "lag_passes", "subset_passes", "smallest_subset"), (int(v) for v in o)))
 
 
+STATS_ALL_LAGS = 0xFFFFFFFF
+
+
+def draw_stats_lags(draws, max_lag=None, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_acov=True):
+    """mi_mcmc_draw_stats_lags: pooled mean [d], autocovariance [K + 1, d] with K = min(max_lag, n_keep - 1) (max_lag=None: every lag), R-hat [d],
+    per-chain ESS [d] over the lags [0, K] and ended [d] (uint8; 0: the window cut Geyer's sum) of a draws slab [n_keep, d, C] of any length, on the
+    fp64 matrix cores (numpy array, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape).  want_acov=False: further bands of lags run
+    only over the dimensions whose sum is still open (acov is None in the result); the other outputs have the same bits.  mcmc_amd.acov is the
+    numpy statement."""
+    if mem == MEM_HOST:
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        n_keep, d, n_chains = draws.shape
+    n_keep, d, n_chains = int(n_keep), int(d), int(n_chains)
+    ml = STATS_ALL_LAGS if max_lag is None else int(max_lag)
+    K = min(ml, max(n_keep, 1) - 1)
+    mean, rhat, ess, ended = np.zeros(d), np.zeros(d), np.zeros(d), np.zeros(d, dtype=np.uint8)
+    acov = np.zeros((K + 1, d)) if want_acov else None
+    _check(lib().mi_mcmc_draw_stats_lags(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint32(ml),
+                                         C.c_void_p(mean.ctypes.data), C.c_void_p(acov.ctypes.data if want_acov else 0), C.c_void_p(rhat.ctypes.data),
+                                         C.c_void_p(ess.ctypes.data), C.c_void_p(ended.ctypes.data), C.c_void_p(stream or 0)))
+    return dict(mean=mean, acov=acov, rhat=rhat, ess=ess, ended=ended)
+
+
+def test_draw_stats_lags_last():
+    """mi_mcmc_test_draw_stats_lags_last (TEST HOOK, mi_mcmc_probes.h): what this thread's last draw_stats_lags call launched -- a dict of ND (block
+    offsets), bands, subset_passes (band passes over a subset of the dimensions), smallest_subset, time_tiles (per series), G (chain groups),
+    tile_chains, K."""
+    o = (C.c_uint64 * 8)()
+    lib().mi_mcmc_test_draw_stats_lags_last(o)
+    return dict(zip(("ND", "bands", "subset_passes", "smallest_subset", "time_tiles", "G", "tile_chains", "K"), (int(v) for v in o)))
+
+
 def draws_covariance(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_mean=True, want_cov=True):
     """mi_mcmc_draws_covariance: pooled mean [d] and covariance [d, d] of the n_keep * C columns of a slab [n_keep, d, C] (numpy array -- a
     2-D [d, C] array is the case n_keep = 1, the chains' state --, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape).
@@ -836,6 +869,19 @@ def draw_stats_ranked(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, s
     res = {k: np.zeros(d) for k in names}
     _check(lib().mi_mcmc_draw_stats_ranked(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
                                            *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(stream or 0)))
+    return res
+
+
+def draw_stats_ranked_lags(draws, max_lag=None, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None):
+    """mi_mcmc_draw_stats_ranked_lags: draw_stats_ranked with every lag of the half-chains up to K = min(max_lag, n_keep // 2 - 1) (max_lag=None: every
+    lag) in the bulk-ESS and the tail-ESS.  Returns a dict of [d] arrays, with ended (uint8): 1 only where all three ESS sums ended."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    names = ("rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail")
+    res = {k: np.zeros(d) for k in names}
+    res["ended"] = np.zeros(d, dtype=np.uint8)
+    ml = STATS_ALL_LAGS if max_lag is None else int(max_lag)
+    _check(lib().mi_mcmc_draw_stats_ranked_lags(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint32(ml),
+                                                *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(res["ended"].ctypes.data), C.c_void_p(stream or 0)))
     return res
 
 

@@ -515,14 +515,19 @@ int mi_mcmc_draws_rank_transform(const double* draws_kdc, int32_t mem, uint64_t 
     return MI_OK;
 }
 
-// Rank-normalised split-R-hat, bulk-ESS and tail-ESS: the pieces above and mi_mcmc_draw_stats on the composed slabs (include/mi_mcmc.h)
-int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* rhat, double* rhat_bulk,
-                              double* rhat_tail, double* ess_bulk, double* ess_tail, void* stream)
+}  // extern "C"
+
+// Rank-normalised split-R-hat, bulk-ESS and tail-ESS: the pieces above and a reducer of the composed slabs [h][nd][2C] on the device, called as
+// reduce(slab, h, nd, C2, rhat or NULL, ess or NULL, ended or NULL) -- mi_mcmc_draw_stats for mi_mcmc_draw_stats_ranked (ended is NULL there),
+// mi_mcmc_draw_stats_lags with the caller's max_lag for mi_mcmc_draw_stats_ranked_lags, where ended[j] = 1 only if all three ESS sums ended
+template <class Reduce>
+static int draw_stats_ranked_run(const char* who, const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* rhat, double* rhat_bulk,
+                                 double* rhat_tail, double* ess_bulk, double* ess_tail, uint8_t* ended, bool has_ended, void* stream, Reduce reduce)
 {
-    const char* who = "draw_stats_ranked";
     int rc = rank_check(who, draws_kdc, n_keep, d, n_chains, MI_RANK_SPLIT);
     if (rc) return rc;
-    if (!rhat && !rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail) return fail(MI_ERR_BAD_ARG, "%s: all five outputs are NULL, nothing is asked for", who);
+    if (!rhat && !rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail && !ended)
+        return fail(MI_ERR_BAD_ARG, has_ended ? "%s: all six outputs are NULL, nothing is asked for" : "%s: all five outputs are NULL, nothing is asked for", who);
     if (n_keep < 4) return fail(MI_ERR_BAD_ARG, "%s: n_keep = %llu, at least 4 draws are needed (two halves of two)", who, (unsigned long long)n_keep);
     if ((rc = need_device())) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -535,9 +540,10 @@ int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_k
     if (rc) return rc;
     char* W = ws.as<char>();
     double* slab = reinterpret_cast<double*>(W + plan.o_slab);
-    const bool want_bulk = rhat || rhat_bulk || ess_bulk, want_fold = rhat || rhat_tail, want_tail = ess_tail != nullptr;
+    const bool want_bulk = rhat || rhat_bulk || ess_bulk || ended, want_fold = rhat || rhat_tail, want_tail = ess_tail || ended;
     std::vector<double> rb(d), rt(d), eb(d), et(d), e05, e95, os, q;
-    std::vector<uint8_t> has_nan(d, 0);
+    std::vector<uint8_t> has_nan(d, 0), en_b, en_05, en_95;
+    if (ended) { en_b.resize(d); std::memset(ended, 1, d); }
     const uint64_t h = plan.h, C2 = 2 * n_chains;
     for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
         const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
@@ -547,23 +553,25 @@ int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_k
         if (rc) return rc;
         if (want_bulk) {
             HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, false, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rb.data() + dim0, ess_bulk ? eb.data() + dim0 : nullptr, stream);
+            rc = reduce(slab, h, nd, C2, rb.data() + dim0, (ess_bulk || ended) ? eb.data() + dim0 : nullptr, ended ? en_b.data() + dim0 : nullptr);
             if (rc) return rc;
         }
         if (want_tail) {
             e05.resize(nd); e95.resize(nd);
+            if (ended) { en_05.resize(nd); en_95.resize(nd); }
             HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 0, W, slab, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e05.data(), stream);
+            rc = reduce(slab, h, nd, C2, nullptr, e05.data(), ended ? en_05.data() : nullptr);
             if (rc) return rc;
             HIP_TRY((hipError_t)mi::drank::rank_indicator_group(x, plan, dim0, nd, 1, W, slab, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, nullptr, e95.data(), stream);
+            rc = reduce(slab, h, nd, C2, nullptr, e95.data(), ended ? en_95.data() : nullptr);
             if (rc) return rc;
             for (uint64_t j = 0; j < nd; ++j) et[dim0 + j] = e95[j] < e05[j] ? e95[j] : e05[j];
+            if (ended) for (uint64_t j = 0; j < nd; ++j) ended[dim0 + j] = (en_b[dim0 + j] && en_05[j] && en_95[j]) ? 1 : 0;
         }
         if (want_fold) {
             HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
             HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, true, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
-            rc = mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, rt.data() + dim0, nullptr, stream);
+            rc = reduce(slab, h, nd, C2, rt.data() + dim0, nullptr, nullptr);
             if (rc) return rc;
         }
     }
@@ -578,6 +586,27 @@ int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_k
         if (ess_tail) ess_tail[i] = bad ? nan : et[i];
     }
     return MI_OK;
+}
+
+extern "C" {
+
+int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, double* rhat, double* rhat_bulk,
+                              double* rhat_tail, double* ess_bulk, double* ess_tail, void* stream)
+{
+    return draw_stats_ranked_run("draw_stats_ranked", draws_kdc, mem, n_keep, d, n_chains, rhat, rhat_bulk, rhat_tail, ess_bulk, ess_tail, nullptr, false, stream,
+                                 [&](const double* slab, uint64_t h, uint64_t nd, uint64_t C2, double* r, double* e, uint8_t*) {
+                                     return mi_mcmc_draw_stats(slab, MI_MEM_DEVICE, h, nd, C2, nullptr, nullptr, r, e, stream);
+                                 });
+}
+
+// ... with every lag up to max_lag of the half-chains (mi_mcmc_draw_stats_lags, draws_lags.hip)
+int mi_mcmc_draw_stats_ranked_lags(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t max_lag, double* rhat,
+                                   double* rhat_bulk, double* rhat_tail, double* ess_bulk, double* ess_tail, uint8_t* ended, void* stream)
+{
+    return draw_stats_ranked_run("draw_stats_ranked_lags", draws_kdc, mem, n_keep, d, n_chains, rhat, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ended, true, stream,
+                                 [&](const double* slab, uint64_t h, uint64_t nd, uint64_t C2, double* r, double* e, uint8_t* en) {
+                                     return mi_mcmc_draw_stats_lags(slab, MI_MEM_DEVICE, h, nd, C2, max_lag, nullptr, nullptr, r, e, en, stream);
+                                 });
 }
 
 int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)

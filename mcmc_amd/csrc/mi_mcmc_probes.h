@@ -80,6 +80,11 @@ void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t 
  * routes), the chain groups G, the 64-chain tiles the largest chain group walked, the window launches, the lag-pass launches (stats_acov_kernel), those of
  * them that ran a subset of the dimensions, and the smallest such subset (0: none).  Host bookkeeping, per thread.  Results do not depend on it. */
 void mi_mcmc_test_draw_stats_last(uint64_t* out8);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats_lags (draw_stats_lags.hpp, draws_lags.hip): what this thread's
+ * last call launched.  out8: the block offsets ND, the bands of the schedule, the band passes that ran over a subset of the dimensions, the smallest
+ * such subset (0: none), the time tiles per series, the chain groups G, the chains per tile (16, or all of a smaller group), the window K.  Host
+ * bookkeeping, per thread.  Results do not depend on it. */
+void mi_mcmc_test_draw_stats_lags_last(uint64_t* out8);
 /* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draws_waic (draws_waic.hpp): the plan of a call, host arithmetic that needs
  * no device.  kind: mi_target_kind (LOGISTIC or NORMAL_MODEL); slab_host / target_host != 0: staged in the workspace; want_loglik != 0: the matrix ll is
  * asked for.  out10: route (0 elementwise, 1 the matrix product), the chunk length in columns, the chunks, workgroups, threads per workgroup, LDS bytes per
