@@ -563,7 +563,7 @@ int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, ui
                        double* mean, double* acov, double* rhat, double* ess, void* stream);
 
 /* The same reducers with EVERY lag of a series of any length, up to a window the caller sets, on the fp64 matrix cores (mcmc_amd/csrc/draw_stats_lags.hpp,
- * draws_lags.hip): K = min(max_lag, n_keep - 1), MI_STATS_ALL_LAGS for every lag.  Outputs are HOST arrays, any of them may be NULL (all NULL:
+ * draw_stats.hip): K = min(max_lag, n_keep - 1), MI_STATS_ALL_LAGS for every lag.  Outputs are HOST arrays, any of them may be NULL (all NULL:
  * MI_ERR_BAD_ARG):
  *   mean [d], rhat [d]   as mi_mcmc_draw_stats defines them
  *   acov [K + 1][d]      exactly K + 1 rows, acov_k = sum_c sum_{t < n - k} v_t v_{t+k} / (C (n - k)); no row is NaN unless the data are non-finite

@@ -742,6 +742,26 @@ def test_draw_stats_last():
     return dict(zip(("route", "NB", "G", "tiles", "window_launches", "lag_passes", "subset_passes", "smallest_subset"), (int(v) for v in o)))
 
 
+def test_stats_host(acov=None, n=None, moments=None, n_chains=None):
+    """mi_mcmc_test_stats_host (TEST HOOK, mi_mcmc_probes.h): the host arithmetic draw_stats and draw_stats_lags share, no device.  acov [nlag, d] of series
+    of n draws -> ess [d], hit [d] (uint8: Geyer's sum over the lags [0, nlag) met its non-positive pair); moments [G, d, 3] of n_chains chains of n draws
+    -> rhat [d].  Returns a dict; what was not asked for is None."""
+    ess = hit = rhat = None
+    nlag = d = G = 0
+    if acov is not None:
+        acov = np.ascontiguousarray(acov, dtype=np.float64)
+        nlag, d = acov.shape
+        ess, hit = np.zeros(d), np.zeros(d, dtype=np.uint8)
+    if moments is not None:
+        moments = np.ascontiguousarray(moments, dtype=np.float64)
+        G, d = moments.shape[:2]
+        rhat = np.zeros(d)
+    ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None else 0)
+    lib().mi_mcmc_test_stats_host(ptr(acov), C.c_uint64(nlag), C.c_uint64(d), C.c_uint64(int(n)), ptr(moments), C.c_uint32(G), C.c_uint64(int(n_chains or 0)),
+                                  ptr(ess), ptr(hit), ptr(rhat))
+    return dict(ess=ess, hit=hit, rhat=rhat)
+
+
 STATS_ALL_LAGS = 0xFFFFFFFF
 
 

@@ -1,12 +1,12 @@
 // draw_stats_lags.hpp -- every autocovariance lag of LONG series of a draws slab [n_keep][d][C], on the fp64 matrix cores (mi_mcmc_draw_stats_lags,
-// draws_lags.hip).  stats_gram_kernel (draw_stats.hpp) keeps one accumulator per block (tb, sb) of G = V V', which stops at n = 128: the upper
+// draw_stats.hip).  stats_gram_kernel (draw_stats.hpp) keeps one accumulator per block (tb, sb) of G = V V', which stops at n = 128: the upper
 // triangle is NB (NB + 1) / 2 blocks of 8 registers.  The lags only need the DIAGONAL sums of G, and those need one 16 x 16 accumulator per block
 // OFFSET delta = sb - tb:
 //     A_delta = sum_tb sum_(chain quads) V_tb V_(tb + delta)',        V_tb = rows [16 tb, 16 tb + 16) of the centred series, 4 chains wide,
 // one v_mfma_f64_16x16x4_f64 per (tb, quad, delta): fragment tb of a quad -- lane l holds v[16 tb + (l & 15)][4 cg + (l >> 4)] -- is the A operand of
 // its own row block and the B operand of the row blocks tb - delta.  With the f64 C/D map col = l & 15, row = (l >> 4) + 4 r, element (row, col) of
 // A_delta belongs to lag 16 delta + col - row: the elements col >= row of A_0 and every element of A_delta, delta >= 1, count each pair (t, t + k) once.
-// Lags 0 .. K need the offsets [0, ND), ND = floor((K + 15) / 16) + 1; the host asks for them in BANDS [d_a, d_b) of at most 16 offsets (draws_lags.hip
+// Lags 0 .. K need the offsets [0, ND), ND = floor((K + 15) / 16) + 1; the host asks for them in BANDS [d_a, d_b) of at most 16 offsets (draw_stats.hip
 // states the schedule), one launch per band, and with acov == NULL only for the dimensions whose Geyer sum is still open.
 //
 // Workgroup = 4 waves, one per SIMD, for (dimension, chain group); it walks its chains in tiles of 16 (wave w owns quad w) and the series in time
@@ -119,22 +119,6 @@ __global__ __launch_bounds__(256, 2) void stats_band_kernel(const double* __rest
         }
         out[(((size_t)g * nd + jj) * NDB + dl) * LAGS_DIAGS + m] = s_;
     }
-}
-
-// partial sums of x - centre[j] (centre == nullptr: of x) over (t = 0, t_step, 2 t_step, ... < n; chains of group g) per dimension: out[g][j]
-// (stats_sum_kernel of draw_stats.hpp, which belongs to another translation unit)
-__global__ __launch_bounds__(64) void stats_lags_sum_kernel(const double* __restrict__ draws, const double* __restrict__ centre, uint32_t n, uint32_t t_step,
-                                                            uint32_t d, uint64_t C, uint32_t G, double* __restrict__ out)
-{
-    const uint32_t j = blockIdx.x, g = blockIdx.y;
-    const double cj = centre ? centre[j] : 0.0;
-    const uint64_t per = (C + G - 1) / G;
-    const uint64_t c_lo = (uint64_t)g * per, c_hi = (c_lo + per < C) ? c_lo + per : C;
-    double s = 0.0;
-    for (uint64_t c = c_lo + threadIdx.x; c < c_hi; c += 64)
-        for (uint32_t t = 0; t < n; t += t_step) s += draws[((size_t)t * d + j) * C + c] - cj;
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-    if (threadIdx.x == 0) out[(size_t)g * d + j] = s;
 }
 
 // The R-hat moments of every dimension: out2[g][j][0..3) = sum over the group's chains of the chain mean m_c of the centred series, of m_c^2 and of the

@@ -1,6 +1,7 @@
-// draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of draw_stats.hpp,
+// draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of
 // draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip, draws_bridge.hip and draws_predict.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
+// mi_mcmc_draw_stats and mi_mcmc_draw_stats_lags are draw_stats.hip; the ranked drivers below reach them through the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +15,6 @@
 #include "host_common.hpp"
 #include "workspace.hpp"
 #include "det_math.hpp"
-#include "draw_stats.hpp"
 #include "draws_cov.hpp"
 #include "draws_select.hpp"
 #include "draws_rank.hpp"
@@ -26,21 +26,9 @@
 #include "draws_predict.hpp"
 #include "launch_common.hpp"
 
-using namespace mi::host;       // fail, need_device, DevBuf (host_common.hpp); WsLease, ws_get (workspace.hpp)
+using namespace mi::host;       // fail, need_device, DevBuf, stage_slab (host_common.hpp); WsLease, ws_get (workspace.hpp)
 
 namespace {
-
-// The slab of a call on the device: the caller's own pointer, or for a host slab a fresh buffer (staged owns it; not the workspace) with the copy
-// enqueued on st.  The buffer dies with the DevBuf, so the caller synchronises the stream before it returns.
-int stage_slab(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, hipStream_t st, DevBuf& staged, const double** x)
-{
-    *x = draws_kdc;
-    if (mem != MI_MEM_HOST) return MI_OK;
-    HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
-    HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
-    *x = staged.as<double>();
-    return MI_OK;
-}
 
 // The type-7 quantile rule, (lo, hi, g) for one probability over S samples and the value from the two order statistics; the arithmetic below IS
 // include/mi_mcmc.h's statement (this file is compiled with -ffp-contract=off: nothing is fused)
@@ -65,10 +53,8 @@ double type7_value(double x_lo, double x_hi, double g)
 extern "C" {
 
 // test hooks, declared in mi_mcmc_probes.h: the workspace budget of the rank transform's groups of dimensions (draws_rank.hpp), the host arithmetic
-// of its group rule and of the plan of mi_mcmc_draws_log_kernel, which need no device, and the host bookkeeping of this thread's last
-// mi_mcmc_draw_stats call (nothing reads it back)
+// of its group rule and of the plan of mi_mcmc_draws_log_kernel, which need no device
 static std::atomic<uint64_t> g_rank_ws_bytes{0};
-static thread_local uint64_t draw_stats_last[8];
 void mi_mcmc_test_set_rank_ws_bytes(uint64_t bytes) { g_rank_ws_bytes.store(bytes, std::memory_order_relaxed); }
 void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes) { mi::drank::rank_counts(sorts, passes); }
 uint64_t mi_mcmc_test_rank_dim_bytes(uint64_t n_keep, uint64_t n_chains, uint32_t flags, int stats)
@@ -84,250 +70,6 @@ void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t 
     const mi::dlogk::LogkPlan p = mi::dlogk::logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host != 0, target_host != 0);
     out8[0] = (uint64_t)p.route; out8[1] = p.grid; out8[2] = p.block; out8[3] = p.lds_bytes;
     out8[4] = p.Kp; out8[5] = p.ldA; out8[6] = p.n_row_tiles; out8[7] = p.bytes;
-}
-void mi_mcmc_test_draw_stats_last(uint64_t* out8)
-{
-    if (out8) std::memcpy(out8, draw_stats_last, sizeof draw_stats_last);
-}
-
-// Pooled mean, autocovariance, R-hat and ESS of every dimension of a slab [n_keep][d][C] (draw_stats.hpp; the definitions: mcmc_amd/ess.py)
-int mi_mcmc_draw_stats(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
-                       double* mean, double* acov, double* rhat, double* ess, void* stream)
-{
-    if (!draws_kdc || n_keep == 0 || d == 0 || n_chains == 0) return fail(MI_ERR_BAD_ARG, "draw_stats: empty input");
-    (void)hipGetLastError();
-    if (n_keep > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "draw_stats: n_keep does not fit 32 bits");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t n = n_keep, C = n_chains;
-    DevBuf staged;
-    const double* x = nullptr;
-    int rc = stage_slab(draws_kdc, mem, n_keep, d, n_chains, st, staged, &x);
-    if (rc) return rc;
-    // chain groups (partials are added in order on the host).  The one-pass Gram kernel (n <= 128) wants few, long workgroups -- its
-    // prologue (first tile) and epilogue (diagonal sums) are per workgroup, and every group is 16 NB x d doubles to fetch --: about 2 048
-    // workgroups in all; the streamed kernels want many short ones.
-    const bool gram = n <= (size_t)mi::STATS_GRAM_MAX_N;
-    const uint32_t G = gram ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(64, (2048 + d - 1) / d), (C + 63) / 64))
-                            : (uint32_t)std::min<uint64_t>(64, (C + 63) / 64);
-    const bool tiled = n > (size_t)mi::STATS_MAX_N;                          // long series: lags below STATS_TILED_LAGS, streamed kernel
-    const size_t nlag_max = tiled ? (size_t)mi::STATS_TILED_LAGS : n;
-    {   // route, NB, G, 64-chain tiles of the largest (first) chain group, window launches, lag passes, lag passes over a subset, smallest subset
-        const uint64_t per = (C + G - 1) / G;
-        uint64_t* const L = draw_stats_last;
-        L[0] = gram ? 0 : (tiled ? 2 : 1); L[1] = gram ? (n + 15) / 16 : 0; L[2] = G; L[3] = (std::min<uint64_t>(per, C) + 63) / 64;
-        L[4] = L[5] = L[6] = L[7] = 0;
-    }
-    const size_t pass_lags = (size_t)mi::STATS_PASS_BLOCKS * mi::STATS_LB;
-    // one device buffer for everything: [G d] sums, [2 d] the centre in two parts, [d] dimension list, [G d 3] moments, [G d max(pass, tiled) lags]
-    const size_t part_lags = tiled ? nlag_max : std::max<size_t>(std::max<size_t>(pass_lags, 16), (n <= (size_t)mi::STATS_GRAM_MAX_N) ? ((n + 15) / 16) * 32 : 0);
-    DevBuf buf;                  // its own buffer, never ws_get(): mi_mcmc_draw_stats_ranked calls this while it holds the stream's lease (workspace.hpp)
-    const size_t o_sum = 0, o_mean = o_sum + (size_t)G * d, o_dims = o_mean + 2 * d, o_mom = o_dims + d, o_part = o_mom + (size_t)G * d * 3;
-    HIP_TRY(buf.alloc((o_part + (size_t)G * d * part_lags) * 8));
-    double* const B = buf.as<double>();
-    // ONE pass over the slab when the Gram kernel serves the request (n <= 128 and more than the mean is asked for): the series are
-    // centred by a PROVISIONAL centre a_j -- the mean over the chains of the FIRST, MIDDLE and LAST kept draw, 3 / n of the slab (the first
-    // draw alone can sit far from the pooled mean when n_burnin is 0 and the chains share a start far from the mode: with e / sigma large
-    // the recentring below would cancel (e / sigma)^2 ulp of the autocovariances) -- and the kernel's row
-    // sums R_t = sum_c (x_t - a) move the centre to the pooled mean afterwards (exactly, in the algebra):  sum_c sum_t (v_t - e)(v_{t+k} - e) = S_k - e (sum_{t < n-k} R_t + sum_{t >= k} R_t) + C (n - k) e^2,
-    // e = pooled mean - a.
-    // The other routes (n > 128) read the slab once for the pooled mean and then run the lag kernels, which centre as they load.  Their centre has
-    // TWO parts, v = (x - a_j) - e_j: the same provisional a_j, and e_j = the mean of x - a_j over the whole slab.  One double cannot hold the
-    // pooled mean to better than |mean| 2^-53 -- 1e-8 standard deviations at mean = 1e8, sd = 1 --, and series centred that far off carry the
-    // error, times their partial sums, into every autocovariance; x - a_j is exact where it matters (x near a_j) and e_j is small.
-    const bool stats = acov || rhat || ess;
-    const bool one_pass = gram && stats;
-    const uint32_t t_step = stats ? (uint32_t)std::max<size_t>(1, (n - 1) / 2) : 1u;         // rows 0, (n-1)/2, 2 ((n-1)/2) [= n-1 or n-2] / every row
-    const uint32_t n_sum = (uint32_t)((n + t_step - 1) / t_step);
-    std::vector<double> part((size_t)G * d), mean_h(d), e_h(d, 0.0);
-    // mean over the rows 0, t_step, ... of x - centre: the G partials added in order
-    auto row_mean = [&](const double* centre, uint32_t step, uint32_t rows, std::vector<double>& dst) -> int {
-        hipLaunchKernelGGL(mi::stats_sum_kernel, dim3((unsigned)d, G), dim3(64), 0, st, x, centre, (uint32_t)n, step, (uint32_t)d, (uint64_t)C, G, B + o_sum);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(part.data(), B + o_sum, part.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t j = 0; j < d; ++j) {
-            double s = 0.0;
-            for (uint32_t g = 0; g < G; ++g) s += part[(size_t)g * d + j];
-            dst[j] = s / ((double)rows * (double)C);
-        }
-        return MI_OK;
-    };
-    if ((rc = row_mean(nullptr, t_step, n_sum, mean_h))) return rc;
-    if (!stats) { if (mean) std::memcpy(mean, mean_h.data(), d * 8); return MI_OK; }
-    HIP_TRY(hipMemcpyAsync(B + o_mean, mean_h.data(), d * 8, hipMemcpyHostToDevice, st));
-    if (!one_pass) {
-        if ((rc = row_mean(B + o_mean, 1u, (uint32_t)n, e_h))) return rc;
-        HIP_TRY(hipMemcpyAsync(B + o_mean + d, e_h.data(), d * 8, hipMemcpyHostToDevice, st));
-        if (mean) for (size_t j = 0; j < d; ++j) mean[j] = mean_h[j] + e_h[j];
-    }
-
-    std::vector<double> ac((size_t)n * d, std::nan(""));     // ac[k * d + j]: pooled over chains, unbiased per lag
-    std::vector<double> mp;                                   // [G][d][3] moments for R-hat
-    // adds the G partials of lags [k_lo, k_lo + cnt) of the listed dimensions (stride `stride` lags per (group, dimension))
-    auto collect = [&](const std::vector<double>& ap, const std::vector<uint32_t>& dl, size_t stride, size_t k_lo, size_t cnt) {
-        const size_t nd = dl.size();
-        for (size_t jj = 0; jj < nd; ++jj)
-            for (size_t k = 0; k < cnt && k_lo + k < nlag_max; ++k) {
-                double s_ = 0.0;
-                for (uint32_t g = 0; g < G; ++g) s_ += ap[((size_t)g * nd + jj) * stride + k];
-                ac[(k_lo + k) * d + dl[jj]] = s_ / (double)C / (double)(n - (k_lo + k));
-            }
-    };
-    // Geyer's initial positive sequence over the lags [0, nlag) (mcmc_amd/ess.py); *ended: the sum met its first non-positive pair
-    // or ran through every lag there is, i.e. more lags would not change it
-    auto geyer = [&](size_t nlag, size_t j, bool* ended) -> double {
-        if (n < 4) { *ended = true; return (double)n; }
-        const double a0 = ac[j];
-        const double den = (a0 > 0.0) ? a0 : 1.0;
-        double tau = -1.0;
-        size_t t = 0;
-        *ended = false;
-        while (t + 1 < nlag) {
-            const double pair = ac[t * d + j] / den + ac[(t + 1) * d + j] / den;
-            if (pair <= 0.0) { *ended = true; break; }
-            tau += 2.0 * pair;
-            t += 2;
-        }
-        if (nlag >= nlag_max) *ended = true;
-        const double e = (tau > 0.0) ? (double)n / std::max(tau, 1.0 / (double)n) : (double)n;
-        return std::min(e, (double)n * 10.0);
-    };
-    std::vector<uint32_t> active(d);
-    for (size_t j = 0; j < d; ++j) active[j] = (uint32_t)j;
-    std::vector<double> ess_h(d, (double)n);
-    size_t computed = 0;                                      // lags [0, computed) are known for the active dimensions
-    auto fetch = [&](std::vector<double>& dst, const double* src, size_t cnt) -> int {
-        dst.resize(cnt);
-        HIP_TRY(hipMemcpyAsync(dst.data(), src, cnt * 8, hipMemcpyDeviceToHost, st));
-        return MI_OK;
-    };
-    auto prune = [&]() {                                      // keep the dimensions whose sum has not ended inside [0, computed)
-        std::vector<uint32_t> next;
-        for (uint32_t j : active) { bool en; ess_h[j] = geyer(computed, j, &en); if (!en) next.push_back(j); }
-        active.swap(next);
-    };
-    std::vector<double> ap;
-    if (tiled) {
-        const size_t lds = (size_t)(mi::STATS_TILE_T + 2 * mi::STATS_TILED_LAGS) * 64 * sizeof(double);
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mi::stats_acov_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(mi::stats_acov_tiled_kernel, dim3((unsigned)d, G), dim3(64), lds, st, x, B + o_mean, (uint32_t)n, (uint32_t)d,
-                           (uint64_t)C, G, B + o_part, B + o_mom);
-        HIP_TRY(hipGetLastError());
-        if ((rc = fetch(ap, B + o_part, (size_t)G * d * nlag_max))) return rc;
-        if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc;
-        HIP_TRY(hipStreamSynchronize(st));
-        collect(ap, active, nlag_max, 0, nlag_max);
-        computed = nlag_max;
-        prune();
-    } else if (gram) {
-        // every lag of every dimension in ONE pass over the slab, on the matrix cores (draw_stats.hpp: stats_gram_kernel)
-        const int nb = (int)((n + 15) / 16);
-        const size_t lds = mi::stats_gram_lds_bytes(nb);
-        auto launch = [&](auto kern) -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)d, G), dim3(512), lds, st, x, B + o_mean, (uint32_t)n, (uint32_t)d, (uint64_t)C, G, B + o_part, B + o_mom);
-            HIP_TRY(hipGetLastError());
-            return MI_OK;
-        };
-        switch (nb) {
-        case 1: rc = launch(mi::stats_gram_kernel<1>); break;
-        case 2: rc = launch(mi::stats_gram_kernel<2>); break;
-        case 3: rc = launch(mi::stats_gram_kernel<3>); break;
-        case 4: rc = launch(mi::stats_gram_kernel<4>); break;
-        case 5: rc = launch(mi::stats_gram_kernel<5>); break;
-        case 6: rc = launch(mi::stats_gram_kernel<6>); break;
-        case 7: rc = launch(mi::stats_gram_kernel<7>); break;
-        default: rc = launch(mi::stats_gram_kernel<8>); break;
-        }
-        if (rc) return rc;
-        const size_t nr = (size_t)16 * nb;
-        if ((rc = fetch(ap, B + o_part, (size_t)G * d * 2 * nr))) return rc;
-        if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc;
-        HIP_TRY(hipStreamSynchronize(st));
-        // move the centre from the provisional a_j (mean_h) to the pooled mean (see above); groups added in order
-        std::vector<double> R(n);
-        for (size_t j = 0; j < d; ++j) {
-            double tot = 0.0;
-            for (size_t t = 0; t < n; ++t) {
-                double r_ = 0.0;
-                for (uint32_t g = 0; g < G; ++g) r_ += ap[((size_t)g * d + j) * 2 * nr + nr + t];
-                R[t] = r_; tot += r_;
-            }
-            const double e = tot / ((double)n * (double)C);
-            double head = tot, tail = tot;                  // sum_{t < n-k} R_t and sum_{t >= k} R_t, k = 0
-            for (size_t k = 0; k < n; ++k) {
-                if (k > 0) { head -= R[n - k]; tail -= R[k - 1]; }
-                double s_ = 0.0;
-                for (uint32_t g = 0; g < G; ++g) s_ += ap[((size_t)g * d + j) * 2 * nr + k];
-                const double cen = s_ - e * (head + tail) + (double)C * (double)(n - k) * e * e;
-                ac[k * d + j] = cen / (double)C / (double)(n - k);
-            }
-            mean_h[j] += e;
-            // (the R-hat moments are sums over chains of the chain mean, its square and the chain variance about the provisional centre:
-            //  the variance of the chain means and the within-chain variances do not depend on the centre)
-        }
-        if (mean) std::memcpy(mean, mean_h.data(), d * 8);
-        computed = n;
-        prune();
-    } else {
-        if (!acov) {
-            // ESS / R-hat only: the first 16 lags (and the moments) straight from HBM at stream speed; a dimension whose Geyer sum ends
-            // inside them is done
-            hipLaunchKernelGGL(mi::stats_window_kernel<16>, dim3((unsigned)d, G), dim3(64), 0, st, x, B + o_mean, (uint32_t)n, (uint32_t)d,
-                               (uint64_t)C, G, B + o_part, B + o_mom);
-            HIP_TRY(hipGetLastError());
-            ++draw_stats_last[4];
-            if ((rc = fetch(ap, B + o_part, (size_t)G * d * 16))) return rc;
-            if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc;
-            HIP_TRY(hipStreamSynchronize(st));
-            collect(ap, active, 16, 0, 16);
-            computed = std::min<size_t>(16, n);
-            prune();
-        }
-        // further lags in passes of up to STATS_PASS_BLOCKS blocks of 16, for the dimensions still open (all of them, every lag, when
-        // the autocovariance itself is asked for)
-        while (!active.empty() && computed < n) {
-            const uint32_t b_lo = (uint32_t)(computed / mi::STATS_LB);
-            const uint32_t b_all = (uint32_t)((n + mi::STATS_LB - 1) / mi::STATS_LB);
-            // (ESS only: the first pass after the 16 streamed lags takes two blocks -- lags 16..47 end most sums of a sampler that mixes)
-            const uint32_t b_hi = std::min<uint32_t>(b_all, b_lo + ((!acov && b_lo == 1) ? 2u : (uint32_t)mi::STATS_PASS_BLOCKS));
-            const size_t npl = (size_t)(b_hi - b_lo) * mi::STATS_LB;
-            const bool all_dims = active.size() == d;
-            const int want_mom = (b_lo == 0) ? 1 : 0;
-            if (!all_dims) HIP_TRY(hipMemcpyAsync(B + o_dims, active.data(), active.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            const size_t lds = (n * 64 + npl * 64) * sizeof(double);
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mi::stats_acov_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(mi::stats_acov_kernel, dim3((unsigned)active.size(), G), dim3(64), lds, st, x, B + o_mean, (uint32_t)n, (uint32_t)d,
-                               (uint64_t)C, G, all_dims ? nullptr : reinterpret_cast<const uint32_t*>(B + o_dims), b_lo, b_hi, want_mom,
-                               B + o_part, B + o_mom);
-            HIP_TRY(hipGetLastError());
-            ++draw_stats_last[5];
-            if (!all_dims) {
-                draw_stats_last[7] = draw_stats_last[6] ? std::min<uint64_t>(draw_stats_last[7], active.size()) : active.size();
-                ++draw_stats_last[6];
-            }
-            if ((rc = fetch(ap, B + o_part, (size_t)G * active.size() * npl))) return rc;
-            if (want_mom) { if ((rc = fetch(mp, B + o_mom, (size_t)G * d * 3))) return rc; }
-            HIP_TRY(hipStreamSynchronize(st));
-            collect(ap, active, npl, (size_t)b_lo * mi::STATS_LB, npl);
-            computed = std::min<size_t>(n, (size_t)b_hi * mi::STATS_LB);
-            if (!acov) prune();
-        }
-        if (acov) { computed = n; prune(); }
-    }
-    if (acov) std::memcpy(acov, ac.data(), ac.size() * 8);
-    if (rhat)
-        for (size_t j = 0; j < d; ++j) {
-            double sm = 0.0, sm2 = 0.0, sv = 0.0;
-            for (uint32_t g = 0; g < G; ++g) { const double* o = &mp[((size_t)g * d + j) * 3]; sm += o[0]; sm2 += o[1]; sv += o[2]; }
-            const double W = sv / (double)C;                                                  // mean within-chain variance
-            const double mbar = sm / (double)C;
-            const double B_over_n = (C > 1) ? (sm2 - (double)C * mbar * mbar) / (double)(C - 1) : 0.0;   // variance of the chain means
-            const double var_plus = ((double)(n - 1) / (double)n) * W + B_over_n;
-            rhat[j] = (W > 0.0) ? std::sqrt(var_plus / W) : 1.0;
-        }
-    if (ess) std::memcpy(ess, ess_h.data(), d * 8);
-    return MI_OK;
 }
 
 // Pooled mean and covariance of the K = n_keep * C columns of a slab [n_keep][d][C] (draws_cov.hip; the arithmetic: include/mi_mcmc.h)
@@ -599,7 +341,7 @@ int mi_mcmc_draw_stats_ranked(const double* draws_kdc, int32_t mem, uint64_t n_k
                                  });
 }
 
-// ... with every lag up to max_lag of the half-chains (mi_mcmc_draw_stats_lags, draws_lags.hip)
+// ... with every lag up to max_lag of the half-chains (mi_mcmc_draw_stats_lags, draw_stats.hip)
 int mi_mcmc_draw_stats_ranked_lags(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint32_t max_lag, double* rhat,
                                    double* rhat_bulk, double* rhat_tail, double* ess_bulk, double* ess_tail, uint8_t* ended, void* stream)
 {
@@ -1537,27 +1279,6 @@ int mi_mcmc_draws_predict(const mi_target* target, const double* draws_kdc, int3
     } else if (slab_host || target_host) {
         HIP_TRY(hipStreamSynchronize(st));               // the outputs are the caller's host arrays / the target's host arrays have been read
     }
-    return MI_OK;
-}
-
-// The device form of mi_mcmc_draws_to_chain_major (stats_collate.hip: the host loops).  It sits here because its kernel is defined in draw_stats.hpp,
-// which one translation unit of the library can include.
-int mi_mcmc_draws_to_chain_major_device(const double* kdc_dev, uint64_t n_keep, uint64_t d, uint64_t C, double* out_dev, void* stream)
-{
-    if (!kdc_dev || !out_dev) return fail(MI_ERR_BAD_ARG, "null buffer");
-    if (n_keep == 0 || d == 0 || C == 0) return MI_OK;
-    if (n_keep > 0xffffffffULL || d > 0x7fffffffULL || (C + 63) / 64 > 65535ULL * 64ULL) return fail(MI_ERR_BAD_ARG, "draws_to_chain_major: shape out of range");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    // grid.y is limited to 65 535: chains in slices of 65 535 tiles
-    const uint64_t tiles = (C + 63) / 64;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += 65535) {
-        const uint64_t nt = std::min<uint64_t>(65535, tiles - t0);
-        const uint64_t c_first = t0 * 64, c_cnt = std::min<uint64_t>(C - c_first, nt * 64);
-        // a slice [c_first, c_first + c_cnt) of the slab has the same row stride C: pass the full C and offset pointers
-        hipLaunchKernelGGL(mi::draws_to_chain_major_slice_kernel, dim3((unsigned)d, (unsigned)nt), dim3(256), 0, st, kdc_dev, (uint32_t)n_keep, (uint32_t)d, C, c_first, c_cnt, out_dev);
-    }
-    HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 

@@ -1,7 +1,7 @@
 // host_common.hpp -- shared by the host-side translation units of the C ABI (mi_mcmc.hip: the samplers; callback_host.hip: the
-// host-callback routes; draws_api.hip: the reducers over a draws slab; stats_collate.hip: multi-GPU collation and the host layout
-// converter; probes.hip: diagnostics): the error channel (status code + thread-local message behind mi_mcmc_last_error), the
-// device probe and the RAII device buffer.  The workspace cache the samplers and the reducers share is workspace.hpp.
+// host-callback routes; draws_api.hip and draw_stats.hip: the reducers over a draws slab; stats_collate.hip: multi-GPU collation and the
+// host layout converter; probes.hip: diagnostics): the error channel (status code + thread-local message behind mi_mcmc_last_error), the
+// device probe, the RAII device buffer and the staging of a host slab.  The workspace cache the samplers and the reducers share is workspace.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,3 +63,21 @@ int literal_run_callback(const char* who, int algo, const double* initial_vals, 
             return ::mi::host::fail(e_ == hipErrorOutOfMemory ? MI_ERR_OOM : MI_ERR_HIP, "%s failed: %s", \
                                     #expr, hipGetErrorString(e_));                                       \
     } while (0)
+
+namespace mi {
+namespace host {
+
+// The slab of a call on the device: the caller's own pointer, or for a host slab a fresh buffer (staged owns it; not the workspace) with the copy
+// enqueued on st.  The buffer dies with the DevBuf, so the caller synchronises the stream before it returns.
+inline int stage_slab(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, hipStream_t st, DevBuf& staged, const double** x)
+{
+    *x = draws_kdc;
+    if (mem != MI_MEM_HOST) return MI_OK;
+    HIP_TRY(staged.alloc(n_keep * d * n_chains * 8));
+    HIP_TRY(hipMemcpyAsync(staged.p, draws_kdc, n_keep * d * n_chains * 8, hipMemcpyHostToDevice, st));
+    *x = staged.as<double>();
+    return MI_OK;
+}
+
+}  // namespace host
+}  // namespace mi

@@ -75,16 +75,23 @@ void mi_mcmc_test_rank_counts(uint64_t* sorts, uint64_t* passes);
  * out8: route (0 one lane per column, 1 the fused matrix product), workgroups, threads per workgroup, LDS bytes per workgroup, the contraction extent Kp,
  * the padded output rows ldA, the row tiles a workgroup walks, the workspace bytes. */
 void mi_mcmc_test_logk_plan(int32_t kind, uint64_t d, uint64_t n_rows, uint64_t n_keep, uint64_t n_chains, int slab_host, int target_host, uint64_t* out8);
-/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats (draw_stats.hpp, draws_api.hip): what this thread's last call
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats (draw_stats.hpp, draw_stats.hip): what this thread's last call
  * launched.  out8: the route (0 the one-pass Gram kernel, 1 the window + lag-block ladder, 2 the streamed kernel), NB of the Gram kernel (0 on the other
  * routes), the chain groups G, the 64-chain tiles the largest chain group walked, the window launches, the lag-pass launches (stats_acov_kernel), those of
  * them that ran a subset of the dimensions, and the smallest such subset (0: none).  Host bookkeeping, per thread.  Results do not depend on it. */
 void mi_mcmc_test_draw_stats_last(uint64_t* out8);
-/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats_lags (draw_stats_lags.hpp, draws_lags.hip): what this thread's
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draw_stats_lags (draw_stats_lags.hpp, draw_stats.hip): what this thread's
  * last call launched.  out8: the block offsets ND, the bands of the schedule, the band passes that ran over a subset of the dimensions, the smallest
  * such subset (0: none), the time tiles per series, the chain groups G, the chains per tile (16, or all of a smaller group), the window K.  Host
  * bookkeeping, per thread.  Results do not depend on it. */
 void mi_mcmc_test_draw_stats_lags_last(uint64_t* out8);
+/* Defined in libmi_mcmc.so itself (a test hook like the ones above), for the host arithmetic that mi_mcmc_draw_stats and mi_mcmc_draw_stats_lags share
+ * (draw_stats_host.hpp).  Inputs and outputs are HOST arrays; no device call is made.  acov [nlag][d] (NULL: ess and hit are left alone): ess[j] = Geyer's
+ * sum of dimension j of a series of n draws over the lags [0, nlag), hit[j] = 1 where it met its first non-positive pair.  moments [G][d][3] (NULL: rhat is
+ * left alone): rhat[j] from the sums over the chains of group g of the chain mean, its square and the chain variance, groups added in ascending order,
+ * of C chains of n draws. */
+void mi_mcmc_test_stats_host(const double* acov, uint64_t nlag, uint64_t d, uint64_t n, const double* moments, uint32_t G, uint64_t C, double* ess, uint8_t* hit,
+                             double* rhat);
 /* Defined in libmi_mcmc.so itself (a test hook like the ones above), for mi_mcmc_draws_waic (draws_waic.hpp): the plan of a call, host arithmetic that needs
  * no device.  kind: mi_target_kind (LOGISTIC or NORMAL_MODEL); slab_host / target_host != 0: staged in the workspace; want_loglik != 0: the matrix ll is
  * asked for.  out10: route (0 elementwise, 1 the matrix product), the chunk length in columns, the chunks, workgroups, threads per workgroup, LDS bytes per

@@ -1,5 +1,5 @@
 // stats_collate.hip -- the multi-GPU helpers of the C ABI (shard arithmetic, RCCL all-gather of the kept draws, merge kernel) and the
-// host layout converter.  The reducers over a draws slab, and the converter's device form, are draws_api.hip.
+// host layout converter.  The reducers over a draws slab are draws_api.hip and draw_stats.hip, where the converter's device form is as well.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -236,7 +236,7 @@ int mi_mcmc_allgather_draws_wait(mi_collation* handle, void* consumer_stream, in
 int mi_mcmc_draws_to_chain_major(const double* kdc, uint64_t n_keep, uint64_t d, uint64_t C, double* out)
 {
     if (!kdc || !out) return fail(MI_ERR_BAD_ARG, "null buffer");
-    // host arrays: blocked over chains so that both sides stay in cache (the device form, in draws_api.hip, is the one for slabs in HBM)
+    // host arrays: blocked over chains so that both sides stay in cache (the device form, in draw_stats.hip, is the one for slabs in HBM)
     constexpr uint64_t CB = 64;
     for (uint64_t c0 = 0; c0 < C; c0 += CB)
         for (uint64_t j = 0; j < d; ++j)
