@@ -478,15 +478,98 @@ int fill_n_leap(uint64_t* dev_ptr, uint64_t n, uint64_t v, hipStream_t st)
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
+int copy_flagged_counts(const uint32_t* flag, const uint64_t* n_leap, uint64_t* n_exec, uint64_t C, hipStream_t st)
+{
+    hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, flag, n_leap, n_exec, C);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+// ---- what every route states once: the target's data on the device, the launch fields all params structs share, the end of a call
+// The matrix of the target in device memory: the n_rows x d design matrix and the labels of MI_TARGET_LOGISTIC (a host target is copied up), the dense
+// d x d precision of the Gaussian kinds (dense_precision_on_device; y stays null).  The copy dies with the owner: a route that owns() one synchronises
+// the stream before it returns.
+struct StagedTarget {
+    DevBuf Xo, yo;
+    const double *mat = nullptr, *y = nullptr;
+    uint64_t n_rows = 0;                                 // (Gaussian kinds: d)
+    bool owns() const { return Xo.p != nullptr; }
+};
+int stage_target(const mi_target* t, StagedTarget& tg, hipStream_t st, uint64_t max_rows = ~0ULL)
+{
+    const uint64_t d = t->d, n = t->n_rows;
+    if (t->kind != MI_TARGET_LOGISTIC) { tg.n_rows = d; return dense_precision_on_device(t, tg.Xo, &tg.mat, st); }
+    if (!t->X || !t->y || n == 0 || n > max_rows) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
+    tg.mat = t->X; tg.y = t->y; tg.n_rows = n;
+    if (t->mem == MI_MEM_HOST) {
+        HIP_TRY(tg.Xo.alloc(n * d * sizeof(double))); HIP_TRY(tg.yo.alloc(n * sizeof(double)));
+        HIP_TRY(hipMemcpy(tg.Xo.p, t->X, n * d * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tg.yo.p, t->y, n * sizeof(double), hipMemcpyHostToDevice));
+        tg.mat = tg.Xo.as<double>(); tg.y = tg.yo.as<double>();
+    }
+    return MI_OK;
+}
+// ... as the literal replay behind such a route reads it: the matrix transposed into tbuf (literal.hpp reads matrices column-major)
+int lit_staged_target(mi::lit::LitTarget& t, const StagedTarget& tg, uint32_t d, double* tbuf, hipStream_t st)
+{
+    const int rc = transpose_on_device(tg.mat, tbuf, (uint32_t)tg.n_rows, d, st);
+    if (rc) return rc;
+    t.d = d;
+    if (tg.y) { t.kind = mi::lit::LIT_LOGISTIC; t.n_rows = (uint32_t)tg.n_rows; t.X = tg.mat; t.y = tg.y; t.Xt = tbuf; }
+    else { t.kind = mi::lit::LIT_DENSE; t.prec = tbuf; }
+    mi::lit::lit_orders(t);
+    return MI_OK;
+}
+
+// the ten fields every params struct has under the same names (what differs in meaning between them -- n_leap, eps / par_scale -- stays with the route)
+template <class P>
+void fill_common(P& p, uint64_t d, const mi_settings* s, const mi_chains* c, const StagedChains& sc)
+{
+    p.d = (uint32_t)d; p.C = c->n_chains; p.chain0 = c->chain0;
+    p.theta = sc.dev.theta; p.draws = sc.dev.draws; p.n_accept = sc.dev.n_accept;
+    p.seed = s->rng_seed_value;
+    p.n_burnin = (uint32_t)s->n_burnin_draws; p.n_keep = (uint32_t)s->n_keep_draws;
+    p.draw0 = (uint32_t)c->draw0;
+}
+// nuts: the continuation rules, the depth and the dual-averaging constants ...
+template <class P>
+int fill_nuts_adapt(P& p, const mi_settings* s, const mi_chains* c)
+{
+    if (int rc = nuts_continuation(s, c, &p.n_adapt)) return rc;
+    p.max_depth = (uint32_t)s->max_tree_depth;
+    p.delta = s->target_accept_rate; p.gamma = s->gamma_val; p.t0 = s->t0_val; p.kappa = s->kappa_val;
+    return MI_OK;
+}
+// ... and its three outputs (GemmNutsRun names them differently: it takes the first half alone)
+template <class P>
+int fill_nuts(P& p, const mi_settings* s, const mi_chains* c, const StagedChains& sc)
+{
+    p.step_out = sc.dev.step_size; p.depth_trace = sc.dev.nuts_depth; p.adapt_state = sc.dev.nuts_adapt_state;
+    return fill_nuts_adapt(p, s, c);
+}
+
+// the end of a route: n_leapfrogs of the samplers whose kernels do not count (fill_n_leap; NO_LEAP_FILL: the kernel counted), the outputs back to a host
+// caller, and the stream idle before anything of `ours` -- a staged target, tables -- dies with the route
+constexpr uint64_t NO_LEAP_FILL = ~0ULL;
+int finish(mi_chains* chains, uint64_t d, const mi_settings* s, StagedChains& sc, hipStream_t st, uint64_t leap_fill, bool ours, uint64_t n_total = 0)
+{
+    int rc;
+    if (leap_fill != NO_LEAP_FILL && (rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, leap_fill, st))) return rc;
+    if ((rc = stage_out(chains, d, s->n_keep_draws, sc, st, n_total))) return rc;
+    if (ours || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
+    return MI_OK;
+}
+uint64_t hmc_leap_total(const mi_settings* s) { return (s->n_burnin_draws + s->n_keep_draws) * s->n_leap_steps; }
 
 // LDS-staged logistic kernels (logistic_lds.hip): workspace from the per-stream cache, launch in their own translation unit
 int launched(const char* what, int hip_err);
 struct LdsTables;
 void lds_tables_replay(const LdsTables& t, const mi::LogitParams& q, mi::lit::LitParams& lp);
 bool lds_tables_active(const LdsTables* t);
-int launch_logit(int algo, mi::LogitParams prm, const double* X_dev, const double* y_dev, hipStream_t st,
-                 const mi_settings* settings, const mi_chains* dev_chains, int lds_target = mi::LOGIT_TARGET_LOGISTIC, const LdsTables* lt = nullptr)
+int launch_logit(int algo, mi::LogitParams prm, const StagedTarget& tg, hipStream_t st,
+                 const mi_settings* settings, const mi_chains* dev_chains, int lds_target, const LdsTables* lt)
 {
+    const double *X_dev = tg.mat, *y_dev = tg.y;
     WsLease base;
     const bool replay = algo != mi::LOGIT_RWMH;          // rwmh forms no product with a vector that can be non-finite (rwmh.cpp:126)
     ReplayWs rp = replay_layout(mi::logit_lds_workspace_bytes(prm.d, prm.NB, prm.C, lds_target), prm.C, prm.d, prm.n_rows, false);
@@ -507,15 +590,8 @@ int launch_logit(int algo, mi::LogitParams prm, const double* X_dev, const doubl
     LitDev ldev;
     if (replay) {                                       // chains that reached the non-finite regime: replayed literally (literal.hpp)
         mi::lit::LitParams lp{};
-        rcw = transpose_on_device(X_dev, rp.tbuf, prm.n_rows, prm.d, st);      // eta = X beta resp. P x read the matrix transposed (literal.hpp)
+        rcw = lit_staged_target(lp.t, tg, prm.d, rp.tbuf, st);      // eta = X beta resp. P x read the matrix transposed (literal.hpp)
         if (rcw) return rcw;
-        if (lds_target == mi::LOGIT_TARGET_DENSE) {
-            lp.t.kind = mi::lit::LIT_DENSE; lp.t.d = prm.d; lp.t.prec = rp.tbuf;
-        } else {
-            lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.d = prm.d; lp.t.n_rows = prm.n_rows; lp.t.X = X_dev; lp.t.y = y_dev;
-            lp.t.Xt = rp.tbuf;
-        }
-        mi::lit::lit_orders(lp.t);
         lit_common(lp, settings, dev_chains, rp, false);
         lp.rs = prm.rs; lp.log_det = prm.log_det; lp.cons_term = prm.cons_term;
         if (dense_m) {                                   // the replay's own copies (transposed: literal_host.hpp)
@@ -632,6 +708,25 @@ void lit_set_chain_mass(mi::lit::LitParams& lp, const double* mass_dev, const Ch
 {
     lp.precond = 1; lp.m = mass_dev; lp.m_sqrt = t.ms.as<double>(); lp.m_inv = t.mi.as<double>(); lp.m_chain_stride = C;
 }
+// the diagonal masses of a plain launch: per chain (mi_chains.mass_diag, [d][C]) or shared (sqrt(m) and 1 / m of a diagonal precond_mat alone, no bounds), or none
+struct HmcMass { ChainMass t; bool per_chain = false, shared = false; };
+template <class P>
+int hmc_mass(HmcMass& hm, P& q, const mi_settings* settings, const StagedChains& sc, bool shared, hipStream_t st)
+{
+    int rc;
+    const uint64_t d = q.d;
+    if (sc.dev.mass_diag) {                              // per-chain tables [d][C]
+        if ((rc = chain_mass_tables(sc.dev.mass_diag, d, q.C, hm.t, st))) return rc;
+        hm.per_chain = true; q.m_per_chain = 1;
+    } else if (shared) {
+        std::vector<double> m(d), m_sqrt(d), m_inv(d);
+        mi::settings::diag_mass(settings->precond_mat, d, m.data(), m_sqrt.data(), m_inv.data());
+        if ((rc = upload_padded(hm.t.ms, m_sqrt.data(), d, d, 1.0)) || (rc = upload_padded(hm.t.mi, m_inv.data(), d, d, 1.0))) return rc;
+        hm.shared = true;
+    } else return MI_OK;
+    q.m_sqrt = hm.t.ms.as<double>(); q.m_inv = hm.t.mi.as<double>();
+    return MI_OK;
+}
 
 // the target of a literal kernel (literal.hpp: LitTarget) in device memory: a host-memory target is staged into a / b, a matrix the literal
 // kernels read transposed into t_t.  The buffers must outlive the launch.
@@ -730,18 +825,10 @@ int run_literal(const char* who, int algo, const mi_target* target, const mi_set
         if ((rc = chain_mass_tables(sc.dev.mass_diag, d, C, cm, st))) return rc;
         lit_set_chain_mass(lp, sc.dev.mass_diag, cm, C);
     }
-    if (algo == 2) {
-        if ((rc = nuts_continuation(settings, chains, &lp.n_adapt))) return rc;
-        lp.max_depth = (uint32_t)settings->max_tree_depth;
-        lp.delta = settings->target_accept_rate; lp.gamma = settings->gamma_val; lp.t0 = settings->t0_val; lp.kappa = settings->kappa_val;
-        lp.step_out = sc.dev.step_size; lp.depth_trace = sc.dev.nuts_depth; lp.adapt_state = sc.dev.nuts_adapt_state;
-    }
+    if (algo == 2 && (rc = fill_nuts(lp, settings, chains, sc))) return rc;
     rc = launched(who, mi::launch_literal(algo, lp, rp.n_wg, st));
     if (rc) return rc;
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
-    if (rc) return rc;
-    if (t_a.p || t_b.p || t_t.p || ldev.any || cm.ms.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, t_a.p || t_b.p || t_t.p || ldev.any || cm.ms.p, n_total);
 }
 
 
@@ -868,76 +955,26 @@ bool lds_general_ok(const mi_target* target, const mi_settings* settings)
     return target->kernel_hint != MI_KERNEL_LITERAL && (!settings->precond_mat || precond_is_diagonal(settings, target->d));
 }
 
-// hmc / rwmh on the logistic-regression target (identity preconditioner / cov_mat, no bounds): logit_lds_kernel<., HMC | RWMH>;
-// settings->step_size is the leapfrog step resp. par_scale
-int run_logit_plain(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
+// hmc / mala / rwmh on the LDS-streamed kernels (logistic_lds.hpp), 8 < d <= 512: the logistic-regression target (LOGIT_TARGET_LOGISTIC: its design matrix
+// is streamed through LDS block by block), and a dense Gaussian with 128 < d (LOGIT_TARGET_DENSE: P no longer fits into LDS, hmc_dense.hpp, so it takes the
+// design matrix's place).  Identity, diagonal or -- without bounds -- dense precond_mat (hmc, mala); bounds (hmc); rwmh plain.  settings->step_size is the
+// leapfrog step resp. par_scale.
+int run_lds(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st, int lds_target)
 {
     int rc;
     const uint64_t d = target->d;
-    if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-    if (d > 512) return fail(MI_ERR_UNSUPPORTED, "%s: logistic target with d = %llu > 512 not implemented", who, (unsigned long long)d);
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
+    if (lds_target == mi::LOGIT_TARGET_LOGISTIC && d > 512) return fail(MI_ERR_UNSUPPORTED, "%s: logistic target with d = %llu > 512 not implemented", who, (unsigned long long)d);
     if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
-    const uint64_t n = target->n_rows;
-    DevBuf Xo, yo;
-    const double *X_dev = target->X, *y_dev = target->y;
-    if (target->mem == MI_MEM_HOST) {
-        HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
-        HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
-        X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-    }
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
     mi::LogitParams q{};
-    q.d = (uint32_t)d; q.n_rows = (uint32_t)n; q.NB = (uint32_t)((n + 15) / 16);
-    q.C = chains->n_chains; q.chain0 = chains->chain0;
-    q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept;
-    q.seed = settings->rng_seed_value;
-    q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
+    fill_common(q, d, settings, chains, sc);
+    q.n_rows = (uint32_t)tg.n_rows; q.NB = (uint32_t)((tg.n_rows + 15) / 16);
     q.n_leap = (uint32_t)settings->n_leap_steps;
     q.eps = settings->step_size;
-    q.draw0 = (uint32_t)chains->draw0;
-    LdsTables lt;
-    LdsDenseM ldm;
-    if (algo == mi::LOGIT_HMC && lds_dense_m_ok(target, settings)) { if ((rc = lds_dense_m(settings, d, ldm, q, algo))) return rc; }      // a dense precond_mat, unbounded
-    else if (algo == mi::LOGIT_HMC) { if ((rc = lds_tables(who, settings, d, lt, q))) return rc; }      // (the caller routed bounds / a DIAGONAL matrix here)
-    rc = launch_logit(algo, q, X_dev, y_dev, st, settings, &sc.dev, mi::LOGIT_TARGET_LOGISTIC, &lt);
-    if (rc) return rc;
-    rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains,
-                     algo == mi::LOGIT_HMC ? (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps : 0, st);
-    if (rc) return rc;
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-    if (rc) return rc;
-    if (Xo.p || lt.ms.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
-}
-
-// hmc / mala / rwmh on a dense Gaussian with 128 < d <= 512 (identity preconditioner / cov_mat, no bounds): P no longer fits into LDS
-// (hmc_dense.hpp), so it is streamed through LDS block by block like the design matrix of the logistic target --
-// logit_lds_kernel<., ., LOGIT_TARGET_DENSE> (logistic_lds.hpp).  settings->step_size is the leapfrog step resp. par_scale.
-int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
-{
-    int rc;
-    const uint64_t d = target->d;
-    if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DENSE needs prec (d*d)");
-    if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
-    DevBuf P_owned;
-    const double* P_dev = nullptr;
-    rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-    if (rc) return rc;
-    StagedChains sc;
-    rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
-    if (rc) return rc;
-    mi::LogitParams q{};
-    q.d = (uint32_t)d; q.n_rows = (uint32_t)d; q.NB = (uint32_t)((d + 15) / 16);
-    q.C = chains->n_chains; q.chain0 = chains->chain0;
-    q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept;
-    q.seed = settings->rng_seed_value;
-    q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
-    q.n_leap = (uint32_t)settings->n_leap_steps;
-    q.eps = settings->step_size;
-    q.draw0 = (uint32_t)chains->draw0;
     if (algo == mi::LOGIT_MALA) {                        // dmvnorm's constants for Sigma = eps^2 I, as the oracle states them
         mi::settings::MalaSigma sg;
         (void)mi::settings::mala_sigma(d, settings->step_size, 0, nullptr, sg);
@@ -949,15 +986,9 @@ int run_dense_lds(const char* who, int algo, const mi_target* target, const mi_s
     if ((algo == mi::LOGIT_HMC || algo == mi::LOGIT_MALA) && lds_dense_m_ok(target, settings)) { if ((rc = lds_dense_m(settings, d, ldm, q, algo))) return rc; }      // a dense precond_mat, unbounded
     else if (algo == mi::LOGIT_HMC) { if ((rc = lds_tables(who, settings, d, lt, q))) return rc; }      // (the caller routed bounds / a DIAGONAL matrix here)
     else if (algo == mi::LOGIT_MALA && settings->precond_mat) { if ((rc = mala_diag_tables(settings, d, mdm, q))) return rc; }
-    rc = launch_logit(algo, q, P_dev, nullptr, st, settings, &sc.dev, mi::LOGIT_TARGET_DENSE, &lt);
+    rc = launch_logit(algo, q, tg, st, settings, &sc.dev, lds_target, &lt);
     if (rc) return rc;
-    rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains,
-                     algo == mi::LOGIT_HMC ? (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps : 0, st);
-    if (rc) return rc;
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-    if (rc) return rc;
-    if (P_owned.p || lt.ms.p || mdm.m.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, algo == mi::LOGIT_HMC ? hmc_leap_total(settings) : 0, tg.owns() || lt.ms.p || mdm.m.p);
 }
 
 // hmc / mala / rwmh on a dense Gaussian or the logistic-regression target BEYOND d = 512 (identity preconditioner / cov_mat; hmc and rwmh also with bounds): the state of a
@@ -1029,30 +1060,16 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     if (algo == 0 && settings->n_leap_steps > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "hmc: too many leapfrog steps");
     const bool bounded = settings->vals_bound != 0;
     if (bounded && (!settings->lower_bounds || !settings->upper_bounds)) return fail(MI_ERR_BAD_ARG, "%s: vals_bound needs lower_bounds and upper_bounds", who);
-    DevBuf P_owned, Xo, yo;
-    const double *P_dev = nullptr, *X_dev = nullptr, *y_dev = nullptr;
-    if (logit) {
-        if (!target->X || !target->y || n == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-        X_dev = target->X; y_dev = target->y;
-        if (target->mem == MI_MEM_HOST) {
-            HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
-            HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
-            X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-        }
-    } else {
-        rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-        if (rc) return rc;
-    }
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
     mi::gemm::GemmRun g;
-    g.algo = algo; g.d = (uint32_t)d; g.C = C; g.chain0 = chains->chain0; g.P = P_dev; g.X = X_dev; g.y = y_dev; g.n_rows = (uint32_t)n;
-    g.theta = sc.dev.theta; g.draws = sc.dev.draws; g.n_accept = sc.dev.n_accept;
-    g.seed = settings->rng_seed_value;
-    g.n_burnin = (uint32_t)settings->n_burnin_draws; g.n_keep = (uint32_t)settings->n_keep_draws; g.n_leap = (uint32_t)settings->n_leap_steps;
-    g.draw0 = (uint32_t)chains->draw0; g.eps = settings->step_size;
+    fill_common(g, d, settings, chains, sc);
+    g.algo = algo; g.n_rows = (uint32_t)n;
+    if (logit) { g.X = tg.mat; g.y = tg.y; } else g.P = tg.mat;
+    g.n_leap = (uint32_t)settings->n_leap_steps; g.eps = settings->step_size;
     // identity or a DIAGONAL precond_mat (hmc.cpp:57-59, mala.cpp:57-58 with mala.ipp:58-64): diag(M), CHOL_LOWER (sqrt), INV (reciprocal) and, mala, INV(eps^2 M) with
     // LOG_DET(eps^2 M) -- all from lit_prepare, in the oracle's operation order; the identity as tables of ones (1.0 * x is x bit for bit)
     mi::lit::LitPrep prep;
@@ -1113,11 +1130,7 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     const int e = mi::gemm::gemm_run(g, st, &kname);
     if (e != 0) return fail(MI_ERR_HIP, "%s: matrix-product sampler: %s", who, hipGetErrorString((hipError_t)e));
     if (replay) {                                        // chains that reached the non-finite regime: replayed literally (literal.hpp)
-        rc = transpose_on_device(logit ? X_dev : P_dev, rp.tbuf, (uint32_t)(logit ? n : d), (uint32_t)d, st);     // (literal.hpp reads the matrix transposed)
-        if (rc) return rc;
-        if (logit) { lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.d = (uint32_t)d; lp.t.n_rows = (uint32_t)n; lp.t.X = X_dev; lp.t.y = y_dev; lp.t.Xt = rp.tbuf; }
-        else { lp.t.kind = mi::lit::LIT_DENSE; lp.t.d = (uint32_t)d; lp.t.prec = rp.tbuf; }
-        mi::lit::lit_orders(lp.t);
+        if ((rc = lit_staged_target(lp.t, tg, (uint32_t)d, rp.tbuf, st))) return rc;
         lit_common(lp, settings, &sc.dev, rp, false);
         lp.rs = g.rs; lp.log_det = g.log_det; lp.cons_term = g.cons_term;
         if (prep.precond == 1) { lp.precond = 1; lp.m = g.mass_tables; lp.m_sqrt = g.mass_tables + dK; lp.m_inv = g.mass_tables + 2 * (size_t)dK; lp.sinv_diag = g.mass_tables + 3 * (size_t)dK; }
@@ -1126,12 +1139,7 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
         if (rc) return rc;
     }
     mi::note_kernel("%s", kname);
-    rc = fill_n_leap(sc.dev.n_leapfrogs, C, algo == 0 ? (settings->n_burnin_draws + settings->n_keep_draws) * settings->n_leap_steps : 0, st);
-    if (rc) return rc;
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));                  // (the mass tables are ours)
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, algo == 0 ? hmc_leap_total(settings) : 0, true);      // (the mass tables are ours)
 }
 
 // The one-lane-per-chain engine (rmhmc_small.hpp, small_samplers.hpp): hmc, mala, rwmh with any precond_mat / cov_mat and any
@@ -1155,13 +1163,9 @@ int run_small(const char* who, int algo, uint64_t d, const mi_settings* settings
     if (rc) return rc;
 
     mi::SmallParams prm{};
-    prm.d = (uint32_t)d;
-    prm.C = chains->n_chains; prm.chain0 = chains->chain0;
-    prm.theta = sc.dev.theta; prm.draws = sc.dev.draws; prm.n_accept = sc.dev.n_accept; prm.n_leap = sc.dev.n_leapfrogs;
-    prm.seed = settings->rng_seed_value;
-    prm.n_burnin = (uint32_t)settings->n_burnin_draws; prm.n_keep = (uint32_t)settings->n_keep_draws;
+    fill_common(prm, d, settings, chains, sc);
+    prm.n_leap = sc.dev.n_leapfrogs;
     prm.n_leap_steps = (uint32_t)settings->n_leap_steps; prm.n_fp_steps = (uint32_t)settings->n_fp_steps;
-    prm.draw0 = (uint32_t)chains->draw0;
     prm.eps = settings->step_size;
     prm.vals_bound = settings->vals_bound ? 1 : 0;
     for (int i = 0; i < mi::SMALL_MAX_D; ++i)
@@ -1171,18 +1175,10 @@ int run_small(const char* who, int algo, uint64_t d, const mi_settings* settings
             for (uint64_t k = 0; k < d; ++k) prm.M[i][k] = settings->precond_mat[i * d + k];
     mi::settings::bounds_tables(d, prm.vals_bound, settings->lower_bounds, settings->upper_bounds, prm.btype, prm.lb, prm.ub);
     mi::settings::pad_table(prm.btype, d, mi::SMALL_MAX_D, 1, prm.btype);      // (prm{}: lb and ub are zeros beyond d already)
-    if (algo == 2) {
-        if ((rc = nuts_continuation(settings, chains, &prm.n_adapt))) return rc;
-        prm.max_depth = (uint32_t)settings->max_tree_depth;
-        prm.delta = settings->target_accept_rate; prm.gamma = settings->gamma_val; prm.t0 = settings->t0_val; prm.kappa = settings->kappa_val;
-        prm.step_out = sc.dev.step_size; prm.depth_trace = sc.dev.nuts_depth; prm.adapt_state = sc.dev.nuts_adapt_state;
-    }
+    if (algo == 2 && (rc = fill_nuts(prm, settings, chains, sc))) return rc;
     rc = launched(who, launch(prm, st));
     if (rc) return rc;
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
-    if (rc) return rc;
-    if (chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, false, n_total);
 }
 
 // the d = 2 normal model of the reference's example programs (MI_TARGET_NORMAL_MODEL)
@@ -1211,24 +1207,18 @@ int run_small_normal_model(const char* who, int algo, const mi_target* target, c
 // logit_lds_kernel): what the LDS kernel does not implement -- nuts, vals_bound, precond_mat / cov_mat
 int run_small_logistic(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
 {
-    const uint64_t d = target->d, n = target->n_rows;
-    if (!target->X || !target->y || n == 0 || n > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
+    const uint64_t d = target->d;
+    StagedTarget tg;
+    int rc = stage_target(target, tg, st, 0xffffffffULL);
+    if (rc) return rc;
     if (d > (uint64_t)mi::SMALL_MAX_D)
         return fail(MI_ERR_UNSUPPORTED, "%s: nuts / vals_bound / precond_mat / cov_mat on the logistic target are implemented for d <= %d "
                                         "(one chain per lane); d = %llu", who, (int)mi::SMALL_MAX_D, (unsigned long long)d);
-    DevBuf Xo, yo;
-    const double *X_dev = target->X, *y_dev = target->y;
-    if (target->mem == MI_MEM_HOST) {
-        HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
-        HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
-        X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-    }
-    const int rc = run_small(who, algo, d, settings, chains, st, [&](const mi::SmallParams& p, hipStream_t s_) {
-        return mi::launch_small_logistic(algo, (int)d, p, X_dev, y_dev, (uint32_t)n, s_);
+    rc = run_small(who, algo, d, settings, chains, st, [&](const mi::SmallParams& p, hipStream_t s_) {
+        return mi::launch_small_logistic(algo, (int)d, p, tg.mat, tg.y, (uint32_t)tg.n_rows, s_);
     });
     if (rc) return rc;
-    if (Xo.p) HIP_TRY(hipStreamSynchronize(st));
+    if (tg.owns()) HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
 
@@ -1741,11 +1731,9 @@ int mi_mcmc_run_tile_target(int algo, uint64_t d, int nt, int wpb, uint64_t lds_
     int rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
     mi::TileParams p{};
-    p.d = (uint32_t)d; p.C = chains->n_chains; p.chain0 = chains->chain0;
-    p.theta = sc.dev.theta; p.draws = sc.dev.draws; p.n_accept = sc.dev.n_accept; p.n_leap = sc.dev.n_leapfrogs;
-    p.seed = settings->rng_seed_value;
-    p.n_burnin = (uint32_t)settings->n_burnin_draws; p.n_keep = (uint32_t)settings->n_keep_draws;
-    p.n_leap_steps = (uint32_t)settings->n_leap_steps; p.draw0 = (uint32_t)chains->draw0;
+    fill_common(p, d, settings, chains, sc);
+    p.n_leap = sc.dev.n_leapfrogs;
+    p.n_leap_steps = (uint32_t)settings->n_leap_steps;
     p.eps = settings->step_size;
     // Sigma = eps^2 M is constant: INV(Sigma) = diag(1 / (eps^2 m_i)) and LOG_DET(Sigma) as the oracle's Gauss-Jordan / Cholesky give them for the identity
     // or a diagonal matrix (settings_host.hpp: mala_sigma; the built-in general mala kernel, mala_dense.hpp, forms the same values)
@@ -1765,11 +1753,8 @@ int mi_mcmc_run_tile_target(int algo, uint64_t d, int nt, int wpb, uint64_t lds_
     }
     WsLease ws;
     if (algo == 2) {                                       // nuts: point records + scalar table of every chain slot (nuts_memo_core.hpp), one workgroup per 64 chains
-        if ((rc = nuts_continuation(settings, chains, &p.n_adapt))) return rc;
-        p.max_depth = (uint32_t)settings->max_tree_depth;
-        p.delta = settings->target_accept_rate; p.eps_bar0 = settings->step_size;
-        p.gamma = settings->gamma_val; p.t0 = settings->t0_val; p.kappa = settings->kappa_val;
-        p.step_out = sc.dev.step_size; p.depth_trace = sc.dev.nuts_depth; p.adapt_state = sc.dev.nuts_adapt_state;
+        if ((rc = fill_nuts(p, settings, chains, sc))) return rc;
+        p.eps_bar0 = settings->step_size;
         const int nt_pad = nt <= 1 ? 1 : nt == 2 ? 2 : nt <= 4 ? 4 : 8;
         // a persistent grid (one workgroup per CU at most) with the chains handed out dynamically: the workspace is sized by the grid's chain slots
         const uint64_t n_wg = mi::nuts_tile_grid(chains->n_chains);
@@ -1791,11 +1776,7 @@ int mi_mcmc_run_tile_target(int algo, uint64_t d, int nt, int wpb, uint64_t lds_
     mi::note_kernel("%s_tile%s_kernel<user target, %d>", algo == 0 ? "hmc" : algo == 1 ? "mala" : "nuts", gt.active ? "_gen" : "", (algo == 0 && !gt.active) ? wpb : 4);     // (mala_tile_gen: mala_tile_kernel<T, true>)
     const int e = launch(algo, &p, target_pod, lds_bytes, stream);
     if (e != 0) return fail(MI_ERR_HIP, "tile target kernel launch: %s", hipGetErrorString((hipError_t)e));
-    if (algo == 1) { rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, 0, st); if (rc) return rc; }
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
-    if (rc) return rc;
-    if (chains->mem == MI_MEM_HOST || gt.active) HIP_TRY(hipStreamSynchronize(st));      // (the tables are ours)
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, algo == 1 ? 0 : NO_LEAP_FILL, gt.active, n_total);      // (the tables are ours)
 }
 
 int mi_mcmc_run_user_target_v(int algo, uint64_t d, mi_small_launch_fn launch, const void* target_pod, uint64_t small_params_bytes,
@@ -1834,149 +1815,85 @@ int mi_mcmc_release_workspace(void* stream, int all_streams, uint64_t* bytes_fre
     return ws_release(static_cast<hipStream_t>(stream), all_streams != 0, bytes_freed);
 }
 
-int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+// ---- the two Gaussian routes of mi_mcmc_hmc_run that are kernels of their own: the elementwise kernels (separable targets, any d) and the d <= 128 tile kernels
+// (static, here and before the other entry points: inside extern "C" a function keeps its C name even in an unnamed namespace, and the library exports the ABI only)
+namespace {
+struct HmcGaussCase { bool dense_m, bounded, diag_precond_elementwise; };      // what the ladder has decided when it reaches them
+// chains that reached the non-finite regime behind a plain launch: replayed literally (literal.hpp) with the same masses.  P_dense / prec_vec: lit_gauss_target
+static int hmc_gauss_replay(const mi_target* target, const mi_settings* settings, const StagedChains& sc, const ReplayWs& rp, const double* P_dense, const double* prec_vec,
+                     const HmcMass& hm, hipStream_t st)
 {
-    int rc = check_common(target, settings, chains, true);
+    mi::lit::LitParams lp{};
+    const int rc = lit_gauss_target(lp.t, target->kind, (uint32_t)target->d, P_dense, prec_vec, rp.tbuf, st);
     if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint64_t d = target->d;
-    if (chains->mass_diag) {
-        // per-chain diagonal masses: separable Gaussians without bounds on the elementwise kernels (below), everything else literally
-        const bool sep = target->kind == MI_TARGET_GAUSS_ISO || target->kind == MI_TARGET_GAUSS_DIAG;
-        // ... a dense precision with d <= 128, no bounds: the MFMA kernel with per-chain tables (round 4; the literal kernel served it before)
-        const bool dense_mfma = target->kind == MI_TARGET_GAUSS_DENSE && d <= 128 && !settings->vals_bound;
-        if ((!sep && !dense_mfma) || settings->vals_bound) {
-            if (target->kind == MI_TARGET_NORMAL_MODEL) return fail(MI_ERR_UNSUPPORTED, "hmc: chains.mass_diag with the normal-model target is not implemented");
-            return run_literal("hmc", 0, target, settings, chains, st);
-        }
-    }
-    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("hmc", 0, target, settings, chains, st);
-    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, true, true, st)) return run_gemm("hmc", 0, target, settings, chains, st);   // d > 512, plain: two matrix products per leapfrog step
-    if (target->kind == MI_TARGET_LOGISTIC) {      // plain: the LDS-staged MFMA kernel (d <= 512); bounds / precond_mat: one chain per lane (d <= 8); else literal.hpp
-        // a DIAGONAL precond_mat alone rides the LDS-staged kernel too (its DIAGM instantiation: two tables read from global memory)
-        // ... and so do bounds (its BOUNDS instantiation, lds_box.hpp), with the identity or a diagonal matrix
-        // ... and, round 5, a DENSE precond_mat without bounds (DENSEM: INV(M) and CHOL_LOWER(M) streamed through LDS like X)
-        const bool lds_general = (settings->vals_bound || settings->precond_mat) && (lds_general_ok(target, settings) || lds_dense_m_ok(target, settings))
-                                 && d > (uint64_t)mi::SMALL_MAX_D && d <= 512;
-        if ((settings->vals_bound || settings->precond_mat) && !lds_general)
-            return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("hmc", 0, target, settings, chains, st) : run_literal("hmc", 0, target, settings, chains, st);
-        return d <= 512 ? run_logit_plain("hmc", mi::LOGIT_HMC, target, settings, chains, st) : run_literal("hmc", 0, target, settings, chains, st);
-    }
-    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
-        return fail(MI_ERR_UNSUPPORTED, "hmc: target kind %d not implemented", target->kind);
-    // precond_mat (hmc.cpp:57-59): INV and CHOL_LOWER of a DIAGONAL matrix are the element-wise 1/m and sqrt(m), exactly what the oracle's
-    // Gauss-Jordan / Cholesky produce; a dense matrix: three fragment sets in LDS (d <= 64), or the two extra ones read from L2 in fragment
-    // order (64 < d <= 128) -- the tables come from settings_host.hpp where a route below needs them
-    const bool dense_m = mi::settings::precond_kind(settings->precond_mat, d) == 2;
-    // sqrt(m) and 1 / m of a diagonal precond_mat alone (no bounds) on the device
-    DevBuf ms_dev, mi_dev;
-    auto upload_diag_mass = [&]() -> int {
-        std::vector<double> m(d), m_sqrt(d), m_inv(d);
-        mi::settings::diag_mass(settings->precond_mat, d, m.data(), m_sqrt.data(), m_inv.data());
-        if (int rcu = upload_padded(ms_dev, m_sqrt.data(), d, d, 1.0)) return rcu;
-        return upload_padded(mi_dev, m_inv.data(), d, d, 1.0);
-    };
-    // beyond d = 128 the tiled kernels serve separable targets without bounds (identity or diagonal precond_mat: hmc_diag.hpp);
-    // everything else there -- dense gradients, bounds, a dense precond_mat -- runs on the literal kernel (literal.hpp)
-    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !(dense_m && settings->vals_bound) && target->kernel_hint != MI_KERNEL_LITERAL)
-        return run_dense_lds("hmc", mi::LOGIT_HMC, target, settings, chains, st);      // P streamed through LDS (logistic_lds.hpp); identity or diagonal precond_mat, with or without bounds; a dense one without
-    if (gemm_case(target, settings, chains, true, true, st)) return run_gemm("hmc", 0, target, settings, chains, st);      // one matrix product per leapfrog step (gemm_samplers.hip)
-    if (d > 128 && (target->kind == MI_TARGET_GAUSS_DENSE || settings->vals_bound || dense_m))
-        return run_literal("hmc", 0, target, settings, chains, st);
-    const bool bounded = settings->vals_bound != 0 || settings->precond_mat != nullptr;   // the general kernel variant
-    if (settings->vals_bound && (!settings->lower_bounds || !settings->upper_bounds))
-        return fail(MI_ERR_BAD_ARG, "hmc: vals_bound needs lower_bounds and upper_bounds");
-    const bool separable_kind = target->kind == MI_TARGET_GAUSS_ISO || target->kind == MI_TARGET_GAUSS_DIAG;
-    // separable target + diagonal precond_mat (no bounds): the elementwise kernel, any d
-    const bool diag_precond_elementwise = separable_kind && !settings->vals_bound && settings->precond_mat && !dense_m && d > 128;
-    if (bounded && d > 128 && !diag_precond_elementwise) return fail(MI_ERR_UNSUPPORTED, "hmc: vals_bound with d > 128 is not implemented");
-    if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
-    const bool separable = target->kind != MI_TARGET_GAUSS_DENSE;
-    // kernel_hint (mi_mcmc.h): an explicit request for the elementwise kernels where the MFMA kernel would be picked; every
-    // kernel produces the same bits, so the hint changes speed only
-    const bool force_diag = !bounded && (target->kernel_hint == MI_KERNEL_ELEMENTWISE_1LANE || target->kernel_hint == MI_KERNEL_ELEMENTWISE_4LANE);
-    if (d > 128 && !separable)
-        return fail(MI_ERR_UNSUPPORTED, "hmc: d = %llu > 128 not implemented for dense-gradient targets", (unsigned long long)d);
-    if (separable && (d > 128 || force_diag || chains->mass_diag)) {
-        if (dense_m) return fail(MI_ERR_UNSUPPORTED, "hmc: a dense precond_mat is implemented for d <= 128");
-        // no contraction: the elementwise (lane-per-chain) kernel
-        DevBuf prec_owned;
-        const double* prec_dev = nullptr;
-        if (target->kind == MI_TARGET_GAUSS_DIAG) {
-            if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DIAG needs prec (d)");
-            if (target->mem == MI_MEM_DEVICE) prec_dev = target->prec;
-            else {
-                HIP_TRY(prec_owned.alloc(d * sizeof(double)));
-                HIP_TRY(hipMemcpy(prec_owned.p, target->prec, d * sizeof(double), hipMemcpyHostToDevice));
-                prec_dev = prec_owned.as<double>();
-            }
-        }
-        StagedChains sc;
-        rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
-        if (rc) return rc;
-        mi::HmcDiagParams q{};
-        q.prec = prec_dev; q.d = (uint32_t)d; q.C = chains->n_chains; q.chain0 = chains->chain0;
-        q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept; q.n_leap = sc.dev.n_leapfrogs;
-        q.seed = settings->rng_seed_value;
-        q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
-        q.n_leap_steps = (uint32_t)settings->n_leap_steps; q.eps = settings->step_size;
-        q.draw0 = (uint32_t)chains->draw0;
-        WsLease scratch;
-        ReplayWs rp = replay_layout(2 * d * chains->n_chains * sizeof(double), chains->n_chains, (uint32_t)d, 0, false, /*needs_matrix=*/false);
-        rc = ws_get(st, rp.total_bytes, scratch);
-        if (rc) return rc;
-        q.scratch = scratch.as<double>();
-        rc = replay_bind(rp, scratch.p, chains->n_chains, st);
-        if (rc) return rc;
-        q.nf_flag = rp.flag;
-        int diag_lanes = mi::hmc_diag_pick_lanes(q.C);          // lanes per chain (hmc_diag.hpp)
-        if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_1LANE) diag_lanes = 1;
-        if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_4LANE) diag_lanes = 4;
-        ChainMass cm;
-        if (sc.dev.mass_diag) {                          // per-chain tables [d][C]
-            if ((rc = chain_mass_tables(sc.dev.mass_diag, d, q.C, cm, st))) return rc;
-            q.m_sqrt = cm.ms.as<double>(); q.m_inv = cm.mi.as<double>(); q.m_per_chain = 1;
-        } else if (diag_precond_elementwise) {
-            if ((rc = upload_diag_mass())) return rc;
-            q.m_sqrt = ms_dev.as<double>(); q.m_inv = mi_dev.as<double>();
-        }
-        const bool precond = q.m_sqrt != nullptr;        // the PRECOND instantiation: mass tables, per chain or shared
-        mi::note_kernel("hmc_diag%d_kernel<%s>", diag_lanes == 4 ? 4 : 1, precond ? "true" : "false");
-        if (diag_lanes == 4) hipLaunchKernelGGL(precond ? mi::hmc_diag4_kernel<true> : mi::hmc_diag4_kernel<false>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
-        else hipLaunchKernelGGL(precond ? mi::hmc_diag1_kernel<true> : mi::hmc_diag1_kernel<false>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
-        HIP_TRY(hipGetLastError());
-        {   // chains that reached the non-finite regime: replayed literally (literal.hpp)
-            mi::lit::LitParams lp{};
-            rc = lit_gauss_target(lp.t, target->kind, (uint32_t)d, nullptr, prec_dev, rp.tbuf, st);
-            if (rc) return rc;
-            lit_common(lp, settings, &sc.dev, rp, false);
-            if (sc.dev.mass_diag) lit_set_chain_mass(lp, sc.dev.mass_diag, cm, q.C);
-            else if (diag_precond_elementwise) { lp.precond = 1; lp.m_sqrt = ms_dev.as<double>(); lp.m_inv = mi_dev.as<double>(); }
-            rc = launched("hmc (literal replay)", mi::launch_literal(0, lp, rp.n_wg, st));
-            if (rc) return rc;
-        }
-        if (diag_precond_elementwise || sc.dev.mass_diag) HIP_TRY(hipStreamSynchronize(st));          // the tables are ours
-        rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-        if (rc) return rc;
-        if (prec_owned.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-        return MI_OK;
-    }
+    lit_common(lp, settings, &sc.dev, rp, false);
+    if (hm.per_chain) lit_set_chain_mass(lp, sc.dev.mass_diag, hm.t, sc.dev.n_chains);
+    else if (hm.shared) { lp.precond = 1; lp.m_sqrt = hm.t.ms.as<double>(); lp.m_inv = hm.t.mi.as<double>(); }
+    return launched("hmc (literal replay)", mi::launch_literal(0, lp, rp.n_wg, st));
+}
 
-    DevBuf P_owned;
-    const double* P_dev = nullptr;
-    rc = dense_precision_on_device(target, P_owned, &P_dev, st);
+// separable targets (ISO / DIAG), any d, no bounds: no contraction, the elementwise (lane-per-chain) kernels of hmc_diag.hpp
+static int run_hmc_elementwise(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st, const HmcGaussCase& hc)
+{
+    int rc;
+    const uint64_t d = target->d;
+    if (hc.dense_m) return fail(MI_ERR_UNSUPPORTED, "hmc: a dense precond_mat is implemented for d <= 128");
+    DevBuf prec_owned;
+    const double* prec_dev = nullptr;
+    if (target->kind == MI_TARGET_GAUSS_DIAG) {
+        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DIAG needs prec (d)");
+        if (target->mem == MI_MEM_DEVICE) prec_dev = target->prec;
+        else {
+            HIP_TRY(prec_owned.alloc(d * sizeof(double)));
+            HIP_TRY(hipMemcpy(prec_owned.p, target->prec, d * sizeof(double), hipMemcpyHostToDevice));
+            prec_dev = prec_owned.as<double>();
+        }
+    }
+    StagedChains sc;
+    rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
+    mi::HmcDiagParams q{};
+    fill_common(q, d, settings, chains, sc);
+    q.prec = prec_dev; q.n_leap = sc.dev.n_leapfrogs;
+    q.n_leap_steps = (uint32_t)settings->n_leap_steps; q.eps = settings->step_size;
+    WsLease scratch;
+    ReplayWs rp = replay_layout(2 * d * chains->n_chains * sizeof(double), chains->n_chains, (uint32_t)d, 0, false, /*needs_matrix=*/false);
+    rc = ws_get(st, rp.total_bytes, scratch);
+    if (rc) return rc;
+    q.scratch = scratch.as<double>();
+    rc = replay_bind(rp, scratch.p, chains->n_chains, st);
+    if (rc) return rc;
+    q.nf_flag = rp.flag;
+    int diag_lanes = mi::hmc_diag_pick_lanes(q.C);          // lanes per chain (hmc_diag.hpp)
+    if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_1LANE) diag_lanes = 1;
+    if (target->kernel_hint == MI_KERNEL_ELEMENTWISE_4LANE) diag_lanes = 4;
+    HmcMass hm;
+    if ((rc = hmc_mass(hm, q, settings, sc, hc.diag_precond_elementwise, st))) return rc;
+    const bool precond = q.m_sqrt != nullptr;        // the PRECOND instantiation: mass tables, per chain or shared
+    mi::note_kernel("hmc_diag%d_kernel<%s>", diag_lanes == 4 ? 4 : 1, precond ? "true" : "false");
+    if (diag_lanes == 4) hipLaunchKernelGGL(precond ? mi::hmc_diag4_kernel<true> : mi::hmc_diag4_kernel<false>, dim3((unsigned)((q.C + 63) / 64)), dim3(256), 0, st, q);
+    else hipLaunchKernelGGL(precond ? mi::hmc_diag1_kernel<true> : mi::hmc_diag1_kernel<false>, dim3((unsigned)((q.C + 255) / 256)), dim3(256), 0, st, q);
+    HIP_TRY(hipGetLastError());
+    if ((rc = hmc_gauss_replay(target, settings, sc, rp, nullptr, prec_dev, hm, st))) return rc;
+    if (hc.diag_precond_elementwise || sc.dev.mass_diag) HIP_TRY(hipStreamSynchronize(st));          // the tables are ours
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, prec_owned.p != nullptr);
+}
+
+// d <= 128, every Gaussian kind: the MFMA tile kernels (hmc_dense.hpp) -- plain, with diagonal masses in the plain kernel's shape, or the general variants
+static int run_hmc_tile(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st, const HmcGaussCase& hc)
+{
+    int rc;
+    const uint64_t d = target->d;
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
 
     mi::HmcParams prm{};
-    prm.P = P_dev;
-    prm.d = (uint32_t)d;
+    fill_common(prm, d, settings, chains, sc);
+    prm.P = tg.mat;
     prm.sep_target = target->kind != MI_TARGET_GAUSS_DENSE;     // ISO / DIAG: the general variants take the gradient element-wise, as the reference's target function does (hmc_dense.hpp: target_times)
-    prm.C = chains->n_chains;
-    prm.chain0 = chains->chain0;
-    prm.theta = sc.dev.theta;
     // stream-ordered workspace: P * theta of the last accepted state, [d][C]
     WsLease wsave;
     const size_t d_pad_h = (d <= 16) ? 16 : (d <= 32) ? 32 : (d <= 64) ? 64 : 128;
@@ -1987,22 +1904,16 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
     // a diagonal precond_mat alone (no bounds): the plain kernel's shape with two mass tables (hmc_dense.hpp, DIAGM), replay as the plain kernel;
     // per-chain diagonal masses (mi_chains.mass_diag) ride the same variant with [d][C] tables in global memory (PCM)
     const bool chain_mass = sc.dev.mass_diag != nullptr;
-    const bool diag_only = (settings->precond_mat != nullptr && !dense_m && !settings->vals_bound) || chain_mass;
-    const bool general = bounded && !diag_only;
+    const bool diag_only = (settings->precond_mat != nullptr && !hc.dense_m && !settings->vals_bound) || chain_mass;
+    const bool general = hc.bounded && !diag_only;
     if (!general) {                                     // the general variants reproduce the dense products themselves
         rc = replay_bind(rp, wsave.p, chains->n_chains, st);
         if (rc) return rc;
         prm.nf_flag = rp.flag;
     }
-    prm.draws = sc.dev.draws;
-    prm.n_accept = sc.dev.n_accept;
     prm.n_leap = sc.dev.n_leapfrogs;
-    prm.seed = settings->rng_seed_value;
-    prm.n_burnin = (uint32_t)settings->n_burnin_draws;
-    prm.n_keep = (uint32_t)settings->n_keep_draws;
     prm.n_leap_steps = (uint32_t)settings->n_leap_steps;
     prm.eps = settings->step_size;
-    prm.draw0 = (uint32_t)chains->draw0;
     prm.stagger = 40;
 #ifdef MI_PROFILING     // A/B library only (make prof): the shipped library reads no environment variable
     if (const char* e = getenv("MI_HMC_STAGGER")) prm.stagger = (uint32_t)atoi(e);
@@ -2017,8 +1928,8 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
         prm.btype = gt.bt.as<int>(); prm.lb = gt.lb.as<double>(); prm.ub = gt.ub.as<double>();
         prm.m_sqrt = gt.ms_dev.as<double>(); prm.m_inv = gt.mi_dev.as<double>();
         prm.vals_bound = settings->vals_bound ? 1 : 0;
-        if (dense_m) { prm.Minv = gt.minv_full.as<double>(); prm.Lchol = gt.l_full.as<double>(); }
-        rc = launched("hmc", mi::launch_hmc_gauss(prm, nt, true, dense_m, st));
+        if (hc.dense_m) { prm.Minv = gt.minv_full.as<double>(); prm.Lchol = gt.l_full.as<double>(); }
+        rc = launched("hmc", mi::launch_hmc_gauss(prm, nt, true, hc.dense_m, st));
         if (!rc) HIP_TRY(hipStreamSynchronize(st));     // the tables are ours
     }
     else {
@@ -2045,35 +1956,78 @@ int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_cha
             default: break;
             }
         }
-        ChainMass cm;
-        if (chain_mass) {
-            if ((rc = chain_mass_tables(sc.dev.mass_diag, d, chains->n_chains, cm, st))) return rc;
-            prm.m_sqrt = cm.ms.as<double>(); prm.m_inv = cm.mi.as<double>(); prm.m_per_chain = 1;
-            rc = launched("hmc", mi::launch_hmc_gauss_diagm(prm, nt, st));
-        } else if (diag_only) {
-            if ((rc = upload_diag_mass())) return rc;
-            prm.m_sqrt = ms_dev.as<double>(); prm.m_inv = mi_dev.as<double>();
-            rc = launched("hmc", mi::launch_hmc_gauss_diagm(prm, nt, st));
-        } else
-        rc = shape == 0 ? launched("hmc", mi::launch_hmc_gauss(prm, nt, false, false, st))
+        HmcMass hm;
+        if ((rc = hmc_mass(hm, prm, settings, sc, diag_only, st))) return rc;
+        rc = diag_only  ? launched("hmc", mi::launch_hmc_gauss_diagm(prm, nt, st))
+           : shape == 0 ? launched("hmc", mi::launch_hmc_gauss(prm, nt, false, false, st))
                         : launched("hmc", mi::launch_hmc_gauss_few_chains(prm, shape, st));
         if (rc) return rc;
-        mi::lit::LitParams lp{};                        // chains that reached the non-finite regime: replayed literally (literal.hpp)
-        rc = lit_gauss_target(lp.t, target->kind, (uint32_t)d, P_dev, nullptr, rp.tbuf, st);
-        if (rc) return rc;
-        lit_common(lp, settings, &sc.dev, rp, false);
-        if (chain_mass) lit_set_chain_mass(lp, sc.dev.mass_diag, cm, chains->n_chains);
-        else if (diag_only) { lp.precond = 1; lp.m_sqrt = ms_dev.as<double>(); lp.m_inv = mi_dev.as<double>(); }
-        rc = launched("hmc (literal replay)", mi::launch_literal(0, lp, rp.n_wg, st));
+        rc = hmc_gauss_replay(target, settings, sc, rp, tg.mat, nullptr, hm, st);
         if (!rc && diag_only) HIP_TRY(hipStreamSynchronize(st));     // the tables are ours
     }
     if (rc) return rc;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, tg.owns());      // (a staged target / host-mode chains must outlive the kernel)
+}
+}  // namespace
 
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
+int mi_mcmc_hmc_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+{
+    int rc = check_common(target, settings, chains, true);
     if (rc) return rc;
-    // buffers we own (staged target / host-mode chains) must outlive the kernel
-    if (P_owned.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d;
+    if (chains->mass_diag) {
+        // per-chain diagonal masses: separable Gaussians without bounds on the elementwise kernels (below), everything else literally
+        const bool sep = target->kind == MI_TARGET_GAUSS_ISO || target->kind == MI_TARGET_GAUSS_DIAG;
+        // ... a dense precision with d <= 128, no bounds: the MFMA kernel with per-chain tables (round 4; the literal kernel served it before)
+        const bool dense_mfma = target->kind == MI_TARGET_GAUSS_DENSE && d <= 128 && !settings->vals_bound;
+        if ((!sep && !dense_mfma) || settings->vals_bound) {
+            if (target->kind == MI_TARGET_NORMAL_MODEL) return fail(MI_ERR_UNSUPPORTED, "hmc: chains.mass_diag with the normal-model target is not implemented");
+            return run_literal("hmc", 0, target, settings, chains, st);
+        }
+    }
+    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("hmc", 0, target, settings, chains, st);
+    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, true, true, st)) return run_gemm("hmc", 0, target, settings, chains, st);   // d > 512, plain: two matrix products per leapfrog step
+    if (target->kind == MI_TARGET_LOGISTIC) {      // plain: the LDS-staged MFMA kernel (d <= 512); bounds / precond_mat: one chain per lane (d <= 8); else literal.hpp
+        // a DIAGONAL precond_mat alone rides the LDS-staged kernel too (its DIAGM instantiation: two tables read from global memory)
+        // ... and so do bounds (its BOUNDS instantiation, lds_box.hpp), with the identity or a diagonal matrix
+        // ... and, round 5, a DENSE precond_mat without bounds (DENSEM: INV(M) and CHOL_LOWER(M) streamed through LDS like X)
+        const bool lds_general = (settings->vals_bound || settings->precond_mat) && (lds_general_ok(target, settings) || lds_dense_m_ok(target, settings))
+                                 && d > (uint64_t)mi::SMALL_MAX_D && d <= 512;
+        if ((settings->vals_bound || settings->precond_mat) && !lds_general)
+            return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("hmc", 0, target, settings, chains, st) : run_literal("hmc", 0, target, settings, chains, st);
+        return d <= 512 ? run_lds("hmc", mi::LOGIT_HMC, target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC) : run_literal("hmc", 0, target, settings, chains, st);
+    }
+    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
+        return fail(MI_ERR_UNSUPPORTED, "hmc: target kind %d not implemented", target->kind);
+    // precond_mat (hmc.cpp:57-59): INV and CHOL_LOWER of a DIAGONAL matrix are the element-wise 1/m and sqrt(m), exactly what the oracle's
+    // Gauss-Jordan / Cholesky produce; a dense matrix: three fragment sets in LDS (d <= 64), or the two extra ones read from L2 in fragment
+    // order (64 < d <= 128) -- the tables come from settings_host.hpp where a route below needs them
+    const bool dense_m = mi::settings::precond_kind(settings->precond_mat, d) == 2;
+    // beyond d = 128 the tiled kernels serve separable targets without bounds (identity or diagonal precond_mat: hmc_diag.hpp);
+    // everything else there -- dense gradients, bounds, a dense precond_mat -- runs on the literal kernel (literal.hpp)
+    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !(dense_m && settings->vals_bound) && target->kernel_hint != MI_KERNEL_LITERAL)
+        return run_lds("hmc", mi::LOGIT_HMC, target, settings, chains, st, mi::LOGIT_TARGET_DENSE);      // P streamed through LDS (logistic_lds.hpp); identity or diagonal precond_mat, with or without bounds; a dense one without
+    if (gemm_case(target, settings, chains, true, true, st)) return run_gemm("hmc", 0, target, settings, chains, st);      // one matrix product per leapfrog step (gemm_samplers.hip)
+    if (d > 128 && (target->kind == MI_TARGET_GAUSS_DENSE || settings->vals_bound || dense_m))
+        return run_literal("hmc", 0, target, settings, chains, st);
+    const bool bounded = settings->vals_bound != 0 || settings->precond_mat != nullptr;   // the general kernel variant
+    if (settings->vals_bound && (!settings->lower_bounds || !settings->upper_bounds))
+        return fail(MI_ERR_BAD_ARG, "hmc: vals_bound needs lower_bounds and upper_bounds");
+    const bool separable_kind = target->kind == MI_TARGET_GAUSS_ISO || target->kind == MI_TARGET_GAUSS_DIAG;
+    // separable target + diagonal precond_mat (no bounds): the elementwise kernel, any d
+    const bool diag_precond_elementwise = separable_kind && !settings->vals_bound && settings->precond_mat && !dense_m && d > 128;
+    if (bounded && d > 128 && !diag_precond_elementwise) return fail(MI_ERR_UNSUPPORTED, "hmc: vals_bound with d > 128 is not implemented");
+    if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    const bool separable = target->kind != MI_TARGET_GAUSS_DENSE;
+    // kernel_hint (mi_mcmc.h): an explicit request for the elementwise kernels where the MFMA kernel would be picked; every
+    // kernel produces the same bits, so the hint changes speed only
+    const bool force_diag = !bounded && (target->kernel_hint == MI_KERNEL_ELEMENTWISE_1LANE || target->kernel_hint == MI_KERNEL_ELEMENTWISE_4LANE);
+    if (d > 128 && !separable)
+        return fail(MI_ERR_UNSUPPORTED, "hmc: d = %llu > 128 not implemented for dense-gradient targets", (unsigned long long)d);
+    const HmcGaussCase hc{dense_m, bounded, diag_precond_elementwise};
+    if (separable && (d > 128 || force_diag || chains->mass_diag)) return run_hmc_elementwise(target, settings, chains, st, hc);
+    return run_hmc_tile(target, settings, chains, st, hc);
 }
 
 // per-dimension variance of the chains' current states, pooled over the chains: out[d] (host); theta [d][C] in `mem`
@@ -2344,92 +2298,28 @@ int mi_mcmc_rmhmc_run_callback(const double* initial_vals, uint64_t d, mi_log_ke
                                           n_accept_draws, nullptr);
 }
 
-int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+namespace {
+// mala on the Gaussian kinds with d <= 128: the MFMA tile kernels (mala_dense.hpp) -- plain, general (bounds and / or a diagonal precond_mat), a dense precond_mat
+// without bounds; with both the literal kernel runs the call entirely
+static int run_mala_tile(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
 {
-    int rc = check_common(target, settings, chains);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
     const uint64_t d = target->d;
-    if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
-    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("mala", 1, target, settings, chains, st);
-    // a DIAGONAL precond_mat alone rides the LDS-staged kernel too (its DIAGM instantiation)
-    // ... and, round 5, a DENSE one without bounds (DENSEM: M, CHOL_LOWER(M) and INV(eps^2 M) streamed through LDS like X)
-    const bool mala_diag_alone = !settings->vals_bound && (precond_is_diagonal(settings, d) || lds_dense_m_ok(target, settings)) && d > (uint64_t)mi::SMALL_MAX_D && d <= 512;
-    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, true, st)) return run_gemm("mala", 1, target, settings, chains, st);    // d > 512, identity or a diagonal precond_mat, no bounds
-    if (target->kind == MI_TARGET_LOGISTIC && (settings->vals_bound || settings->precond_mat) && !mala_diag_alone)
-        return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("mala", 1, target, settings, chains, st) : run_literal("mala", 1, target, settings, chains, st);
-    if (target->kind == MI_TARGET_LOGISTIC && d > 512) return run_literal("mala", 1, target, settings, chains, st);
-    // Sigma = eps^2 * I (mala.ipp:41,63): INV by Gauss-Jordan gives diag(1/s2); CHOL gives diag(sqrt(s2));
-    // LOG_DET = sum_i 2 log L_ii accumulated sequentially, exactly as the oracle states it (settings_host.hpp: mala_sigma).
-    const double s2_ = settings->step_size * settings->step_size;
-    mi::settings::MalaSigma sg;
-    (void)mi::settings::mala_sigma(d, settings->step_size, 0, nullptr, sg);
-    if (target->kind == MI_TARGET_LOGISTIC) {
-        if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-        if (d > 512) return fail(MI_ERR_UNSUPPORTED, "mala: logistic target with d = %llu > 512 not implemented", (unsigned long long)d);
-        const uint64_t n = target->n_rows;
-        DevBuf Xo, yo;
-        const double *X_dev = target->X, *y_dev = target->y;
-        if (target->mem == MI_MEM_HOST) {
-            HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
-            HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
-            X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-        }
-        StagedChains sc;
-        rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
-        if (rc) return rc;
-        mi::LogitParams q{};
-        q.d = (uint32_t)d; q.n_rows = (uint32_t)n; q.NB = (uint32_t)((n + 15) / 16);
-        q.C = chains->n_chains; q.chain0 = chains->chain0;
-        q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept;
-        q.seed = settings->rng_seed_value;
-        q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
-        q.eps = settings->step_size; q.s2 = s2_; q.rs = sg.rs; q.cons_term = sg.cons_term; q.log_det = sg.log_det;
-        q.draw0 = (uint32_t)chains->draw0;
-        MalaDiagMass mdm;
-        LdsDenseM ldm;
-        if (lds_dense_m_ok(target, settings)) { if ((rc = lds_dense_m(settings, d, ldm, q, mi::LOGIT_MALA))) return rc; }     // dense, no bounds
-        else if (settings->precond_mat) { if ((rc = mala_diag_tables(settings, d, mdm, q))) return rc; }     // (diagonal, no bounds: routed above)
-        rc = launch_logit(mi::LOGIT_MALA, q, X_dev, y_dev, st, settings, &sc.dev);
-        if (rc) return rc;
-        rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, 0, st);
-        if (rc) return rc;
-        rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-        if (rc) return rc;
-        if (Xo.p || mdm.m.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-        return MI_OK;
-    }
-    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
-        return fail(MI_ERR_UNSUPPORTED, "mala: target kind %d not implemented", target->kind);
-    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !settings->vals_bound
-        && (!settings->precond_mat || precond_is_diagonal(settings, d) || lds_dense_m_ok(target, settings)))
-        return run_dense_lds("mala", mi::LOGIT_MALA, target, settings, chains, st);     // P streamed through LDS (logistic_lds.hpp); identity, diagonal or (round 5) dense precond_mat
-    if (gemm_case(target, settings, chains, false, true, st)) return run_gemm("mala", 1, target, settings, chains, st);    // one matrix product per draw (gemm_samplers.hip)
-    if (d > 128) return run_literal("mala", 1, target, settings, chains, st);      // no other tiled kernel beyond d = 128: literal.hpp
-
-    DevBuf P_owned;
-    const double* P_dev = nullptr;
-    rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-    if (rc) return rc;
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
 
     mi::MalaParams prm{};
-    prm.P = P_dev;
-    prm.d = (uint32_t)d;
-    prm.C = chains->n_chains;
-    prm.chain0 = chains->chain0;
-    prm.theta = sc.dev.theta;
-    prm.draws = sc.dev.draws;
-    prm.n_accept = sc.dev.n_accept;
-    prm.seed = settings->rng_seed_value;
-    prm.n_burnin = (uint32_t)settings->n_burnin_draws;
-    prm.n_keep = (uint32_t)settings->n_keep_draws;
+    fill_common(prm, d, settings, chains, sc);
+    prm.P = tg.mat;
     prm.eps = settings->step_size;
-    prm.draw0 = (uint32_t)chains->draw0;
-    prm.s2 = s2_; prm.rs = sg.rs; prm.cons_term = sg.cons_term; prm.log_det = sg.log_det;      // Sigma = eps^2 I, from above
+    // Sigma = eps^2 * I (mala.ipp:41,63): INV by Gauss-Jordan gives diag(1/s2); CHOL gives diag(sqrt(s2));
+    // LOG_DET = sum_i 2 log L_ii accumulated sequentially, exactly as the oracle states it (settings_host.hpp: mala_sigma).
+    mi::settings::MalaSigma sg;
+    (void)mi::settings::mala_sigma(d, settings->step_size, 0, nullptr, sg);
+    prm.s2 = settings->step_size * settings->step_size; prm.rs = sg.rs; prm.cons_term = sg.cons_term; prm.log_det = sg.log_det;
 
     const int nt = (int)((d + 15) / 16);
     GeneralTables gt;
@@ -2449,7 +2339,7 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
         if (rc) return rc;
         rc = replay_bind(rp, lws.p, chains->n_chains, st);
         if (rc) return rc;
-        rc = lit_gauss_target(lp.t, target->kind, (uint32_t)d, P_dev, nullptr, rp.tbuf, st);
+        rc = lit_gauss_target(lp.t, target->kind, (uint32_t)d, tg.mat, nullptr, rp.tbuf, st);
         if (rc) return rc;
         lit_common(lp, settings, &sc.dev, rp, literal_only);
         mi::lit::LitPrep prep;
@@ -2492,51 +2382,51 @@ int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_ch
     }
     if (rc) return rc;
     if (gt.active || ldev.any) HIP_TRY(hipStreamSynchronize(st));     // the tables are ours
-    rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, 0, st);
-    if (rc) return rc;
-
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
-    if (rc) return rc;
-    if (P_owned.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, 0, tg.owns());
 }
+}  // namespace
 
-// mcmc::rwmh (src/rwmh.cpp:30-175) for many chains.  settings->step_size carries rwmh_settings.par_scale and
-// settings->precond_mat carries rwmh_settings.cov_mat (identity when NULL, rwmh.cpp:58).
-int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
 {
     int rc = check_common(target, settings, chains);
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint64_t d = target->d;
-    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("rwmh", 3, target, settings, chains, st);
-    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);    // d > 512, plain or with bounds
-    if (target->kind == MI_TARGET_LOGISTIC) {
-        if (settings->vals_bound || settings->precond_mat)
-            return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("rwmh", 3, target, settings, chains, st) : run_literal("rwmh", 3, target, settings, chains, st);
-        return d <= 512 ? run_logit_plain("rwmh", mi::LOGIT_RWMH, target, settings, chains, st) : run_literal("rwmh", 3, target, settings, chains, st);
-    }
+    if (settings->n_burnin_draws + settings->n_keep_draws > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("mala", 1, target, settings, chains, st);
+    // a DIAGONAL precond_mat alone rides the LDS-staged kernel too (its DIAGM instantiation)
+    // ... and, round 5, a DENSE one without bounds (DENSEM: M, CHOL_LOWER(M) and INV(eps^2 M) streamed through LDS like X)
+    const bool mala_diag_alone = !settings->vals_bound && (precond_is_diagonal(settings, d) || lds_dense_m_ok(target, settings)) && d > (uint64_t)mi::SMALL_MAX_D && d <= 512;
+    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, true, st)) return run_gemm("mala", 1, target, settings, chains, st);    // d > 512, identity or a diagonal precond_mat, no bounds
+    if (target->kind == MI_TARGET_LOGISTIC && (settings->vals_bound || settings->precond_mat) && !mala_diag_alone)
+        return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("mala", 1, target, settings, chains, st) : run_literal("mala", 1, target, settings, chains, st);
+    if (target->kind == MI_TARGET_LOGISTIC && d > 512) return run_literal("mala", 1, target, settings, chains, st);
+    if (target->kind == MI_TARGET_LOGISTIC) return run_lds("mala", mi::LOGIT_MALA, target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC);
     if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
-        return fail(MI_ERR_UNSUPPORTED, "rwmh: target kind %d not implemented", target->kind);
-    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !settings->vals_bound && !settings->precond_mat)
-        return run_dense_lds("rwmh", mi::LOGIT_RWMH, target, settings, chains, st);     // P streamed through LDS (logistic_lds.hpp)
-    if (gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);
-    if (d > 128) return run_literal("rwmh", 3, target, settings, chains, st);      // no other tiled kernel beyond d = 128: literal.hpp
+        return fail(MI_ERR_UNSUPPORTED, "mala: target kind %d not implemented", target->kind);
+    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !settings->vals_bound
+        && (!settings->precond_mat || precond_is_diagonal(settings, d) || lds_dense_m_ok(target, settings)))
+        return run_lds("mala", mi::LOGIT_MALA, target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (logistic_lds.hpp); identity, diagonal or (round 5) dense precond_mat
+    if (gemm_case(target, settings, chains, false, true, st)) return run_gemm("mala", 1, target, settings, chains, st);    // one matrix product per draw (gemm_samplers.hip)
+    if (d > 128) return run_literal("mala", 1, target, settings, chains, st);      // no other tiled kernel beyond d = 128: literal.hpp
+    return run_mala_tile(target, settings, chains, st);
+}
 
-    DevBuf P_owned;
-    const double* P_dev = nullptr;
-    rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-    if (rc) return rc;
+namespace {
+// rwmh on the Gaussian kinds with d <= 128: the MFMA tile kernels (rwmh_dense.hpp), plain or general (bounds and / or a cov_mat)
+static int run_rwmh_tile(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
+{
+    int rc;
+    const uint64_t d = target->d;
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st);
     if (rc) return rc;
 
     mi::RwmhParams prm{};
-    prm.P = P_dev; prm.d = (uint32_t)d; prm.C = chains->n_chains; prm.chain0 = chains->chain0;
-    prm.theta = sc.dev.theta; prm.draws = sc.dev.draws; prm.n_accept = sc.dev.n_accept;
-    prm.seed = settings->rng_seed_value;
-    prm.n_burnin = (uint32_t)settings->n_burnin_draws; prm.n_keep = (uint32_t)settings->n_keep_draws;
-    prm.draw0 = (uint32_t)chains->draw0;
+    fill_common(prm, d, settings, chains, sc);
+    prm.P = tg.mat;
     prm.par_scale = settings->step_size;
 
     const int nt = (int)((d + 15) / 16);
@@ -2564,13 +2454,32 @@ int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_ch
     }
     else rc = launched("rwmh", mi::launch_rwmh_gauss(prm, nt, false, false, st));
     if (rc) return rc;
-    rc = fill_n_leap(sc.dev.n_leapfrogs, chains->n_chains, 0, st);
-    if (rc) return rc;
+    return finish(chains, d, settings, sc, st, 0, tg.owns());
+}
+}  // namespace
 
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st);
+// mcmc::rwmh (src/rwmh.cpp:30-175) for many chains.  settings->step_size carries rwmh_settings.par_scale and
+// settings->precond_mat carries rwmh_settings.cov_mat (identity when NULL, rwmh.cpp:58).
+int mi_mcmc_rwmh_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+{
+    int rc = check_common(target, settings, chains);
     if (rc) return rc;
-    if (P_owned.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d;
+    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("rwmh", 3, target, settings, chains, st);
+    if (target->kind == MI_TARGET_LOGISTIC && gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);    // d > 512, plain or with bounds
+    if (target->kind == MI_TARGET_LOGISTIC) {
+        if (settings->vals_bound || settings->precond_mat)
+            return d <= (uint64_t)mi::SMALL_MAX_D ? run_small_logistic("rwmh", 3, target, settings, chains, st) : run_literal("rwmh", 3, target, settings, chains, st);
+        return d <= 512 ? run_lds("rwmh", mi::LOGIT_RWMH, target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC) : run_literal("rwmh", 3, target, settings, chains, st);
+    }
+    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
+        return fail(MI_ERR_UNSUPPORTED, "rwmh: target kind %d not implemented", target->kind);
+    if (d > 128 && d <= 512 && target->kind == MI_TARGET_GAUSS_DENSE && !settings->vals_bound && !settings->precond_mat)
+        return run_lds("rwmh", mi::LOGIT_RWMH, target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (logistic_lds.hpp)
+    if (gemm_case(target, settings, chains, false, false, st)) return run_gemm("rwmh", 3, target, settings, chains, st);
+    if (d > 128) return run_literal("rwmh", 3, target, settings, chains, st);      // no other tiled kernel beyond d = 128: literal.hpp
+    return run_rwmh_tile(target, settings, chains, st);
 }
 
 // nuts on the LDS-streamed evaluation (nuts_lds.hpp): the logistic target with 8 < d <= 512 and dense Gaussians with 128 < d <= 512,
@@ -2583,41 +2492,19 @@ int run_lds_nuts(const mi_target* target, const mi_settings* settings, mi_chains
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
     if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
     const bool dense = lds_target == mi::LOGIT_TARGET_DENSE;
-    DevBuf Xo, yo, P_owned;
-    const double *X_dev = nullptr, *y_dev = nullptr;
-    uint64_t n_rows = d;
-    if (dense) {
-        if (!target->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DENSE needs prec (d*d)");
-        rc = dense_precision_on_device(target, P_owned, &X_dev, st);
-        if (rc) return rc;
-    } else {
-        if (!target->X || !target->y || target->n_rows == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-        n_rows = target->n_rows;
-        X_dev = target->X; y_dev = target->y;
-        if (target->mem == MI_MEM_HOST) {
-            HIP_TRY(Xo.alloc(n_rows * d * sizeof(double))); HIP_TRY(yo.alloc(n_rows * sizeof(double)));
-            HIP_TRY(hipMemcpy(Xo.p, target->X, n_rows * d * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(yo.p, target->y, n_rows * sizeof(double), hipMemcpyHostToDevice));
-            X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-        }
-    }
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
+    const uint64_t n_rows = tg.n_rows;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
     mi::LogitParams q{};
-    q.d = (uint32_t)d; q.n_rows = (uint32_t)n_rows; q.NB = (uint32_t)((n_rows + 15) / 16);
-    q.C = C; q.chain0 = chains->chain0;
-    q.theta = sc.dev.theta; q.draws = sc.dev.draws; q.n_accept = sc.dev.n_accept;
-    q.seed = settings->rng_seed_value;
-    q.n_burnin = (uint32_t)settings->n_burnin_draws; q.n_keep = (uint32_t)settings->n_keep_draws;
-    q.draw0 = (uint32_t)chains->draw0;
-    q.n_leap_out = sc.dev.n_leapfrogs; q.step_out = sc.dev.step_size; q.depth_trace = sc.dev.nuts_depth;
+    fill_common(q, d, settings, chains, sc);
+    q.n_rows = (uint32_t)n_rows; q.NB = (uint32_t)((n_rows + 15) / 16);
+    q.n_leap_out = sc.dev.n_leapfrogs;
     q.n_exec_out = sc.dev.n_leapfrogs_executed; sc.exec_written = q.n_exec_out != nullptr;      // (every doubling on a memoised trajectory: nuts_lds.hpp)
-    if ((rc = nuts_continuation(settings, chains, &q.n_adapt))) return rc;
-    q.adapt_state = sc.dev.nuts_adapt_state;
-    q.max_depth = (uint32_t)settings->max_tree_depth;
-    q.delta = settings->target_accept_rate; q.eps_bar0 = settings->step_size;
-    q.gamma = settings->gamma_val; q.t0 = settings->t0_val; q.kappa = settings->kappa_val;
+    if ((rc = fill_nuts(q, settings, chains, sc))) return rc;
+    q.eps_bar0 = settings->step_size;
     // a DENSE precond_mat without bounds (round 6): INV(M) and CHOL_LOWER(M) streamed through LDS like the target's matrix (nuts_lds.hpp: DENSEM)
     const bool dense_m = lds_dense_m_ok(target, settings);
     LdsTables lt;
@@ -2647,24 +2534,15 @@ int run_lds_nuts(const mi_target* target, const mi_settings* settings, mi_chains
     if (split_bytes) q.split_ws = static_cast<char*>(base.p) + rp_bytes;
     DevBuf mws;                                          // dense_m: the block images of the two matrices (+ the exchange vectors of their products)
     if (dense_m) HIP_TRY(mws.alloc(mi::logit_lds_nuts_dense_m_bytes(q.d, C, lds_target)));
-    const int e = dense_m ? mi::logit_lds_launch_nuts_dense_m(q, X_dev, y_dev, base.p, mws.p, st, lds_target)
-                          : mi::logit_lds_launch(mi::LOGIT_NUTS, q, X_dev, y_dev, base.p, st, lds_target);
+    const int e = dense_m ? mi::logit_lds_launch_nuts_dense_m(q, tg.mat, tg.y, base.p, mws.p, st, lds_target)
+                          : mi::logit_lds_launch(mi::LOGIT_NUTS, q, tg.mat, tg.y, base.p, st, lds_target);
     if (e != 0) return fail(MI_ERR_HIP, "LDS-streamed nuts kernel launch: %s", hipGetErrorString((hipError_t)e));
     const std::string lds_name = mi::host::last_kernel();
     {
         mi::lit::LitParams lp{};
-        rc = transpose_on_device(X_dev, rp.tbuf, (uint32_t)n_rows, (uint32_t)d, st);
-        if (rc) return rc;
-        if (dense) { lp.t.kind = mi::lit::LIT_DENSE; lp.t.d = (uint32_t)d; lp.t.prec = rp.tbuf; }
-        else {
-            lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.d = (uint32_t)d; lp.t.n_rows = (uint32_t)n_rows; lp.t.X = X_dev; lp.t.y = y_dev;
-            lp.t.Xt = rp.tbuf;
-        }
-        mi::lit::lit_orders(lp.t);
+        if ((rc = lit_staged_target(lp.t, tg, (uint32_t)d, rp.tbuf, st))) return rc;
         lit_common(lp, settings, &sc.dev, rp, false);
-        lp.n_adapt = q.n_adapt; lp.max_depth = q.max_depth;
-        lp.delta = q.delta; lp.gamma = q.gamma; lp.t0 = q.t0; lp.kappa = q.kappa;
-        lp.step_out = sc.dev.step_size; lp.depth_trace = sc.dev.nuts_depth; lp.adapt_state = sc.dev.nuts_adapt_state;
+        if ((rc = fill_nuts(lp, settings, chains, sc))) return rc;
         LitDev ldev;
         if (dense_m) {                                   // the replay's own copies of M, INV(M), CHOL_LOWER(M) (transposed: literal_host.hpp)
             mi::lit::LitPrep prep;
@@ -2675,19 +2553,12 @@ int run_lds_nuts(const mi_target* target, const mi_settings* settings, mi_chains
         }
         else lds_tables_replay(lt, q, lp);
         rc = launched("LDS-streamed nuts kernel (literal replay)", mi::launch_literal(2, lp, rp.n_wg, st));
-        if (!rc && q.n_exec_out) {                       // a replayed chain executed every leapfrog it counts
-            hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, rp.flag, q.n_leap_out, q.n_exec_out, C);
-            HIP_TRY(hipGetLastError());
-        }
+        if (!rc && q.n_exec_out) rc = copy_flagged_counts(rp.flag, q.n_leap_out, q.n_exec_out, C, st);      // a replayed chain executed every leapfrog it counts
         if (!rc && dense_m) HIP_TRY(hipStreamSynchronize(st));     // (the replay's matrices are ours)
-
         if (rc) return rc;
         mi::host::last_kernel() = lds_name;
     }
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
-    if (rc) return rc;
-    if (Xo.p || P_owned.p || lt.ms.p || dense_m || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, tg.owns() || lt.ms.p || dense_m, n_total);
 }
 // the cases nuts_lds.hpp covers (everything else on these targets: literal.hpp): no bounds / bounds with the identity or a diagonal precond_mat, and --
 // round 6 -- a DENSE precond_mat without bounds
@@ -2750,34 +2621,20 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     const uint64_t n = logit ? target->n_rows : 0;
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
     if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
-    DevBuf P_owned, Xo, yo;
-    const double *P_dev = nullptr, *X_dev = nullptr, *y_dev = nullptr;
-    if (logit) {
-        if (!target->X || !target->y || n == 0) return fail(MI_ERR_BAD_ARG, "LOGISTIC needs X, y, n_rows");
-        X_dev = target->X; y_dev = target->y;
-        if (target->mem == MI_MEM_HOST) {
-            HIP_TRY(Xo.alloc(n * d * sizeof(double))); HIP_TRY(yo.alloc(n * sizeof(double)));
-            HIP_TRY(hipMemcpy(Xo.p, target->X, n * d * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(yo.p, target->y, n * sizeof(double), hipMemcpyHostToDevice));
-            X_dev = Xo.as<double>(); y_dev = yo.as<double>();
-        }
-    } else {
-        rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-        if (rc) return rc;
-    }
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
     mi::gemm::GemmNutsRun g;
-    g.d = (uint32_t)d; g.C_total = C; g.chain0 = chains->chain0; g.P = P_dev; g.X = X_dev; g.y = y_dev; g.n_rows = (uint32_t)n;
-    g.theta = sc.dev.theta; g.draws = sc.dev.draws; g.n_accept = sc.dev.n_accept; g.n_leap = sc.dev.n_leapfrogs; g.n_exec = sc.dev.n_leapfrogs_executed;
+    fill_common(g, d, settings, chains, sc);             // (g.C: the range loop below sets it per range)
+    g.C_total = C; g.n_rows = (uint32_t)n;
+    if (logit) { g.X = tg.mat; g.y = tg.y; } else g.P = tg.mat;
+    g.n_leap = sc.dev.n_leapfrogs; g.n_exec = sc.dev.n_leapfrogs_executed;
     g.step = sc.dev.step_size; g.depth = sc.dev.nuts_depth; g.adapt = sc.dev.nuts_adapt_state;
     sc.exec_written = g.n_exec != nullptr;               // (every doubling on a memoised trajectory)
-    g.seed = settings->rng_seed_value;
-    g.n_burnin = (uint32_t)settings->n_burnin_draws; g.n_keep = (uint32_t)settings->n_keep_draws; g.draw0 = (uint32_t)chains->draw0;
-    if ((rc = nuts_continuation(settings, chains, &g.n_adapt))) return rc;
-    g.max_depth = (uint32_t)settings->max_tree_depth;
-    g.eps_bar0 = settings->step_size; g.delta = settings->target_accept_rate; g.gamma = settings->gamma_val; g.t0 = settings->t0_val; g.kappa = settings->kappa_val;
+    if ((rc = fill_nuts_adapt(g, settings, chains))) return rc;
+    g.eps_bar0 = settings->step_size;
     // identity or a DIAGONAL precond_mat: diag(M), CHOL_LOWER (sqrt), INV (reciprocal) from lit_prepare, in the oracle's operation order; the identity as tables of ones
     mi::lit::LitPrep prep;
     rc = mi::lit::lit_prepare(0, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
@@ -2821,72 +2678,66 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     g_gemm_nuts_ticks.store(ticks, std::memory_order_relaxed); g_gemm_nuts_points.store(points, std::memory_order_relaxed); g_gemm_nuts_slots.store(slots, std::memory_order_relaxed);
     {   // chains that reached the non-finite regime (or ran past the search's allowance): replayed literally (literal.hpp)
         mi::lit::LitParams lp{};
-        rc = transpose_on_device(logit ? X_dev : P_dev, rp.tbuf, (uint32_t)(logit ? n : d), (uint32_t)d, st);
-        if (rc) return rc;
-        if (logit) { lp.t.kind = mi::lit::LIT_LOGISTIC; lp.t.d = (uint32_t)d; lp.t.n_rows = (uint32_t)n; lp.t.X = X_dev; lp.t.y = y_dev; lp.t.Xt = rp.tbuf; }
-        else { lp.t.kind = mi::lit::LIT_DENSE; lp.t.d = (uint32_t)d; lp.t.prec = rp.tbuf; }
-        mi::lit::lit_orders(lp.t);
+        if ((rc = lit_staged_target(lp.t, tg, (uint32_t)d, rp.tbuf, st))) return rc;
         lit_common(lp, settings, &sc.dev, rp, false);
-        lp.n_adapt = g.n_adapt; lp.max_depth = g.max_depth;
-        lp.delta = g.delta; lp.gamma = g.gamma; lp.t0 = g.t0; lp.kappa = g.kappa;
-        lp.step_out = sc.dev.step_size; lp.depth_trace = sc.dev.nuts_depth; lp.adapt_state = sc.dev.nuts_adapt_state;
+        if ((rc = fill_nuts(lp, settings, chains, sc))) return rc;
         if (prep.precond == 1) { lp.precond = 1; lp.m = g.mass_tables; lp.m_sqrt = g.mass_tables + dK; lp.m_inv = g.mass_tables + 2 * (size_t)dK; }
         rc = launched("matrix-product nuts (literal replay)", mi::launch_literal(2, lp, rp.n_wg, st));
         if (rc) return rc;
-        if (g.n_exec) {                                  // a replayed chain executed every leapfrog it counts
-            hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, rp.flag, g.n_leap, g.n_exec, C);
-            HIP_TRY(hipGetLastError());
-        }
+        if (g.n_exec && (rc = copy_flagged_counts(rp.flag, g.n_leap, g.n_exec, C, st))) return rc;      // a replayed chain executed every leapfrog it counts
     }
     mi::note_kernel("%s", kname);
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));                  // (the mass tables are ours)
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, true, n_total);      // (the mass tables are ours)
 }
 
-int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+namespace {
+// The memoised kernel (nuts_memo.hpp; gt: its DIAGM form with the two mass tables of a diagonal precond_mat), whose name last_kernel() keeps.  Behind it the general
+// variant replays the chains it flagged as non-finite -- with gt's tables or, gt null (the plain case), with identity tables filled into id_tab: it reproduces the
+// reference's dense products --, and a replayed chain executed every leapfrog it counts
+static int nuts_memo_and_replay(mi::NutsParams& prm, StagedChains& sc, int nt, const GeneralTables* gt, uint32_t* nf_flag, double* id_tab, uint32_t nuts_batch, hipStream_t st)
 {
-    int rc = check_common(target, settings, chains);
+    const uint64_t C = prm.C;
+    HIP_TRY(hipMemsetAsync(nf_flag, 0, (C + 1) * sizeof(uint32_t), st));
+    prm.nf_flag = nf_flag;
+    if (gt) { prm.m_sqrt = gt->ms_dev.as<double>(); prm.m_inv = gt->mi_dev.as<double>(); }
+    prm.n_exec = sc.dev.n_leapfrogs_executed; sc.exec_written = prm.n_exec != nullptr;
+    int rc = launched("nuts", mi::launch_nuts_gauss_memo(prm, nt, st, gt != nullptr));
     if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint64_t d = target->d;
-    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("nuts", 2, target, settings, chains, st);
-    if (target->kind == MI_TARGET_LOGISTIC) {
-        if (d <= (uint64_t)mi::SMALL_MAX_D && settings->max_tree_depth <= 10) return run_small_logistic("nuts", 2, target, settings, chains, st);
-        if (d <= 512 && lds_nuts_case(target, settings)) return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC);
-        GemmNutsPlan plan;
-        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, two matrix products per tick
-        return run_literal("nuts", 2, target, settings, chains, st);
+    const std::string reg_name = mi::host::last_kernel();
+    mi::NutsParams rp = prm;
+    rp.n_exec = nullptr;
+    rp.nf_flag = nullptr; rp.replay_flag = nf_flag;
+    if (gt) { rp.btype = gt->bt.as<int>(); rp.lb = gt->lb.as<double>(); rp.ub = gt->ub.as<double>(); }
+    else {
+        int* bt_i = reinterpret_cast<int*>(id_tab);
+        hipLaunchKernelGGL(fill_identity_tables_kernel, dim3(1), dim3(128), 0, st, bt_i, id_tab + 128, id_tab + 256, id_tab + 384, id_tab + 512, 128u);
+        HIP_TRY(hipGetLastError());
+        rp.btype = bt_i; rp.lb = id_tab + 128; rp.ub = id_tab + 256; rp.m_sqrt = id_tab + 384; rp.m_inv = id_tab + 512;
     }
-    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
-        return fail(MI_ERR_UNSUPPORTED, "nuts: target kind %d not implemented", target->kind);
-    // the tiled kernels: d <= 128, max_tree_depth <= 10 (per-level records and scalars are sized for that); beyond, literal.hpp
-    if (target->kind == MI_TARGET_GAUSS_DENSE && d > 128 && d <= 512 && lds_nuts_case(target, settings))
-        return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (nuts_lds.hpp)
-    {
-        GemmNutsPlan plan;
-        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, one matrix product per tick (gemm_nuts.hpp)
-    }
-    if (d > 128 || settings->max_tree_depth > (uint64_t)mi::NUTS_MAX_DEPTH) return run_literal("nuts", 2, target, settings, chains, st);
-    const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
-    if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    rp.vals_bound = 0;
+    rc = launched("nuts (replay)", mi::launch_nuts_gauss(rp, nt, true, false, false, nuts_batch, st));
+    mi::host::last_kernel() = reg_name;
+    if (!rc && prm.n_exec) rc = copy_flagged_counts(nf_flag, prm.n_leap, prm.n_exec, C, st);
+    return rc;
+}
 
-    DevBuf P_owned;
-    const double* P_dev = nullptr;
-    rc = dense_precision_on_device(target, P_owned, &P_dev, st);
-    if (rc) return rc;
+// nuts on the Gaussian kinds with d <= 128, max_tree_depth <= 10: the tile kernels -- the memoised trajectory (nuts_memo.hpp; plain or a diagonal precond_mat alone),
+// its bounded form (nuts_bounded_launch.hip), the asynchronous general variants (nuts_async.hpp: a dense precond_mat, the hints)
+static int run_nuts_tile(const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
+{
+    int rc;
+    const uint64_t d = target->d;
+    const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
+    StagedTarget tg;
+    if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
     rc = stage_in(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
 
     mi::NutsParams prm{};
-    prm.P = P_dev;
-    prm.d = (uint32_t)d;
+    fill_common(prm, d, settings, chains, sc);
+    prm.P = tg.mat;
     prm.sep_target = target->kind != MI_TARGET_GAUSS_DENSE;     // ISO / DIAG: the general variants (and the replay of flagged chains, which is one) take the gradient element-wise
-    prm.C = chains->n_chains;
-    prm.chain0 = chains->chain0;
-    prm.theta = sc.dev.theta;
     const int nt = (int)((d + 15) / 16);
     GeneralTables gt;
     rc = general_tables("nuts", settings, d, gt, true, true);
@@ -2930,32 +2781,18 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
     uint32_t* const nf_flag = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.p) + ws_own_r);
     double* const id_tab = reinterpret_cast<double*>(static_cast<char*>(ws.p) + ws_own_r + flag_bytes);
     prm.next_chain = reinterpret_cast<uint32_t*>(static_cast<char*>(ws.p) + ((ws_own_r + flag_bytes + 5 * 128 * sizeof(double) + 255) & ~(size_t)255));
-    prm.draws = sc.dev.draws;
-    prm.n_accept = sc.dev.n_accept;
     prm.n_leap = sc.dev.n_leapfrogs;
-    prm.step_out = sc.dev.step_size;
-    prm.depth_trace = sc.dev.nuts_depth;
 #ifdef MI_PROFILING
     DevBuf prof_buf;
     if (getenv("MI_NUTS_PROF")) { HIP_TRY(prof_buf.alloc(96 * 8)); HIP_TRY(hipMemset(prof_buf.p, 0, 96 * 8)); prm.prof = prof_buf.as<unsigned long long>();
 }
 #endif
-    prm.seed = settings->rng_seed_value;
-    prm.n_burnin = (uint32_t)settings->n_burnin_draws;
-    prm.n_keep = (uint32_t)settings->n_keep_draws;
-    prm.draw0 = (uint32_t)chains->draw0;
     // continuation (checkpoint / resume): the step sizes come back in; inside the adaptation window also the dual-averaging state.
     // (The lock-step hint cannot be honoured for a continuation -- that kernel keeps no per-chain step size: as mi_mcmc.h promises for a
     //  hint the request cannot take, it is ignored and the default kernel runs; it also clamps the window to the call, nuts.cpp:54, which is
     //  the same thing for the single call it serves.)
-    if ((rc = nuts_continuation(settings, chains, &prm.n_adapt))) return rc;
-    prm.adapt_state = sc.dev.nuts_adapt_state;
-    prm.max_depth = (uint32_t)settings->max_tree_depth;
-    prm.delta = settings->target_accept_rate;
+    if ((rc = fill_nuts(prm, settings, chains, sc))) return rc;
     prm.eps_bar0 = settings->step_size;
-    prm.gamma = settings->gamma_val;
-    prm.t0 = settings->t0_val;
-    prm.kappa = settings->kappa_val;
 
     uint32_t nuts_batch = 8;                 // momentum-refresh batch of the asynchronous kernel
 #ifdef MI_PROFILING
@@ -2972,24 +2809,7 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
     else if (gt.active && memo) {
         // a diagonal precond_mat alone: the plain-case kernel with two mass tables (nuts_memo.hpp, DIAGM); flagged chains are replayed
         // by the general variant with the same tables
-        HIP_TRY(hipMemsetAsync(nf_flag, 0, (chains->n_chains + 1) * sizeof(uint32_t), st));
-        prm.nf_flag = nf_flag;
-        prm.m_sqrt = gt.ms_dev.as<double>(); prm.m_inv = gt.mi_dev.as<double>();
-        prm.n_exec = sc.dev.n_leapfrogs_executed; sc.exec_written = prm.n_exec != nullptr;
-        rc = launched("nuts", mi::launch_nuts_gauss_memo(prm, nt, st, true));
-        if (rc) return rc;
-        const std::string reg_name = mi::host::last_kernel();
-        mi::NutsParams rp = prm;
-        rp.n_exec = nullptr;
-        rp.nf_flag = nullptr; rp.replay_flag = nf_flag;
-        rp.btype = gt.bt.as<int>(); rp.lb = gt.lb.as<double>(); rp.ub = gt.ub.as<double>();
-        rp.vals_bound = 0;
-        rc = launched("nuts (replay)", mi::launch_nuts_gauss(rp, nt, true, false, false, nuts_batch, st));
-        mi::host::last_kernel() = reg_name;
-        if (!rc && prm.n_exec) {
-            hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((chains->n_chains + 255) / 256)), dim3(256), 0, st, nf_flag, prm.n_leap, prm.n_exec, chains->n_chains);
-            HIP_TRY(hipGetLastError());
-        }
+        rc = nuts_memo_and_replay(prm, sc, nt, &gt, nf_flag, id_tab, nuts_batch, st);
         if (!rc) HIP_TRY(hipStreamSynchronize(st));     // the tables are ours
     }
     else if (gt.active) {
@@ -3007,31 +2827,8 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
     else {
         // the plain case: nuts_gauss_memo_kernel; chains that reach the non-finite regime are flagged there and
         // replayed by the general variant, which reproduces the reference's dense products, with identity tables
-        HIP_TRY(hipMemsetAsync(nf_flag, 0, (chains->n_chains + 1) * sizeof(uint32_t), st));
-        prm.nf_flag = nf_flag;
-        const uint64_t C_ = chains->n_chains;
-        prm.n_exec = sc.dev.n_leapfrogs_executed; sc.exec_written = prm.n_exec != nullptr;
-        rc = launched("nuts", mi::launch_nuts_gauss_memo(prm, nt, st));
-        if (rc) return rc;
-        const std::string reg_name = mi::host::last_kernel();
-        int* bt_i = reinterpret_cast<int*>(id_tab);
-        hipLaunchKernelGGL(fill_identity_tables_kernel, dim3(1), dim3(128), 0, st, bt_i, id_tab + 128, id_tab + 256, id_tab + 384, id_tab + 512, 128u);
-        HIP_TRY(hipGetLastError());
-        mi::NutsParams rp = prm;
-        rp.n_exec = nullptr;
-        rp.nf_flag = nullptr; rp.replay_flag = nf_flag;
-        rp.btype = bt_i; rp.lb = id_tab + 128; rp.ub = id_tab + 256; rp.m_sqrt = id_tab + 384; rp.m_inv = id_tab + 512;
-        rp.vals_bound = 0;
-        rc = launched("nuts (replay)", mi::launch_nuts_gauss(rp, nt, true, false, false, nuts_batch, st));
-        mi::host::last_kernel() = reg_name;
-        if (!rc && prm.n_exec) {
-            hipLaunchKernelGGL(copy_flagged_counts_kernel, dim3((unsigned)((C_ + 255) / 256)), dim3(256), 0, st, nf_flag, prm.n_leap, prm.n_exec, C_);
-            HIP_TRY(hipGetLastError());
-        }
+        rc = nuts_memo_and_replay(prm, sc, nt, nullptr, nf_flag, id_tab, nuts_batch, st);
     }
-    if (rc) return rc;
-
-    rc = stage_out(chains, d, settings->n_keep_draws, sc, st, n_total);
     if (rc) return rc;
 #ifdef MI_PROFILING
     if (prm.prof) {
@@ -3048,8 +2845,37 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
                 (double)tot / (h[12] ? h[12] : 1), h[13], (double)h[13] / (h[12] ? h[12] : 1), h[10], (double)h[10] / (h[12] ? h[12] : 1), h[14], h[15]);
     }
 #endif
-    if (P_owned.p || chains->mem == MI_MEM_HOST) HIP_TRY(hipStreamSynchronize(st));
-    return MI_OK;
+    return finish(chains, d, settings, sc, st, NO_LEAP_FILL, tg.owns(), n_total);
+}
+}  // namespace
+
+int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream)
+{
+    int rc = check_common(target, settings, chains);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint64_t d = target->d;
+    if (target->kind == MI_TARGET_NORMAL_MODEL) return run_small_normal_model("nuts", 2, target, settings, chains, st);
+    if (target->kind == MI_TARGET_LOGISTIC) {
+        if (d <= (uint64_t)mi::SMALL_MAX_D && settings->max_tree_depth <= 10) return run_small_logistic("nuts", 2, target, settings, chains, st);
+        if (d <= 512 && lds_nuts_case(target, settings)) return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC);
+        GemmNutsPlan plan;
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, two matrix products per tick
+        return run_literal("nuts", 2, target, settings, chains, st);
+    }
+    if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
+        return fail(MI_ERR_UNSUPPORTED, "nuts: target kind %d not implemented", target->kind);
+    // the tiled kernels: d <= 128, max_tree_depth <= 10 (per-level records and scalars are sized for that); beyond, literal.hpp
+    if (target->kind == MI_TARGET_GAUSS_DENSE && d > 128 && d <= 512 && lds_nuts_case(target, settings))
+        return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (nuts_lds.hpp)
+    {
+        GemmNutsPlan plan;
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, one matrix product per tick (gemm_nuts.hpp)
+    }
+    if (d > 128 || settings->max_tree_depth > (uint64_t)mi::NUTS_MAX_DEPTH) return run_literal("nuts", 2, target, settings, chains, st);
+    const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
+    if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    return run_nuts_tile(target, settings, chains, st);
 }
 
 // mcmc::rmhmc (src/rmhmc.cpp:30-287) for many chains of a small-dimensional target with a built-in metric tensor.
