@@ -1,6 +1,6 @@
-// host_common.hpp -- shared by the host-side translation units of the C ABI (mi_mcmc.hip: the samplers; callback_host.hip: the
-// host-callback routes; draws_api.hip and draw_stats.hip: the reducers over a draws slab; stats_collate.hip: multi-GPU collation and the
-// host layout converter; probes.hip: diagnostics): the error channel (status code + thread-local message behind mi_mcmc_last_error), the
+// host_common.hpp -- shared by the host-side translation units of the C ABI (mi_mcmc.hip: the samplers; mass_adapt.hip: the mass adaptations
+// above them, over sampler_host.hpp; callback_host.hip: the host-callback routes; draws_api.hip and draw_stats.hip: the reducers over a draws
+// slab; stats_collate.hip: multi-GPU collation and the host layout converter; probes.hip: diagnostics): the error channel (status code + thread-local message behind mi_mcmc_last_error), the
 // device probe, the RAII device buffer and the staging of a host slab.  The workspace cache the samplers and the reducers share is workspace.hpp.
 #pragma once
 

@@ -1,6 +1,9 @@
 // host_linalg.hpp -- INV / CHOL_LOWER of a dense precond_mat in the operation order the oracle states for the reference's BMO_MATOPS_INV /
-// BMO_MATOPS_CHOL_LOWER, shared by the C ABI (mi_mcmc.hip), the literal replay preparation (literal_host.hpp) and its host test shim: the host
-// loops, and the switch to their device form (linalg_device.hip) that the product installs.
+// BMO_MATOPS_CHOL_LOWER, shared by the host files of the C ABI that factorise (mi_mcmc.hip, mass_adapt.hip), the literal
+// replay preparation (literal_host.hpp) and its host test shim: the host loops, and the switch to their device form (linalg_device.hip) that the
+// product installs.  The loops are file-local (each translation unit its own copy of the same statements); the STATE -- what is installed, the
+// staging budget, the counters, the memo -- is inline with external linkage: one per library, whichever translation unit asks
+// (tests/test_linalg_state_cpu.py).
 #pragma once
 
 #include <atomic>
@@ -53,16 +56,18 @@ inline void host_inverse_compute(const double* A, size_t d, std::vector<double>&
     }
 }
 
+}  // namespace
+
 // Where the factorisations run.  The product (mi_mcmc.hip) installs the device implementations (linalg_device.hip: the same IEEE operations per
-// element, hence the same bits, as one cooperative launch instead of 89 ms / 40 ms of one host core at d = 512) for d >= min_d; a translation
-// unit that installs nothing (the host test shim tests/lit_host.hip) runs the loops above.  A device failure is an ERROR (the status is returned
+// element, hence the same bits, as one cooperative launch instead of 89 ms / 40 ms of one host core at d = 512) for d >= min_d; a
+// library that installs nothing (the host test shim tests/lit_host.hip) runs the loops above.  A device failure is an ERROR (the status is returned
 // and mi_mcmc_last_error says why), never a silent switch to the host loops.
 //
 // CAPACITY is a routing condition, not an error: the device kernels stage the scaled pivot row of the working copy and of the inverse (INV:
 // 2 d doubles), resp. the finished column (CHOL_LOWER: d doubles), in LDS.  A matrix whose staging exceeds the budget -- LINALG_STAGE_BYTES:
 // d > 3840 for INV, d > 7680 for CHOL_LOWER -- runs the host loops of this file: the same statements, the same bits, one host core (as every such
 // call ran before the device kernels existed).  TEST HOOK (mi_mcmc_test_set_linalg_stage_bytes, mi_mcmc_probes.h): a smaller budget for this
-// process, so that the routing runs at sizes where the oracle costs milliseconds; every change of it starts a new epoch, and a memo of
+// library, so that the routing runs at sizes where the oracle costs milliseconds; every change of it starts a new epoch, and a memo of
 // another epoch is emptied before it is read (a result computed under one setting never answers a call under the other).
 struct LinalgAccel {
     int (*inverse)(const double* A, size_t d, double* Ainv) = nullptr;
@@ -90,7 +95,8 @@ inline bool linalg_on_device(int which, size_t d)
 
 // INV behind a two-entry memo keyed by the matrix itself: one sampler call asks for the same inverse more than once (its own and the literal
 // replay's preparation; mala: INV(M) and INV(eps^2 M)), as do the calls of a run cut into pieces (checkpoint / resume) -- a deterministic function
-// of its input, so the copy has the bits of a recomputation.  Per thread; small matrices are not kept; mi_mcmc_release_workspace empties it.
+// of its input, so the copy has the bits of a recomputation.  One per thread of the library; small matrices are not kept;
+// mi_mcmc_release_workspace empties it.
 struct LinalgMemoEntry { std::vector<double> key, val; };
 struct LinalgMemo { LinalgMemoEntry e[2]; int last = 0; uint64_t epoch = 0; };
 inline LinalgMemo& linalg_memo_raw(int which) { static thread_local LinalgMemo m[2]; return m[which]; }      // 0: INV, 1: CHOL_LOWER
@@ -166,5 +172,3 @@ inline int host_cholesky_lower(const double* A, size_t d, std::vector<double>& L
     if (d >= 64) linalg_memo_keep(1, A, d * d, L);
     return 0;
 }
-
-}  // namespace
