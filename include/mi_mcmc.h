@@ -61,16 +61,19 @@ typedef enum mi_target_kind {
                                  * same kernel, d <= 3840 and a workspace that fits the free device memory; otherwise the literal kernels);
                                  * hmc (identity / diagonal precond_mat) and rwmh (no cov_mat) there also with vals_bound: the chains in the transformed space, the products at
                                  * x = inv_transform(theta), J(theta) g in the product's epilogue (three more state vectors in the workspace; what does not fit the free device
-                                 * memory, bounds with a dense precond_mat or chains.mass_diag, bounded nuts: the literal kernels; bounded mala beyond d = 512: MI_ERR_UNSUPPORTED);
-                                 * nuts there without bounds, with the identity or a DIAGONAL precond_mat and 1 <= max_tree_depth <= 10: per-chain memoised trees, every chain
+                                 * memory, bounds with a dense precond_mat or chains.mass_diag: the literal kernels; bounded mala beyond d = 512: MI_ERR_UNSUPPORTED);
+                                 * nuts there with or without vals_bound, with the identity or a DIAGONAL precond_mat and 1 <= max_tree_depth <= 10: per-chain memoised trees, every chain
                                  * at its own point of its own doubling of its own draw, the gradients of all chains as the products of one TICK (gemm_nuts.hpp); the host
                                  * polls a device counter of running chains -- nothing waits on the device -- up to a tick ceiling computed from the settings
-                                 * (beyond it: MI_ERR_HIP).  Capacity rule: a chain holds 11 + 2 (1 + (D - 1) D / 2) vectors of d (padded to 16) doubles, D = max_tree_depth,
+                                 * (beyond it: MI_ERR_HIP).  With vals_bound the chain's last point, prev_draw, the point records and the tree's edges hold theta in the
+                                 * transformed space, the products are taken at x = inv_transform(theta), J(theta) g is applied in the product's epilogue (gemm_step_kernel<13, .>)
+                                 * and it is x that leaves.  Capacity rule: a chain holds 11 + 2 (1 + (D - 1) D / 2) vectors of d (padded to 16) doubles, D = max_tree_depth,
+                                 * with vals_bound ONE more such vector (theta of the last point next to x),
                                  * the logistic target two more of n_rows (padded to 16), and 5.9 KB of scalars (0.85 MB at d = 1024, D = 10); next to the chains the
                                  * call needs the packed matrices, the literal replay's areas and, for chains / a target in host memory, their staged copies, which are
                                  * counted.  Chains that do not fit the free device memory together run as consecutive ranges, in multiples of 128
-                                 * (same bits: the random numbers are counter-based on the global chain index); where not even 128 fit, and for bounded nuts, a dense
-                                 * precond_mat, max_tree_depth > 10 and mi_mcmc_nuts_run_callback: the literal kernels;
+                                 * (same bits: the random numbers are counter-based on the global chain index); where not even 128 fit, and for a dense
+                                 * precond_mat, max_tree_depth > 10, vals_bound with fewer than 16 chains and mi_mcmc_nuts_run_callback: the literal kernels;
                                  * the same for MI_TARGET_GAUSS_DENSE beyond d = 512 (one product per gradient) */
     MI_TARGET_NORMAL_MODEL = 5, /* d = 2, vals = (mu, sigma), observations x_1..x_n in y[0..n_rows): the model of the reference's
                                  * example programs (/root/reference/examples/eigen/rmhmc_normal.cpp:44-106),

@@ -338,6 +338,12 @@ def test_gemm_nuts_chain_bytes(d, n_rows, max_tree_depth):
     return _u64_hook("mi_mcmc_test_gemm_nuts_chain_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint32(int(max_tree_depth)))
 
 
+def test_gemm_nuts_bounded_chain_bytes(d, n_rows, max_tree_depth):
+    """mi_mcmc_test_gemm_nuts_bounded_chain_bytes (TEST HOOK; host arithmetic): workspace bytes per chain of a call with vals_bound -- one vector of padded d doubles
+    more than test_gemm_nuts_chain_bytes (theta of the last point next to x)."""
+    return _u64_hook("mi_mcmc_test_gemm_nuts_bounded_chain_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint32(int(max_tree_depth)))
+
+
 def test_gemm_nuts_fixed_bytes(d, n_rows):
     """mi_mcmc_test_gemm_nuts_fixed_bytes (TEST HOOK; host arithmetic): workspace bytes that do not depend on the chains (the packed matrices, the counters)."""
     return _u64_hook("mi_mcmc_test_gemm_nuts_fixed_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)))

@@ -2,7 +2,7 @@
 // inside namespace mi::gemm: it shares gemm_step_kernel, gemm_rowterm_kernel, log_kernel_value and class_sum).
 //
 // Replaces, for C independent chains, mcmc::internal::nuts_impl with nuts_find_initial_step_size and the recursive nuts_build_tree (ref: src/nuts.cpp:30-332,
-// include/mcmc/nuts.ipp:30-241; leap_frog_fn src/nuts.cpp:139-154), identity or DIAGONAL precond_mat, no bounds, 1 <= max_tree_depth <= 10.  Before, such a call ran
+// include/mcmc/nuts.ipp:30-241; leap_frog_fn src/nuts.cpp:139-154), identity or DIAGONAL precond_mat, with or without settings.vals_bound (the BOX instantiations below), 1 <= max_tree_depth <= 10.  Before, such a call ran
 // on literal_kernel<2>: one workgroup per chain, every leaf of every doubling executed.
 //
 // The sampler is nuts_lds.hpp's machine -- every doubling on the MEMOISED trajectory (nuts_memo.hpp, DESIGN.md 4.4e: leaf i of a doubling is the state
@@ -35,6 +35,10 @@
 // replay (which loops as the reference does), and a ceiling reached with chains still running is an error, never a longer loop.
 // Non-finite regime: detected through the energies of every point; the chain is flagged (nf_flag), takes no further part and is replayed by literal_kernel<2>.
 // n_leap_out reports the REFERENCE's count (one per leaf walked plus the search), n_exec_out the leapfrogs really made.
+// settings.vals_bound (BOX; nuts.cpp:93-135,158-162): the chain lives in the transformed space -- the last point TH, prev_draw, the records and the edges hold theta, X
+// holds x = inv_transform(theta), which the product reads; the half-kicks take J(theta) g (the second one in the epilogue EP_NUTS_BOX = 13, the RAW gradient stored),
+// U = -(log K(x) + log_jacobian(theta)), K, the records and the U-turn tests run on theta and p, and it is x that leaves (the kept rows, chains.theta).  The unbounded
+// instantiations keep their code.
 
 namespace nuts {
 enum : int { NS_NEED_DRAW = 0, NS_TREE = 1, NS_DONE = 2, NS_INIT = 3, NS_SEARCH = 4, NS_REGRAD = 5 };
@@ -77,6 +81,8 @@ struct TickParams {
     uint64_t seed;
     uint32_t n_burnin, n_total, draw0, n_adapt, max_depth, search_allowance;
     double eps_bar0, delta, gamma, t0, kappa;
+    double* TH;              // BOX: theta of the last point in the transformed space (X = inv_transform(TH); prev_draw, the records and the edges hold theta).  Behind the
+                             // fields of the unbounded tick, which keep their offsets
 };
 
 __global__ void nuts_init_kernel(const TickParams prm)
@@ -94,7 +100,9 @@ __global__ void nuts_init_kernel(const TickParams prm)
     if (blockIdx.x == 0 && threadIdx.x == 0) { *prm.running = (uint32_t)prm.C; *prm.points = 0ull; }
 }
 
-// one Philox slot -- two dimensions (slot_dims) -- per thread
+// one Philox slot -- two dimensions (slot_dims) -- per thread.  BOX (settings.vals_bound): the chain moves in the transformed space -- the half-kick takes J(theta) g
+// (nuts.cpp:108-135), the drift moves theta, and x = inv_transform(theta') is what the product reads (:115); the initial values go through transform (:158-162)
+template <bool BOX>
 __global__ __launch_bounds__(256) void nuts_prepare_kernel(const TickParams prm)
 {
     using namespace nuts;
@@ -114,6 +122,38 @@ __global__ __launch_bounds__(256) void nuts_prepare_kernel(const TickParams prm)
     for (int h = 0; h < 2; ++h) {
         const uint32_t i = dim[h];
         const size_t e = (size_t)i * prm.Cp + c;
+        if constexpr (BOX) {
+            const BoxParams& bx = prm.lk.bx;
+            const bool boxed = bx.blocks[i >> 4] != 0u;      // (both dimensions of a slot sit in one 16-dimension block)
+            const int bt = boxed ? bx.bt[i] : 1;
+            const double lo = boxed ? bx.lb[i] : 0.0, hi = boxed ? bx.ub[i] : 0.0;
+            auto inv = [&](double t) -> double { return boxed ? box_inv_transform(t, bt, lo, hi) : t; };
+            if (mode == CM_STEP || mode == CM_ORIGIN) {      // the first half-kick with J(theta) g and the drift of theta, from the last point or from the origin of a doubling
+                const bool org = mode == CM_ORIGIN;
+                const double th = org ? prev[e] : prm.TH[e], g = org ? prm.gprev[e] : prm.G[e];
+                const double jg = boxed ? dfma(box_inv_jacobian(th, bt, lo, hi), g, 0.0) : g;
+                const double p = (org ? prm.mntm[e] : prm.pm[e]) + (ec * jg) / 2.0;
+                const double tn = th + ec * (prm.m_inv[i] * p);
+                prm.pm[e] = p;
+                prm.TH[e] = tn;
+                prm.X[e] = inv(tn);
+            } else if (mode == CM_REGRAD || mode == CM_DRAW) {
+                const double p = mode == CM_DRAW ? prm.m_sqrt[i] * z[h] : prm.mntm[e];
+                const double th = prev[e];
+                if (mode == CM_DRAW) prm.mntm[e] = p;
+                prm.pm[e] = p;
+                prm.TH[e] = th;
+                prm.X[e] = inv(th);
+            } else {                                         // CM_INIT: first_draw = transform(initial_vals) (:158-162) and z_init
+                const bool in = i < prm.d && c < prm.C;
+                const double t = in ? box_transform(prm.theta[(size_t)i * prm.Ct + prm.c_off + c], bx.bt[i], bx.lb[i], bx.ub[i]) : 0.0;
+                prm.TH[e] = t;
+                prm.prev0[e] = t;
+                prm.X[e] = in ? box_inv_transform(t, bx.bt[i], bx.lb[i], bx.ub[i]) : 0.0;
+                prm.pm[e] = prm.m_sqrt[i] * z[h];
+            }
+            continue;
+        }
         if (mode == CM_STEP) {                               // the next point from the last one (nuts.cpp:139-154): p += (e g) / 2, theta += e (Minv p)
             const double p = prm.pm[e] + (ec * prm.G[e]) / 2.0;
             prm.pm[e] = p;
@@ -139,7 +179,7 @@ __global__ __launch_bounds__(256) void nuts_prepare_kernel(const TickParams prm)
     }
 }
 
-template <int TGT>
+template <int TGT, bool BOX>
 __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
 {
     using namespace nuts;
@@ -178,6 +218,7 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
     const unsigned long long busy = __ballot(state != NS_DONE) & 0xffffull;      // (lanes 0 .. 15: one per chain of the wave)
     if (lane == 0) atomicAdd(prm.points, (unsigned long long)__builtin_popcountll(busy));
     auto pvec = [&](int b) -> double* { return b ? prm.prev1 : prm.prev0; };
+    const double* const pos = BOX ? prm.TH : prm.X;      // the point as the chain sees it: with bounds theta, in the transformed space (K, the records, the U-turn tests)
 
     // ------------------------------------------------------------ the new point: K, U, its record, the far edge of the tree, the gradient at prev_draw
     const uint32_t mpt = npts + 1u;                      // the point this tick computed (run lanes)
@@ -197,7 +238,7 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
 #pragma unroll 4
         for (uint32_t i = (uint32_t)j; i < dK; i += 4u) {
             const size_t e = (size_t)i * Cp + c;
-            const double x = prm.X[e], p = prm.pm[e];
+            const double x = pos[e], p = prm.pm[e];
             qk = dfma(p, prm.m_inv[i] * p, qk);              // K = p . (Minv p) / 2 (nuts.ipp:51,66,140; nuts.cpp:204)
             if (st_rec) { rt[e] = x; rp[e] = p; }
             if (st_edge) { et[e] = x; ep[e] = p; }
@@ -206,7 +247,8 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
         if (st_edge) { if (vdir > 0) pos_init = false; else neg_init = false; }
         pK = class_sum(qk) / 2.0;
     }
-    const double val = log_kernel_value<TGT>(prm.lk, prm.X, prm.G, c, j);
+    double val = log_kernel_value<TGT>(prm.lk, prm.X, prm.G, c, j);
+    if constexpr (BOX) val = val + box_log_jacobian(prm.lk, prm.TH, c, lane);      // box_log_kernel (nuts.cpp:93-104): log K(x) + log_jacobian(theta)
     // ------------------------------------------------------------ the U-turn tests this point closes: level l against point mpt - l (nuts.ipp:224-229)
     while (any(pmask != 0u)) {
         const bool t = pmask != 0u;
@@ -218,7 +260,7 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
         for (uint32_t i = (uint32_t)j; i < dK; i += 4u) {
             const size_t e = (size_t)i * Cp + c;
             const double tb = t ? rt[e] : 0.0, pbv = t ? rp[e] : 0.0;
-            const double x = prm.X[e], p = prm.pm[e];
+            const double x = pos[e], p = prm.pm[e];
             const double dd = (vdir > 0) ? (x - tb) : (tb - x);
             r1 = dfma(dd, pbv, r1);
             r2 = dfma(dd, p, r2);
@@ -415,10 +457,15 @@ __global__ __launch_bounds__(256) void nuts_point_kernel(const TickParams prm)
     if (any(row || retire)) {
         const double* const src = pvec(pb);
         double* const out = row ? prm.draws + (size_t)row_idx * prm.d * prm.Ct + cg : nullptr;
+        constexpr int UNROLL = BOX ? 1 : 4;              // (the bounded loop calls out of line)
         if (row || retire)
-#pragma unroll 4
+#pragma unroll UNROLL
             for (uint32_t i = (uint32_t)j; i < prm.d; i += 4u) {
-                const double v = src[(size_t)i * Cp + c];
+                double v = src[(size_t)i * Cp + c];
+                if constexpr (BOX) {                         // it is x = inv_transform(theta) that leaves (nuts.cpp: the final inv_transform of draws_out)
+                    const BoxParams& bx = prm.lk.bx;
+                    if (bx.blocks[i >> 4] != 0u) v = box_inv_transform(v, bx.bt[i], bx.lb[i], bx.ub[i]);
+                }
                 if (row && !flagged) out[(size_t)i * prm.Ct] = v;                   // nuts.cpp:306-309
                 if (retire) prm.theta[(size_t)i * prm.Ct + cg] = v;
             }
@@ -474,16 +521,18 @@ uint64_t gemm_nuts_tick_ceiling(uint32_t max_depth, uint64_t n_total, bool searc
     return 1 + (search ? (uint64_t)NUTS_SEARCH_TICKS + 1 : 0) + n_total * (1 + (uint64_t)(max_depth - 1) + pts);
 }
 // The workspace of a range of Cp columns (gemm_samplers.hip: Carve): first what does not depend on the chains -- the packed matrices, the counters --, then per chain the
-// fixed vectors and 2 (theta, p) x gemm_nuts_points record vectors of gemm_padded_d(d) doubles, the logistic target's two row-term vectors, the scalars, the column words
+// fixed vectors and 2 (theta, p) x gemm_nuts_points record vectors of gemm_padded_d(d) doubles, the logistic target's two row-term vectors, the scalars, the column words;
+// with bounds ONE more vector behind them all: theta of the last point (the eleven fixed vectors keep their places)
 struct NutsWs : TargetWs {
     double* ctr;               // 32 doubles: the two counters
     double* fix[nuts::NFIX];   // X, pm, G | prev_draw x 2, its gradient | mntm_vec | the four edge vectors
     double* rec;
     double *sc, *ecol;
     uint32_t *colmode, *pbsel, *didx;
+    double* th;                // vals_bound: theta of the last point
     size_t fixed, n_doubles;   // doubles that do not depend on the chains, and all of them
 };
-static NutsWs gemm_nuts_carve(uint32_t d, uint32_t n_rows, uint32_t max_depth, uint64_t Cp, double* base)
+static NutsWs gemm_nuts_carve(uint32_t d, uint32_t n_rows, uint32_t max_depth, uint64_t Cp, bool bounded, double* base)
 {
     NutsWs w{};
     w.l = layout_of(d, n_rows, Cp);
@@ -499,16 +548,17 @@ static NutsWs gemm_nuts_carve(uint32_t d, uint32_t n_rows, uint32_t max_depth, u
     w.ecol = cv.take(l.Cp);
     w.colmode = reinterpret_cast<uint32_t*>(cv.take(2 * l.Cp));              // 3 Cp words in 2 Cp doubles
     w.pbsel = w.colmode + l.Cp; w.didx = w.pbsel + l.Cp;
+    if (bounded) w.th = cv.take(l.vec);
     w.n_doubles = cv.n;
     return w;
 }
 // bytes per chain (every region behind the fixed ones is a multiple of the columns: one column counts them), and of what does not depend on the chains
-size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth)
+size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth, bool bounded)
 {
-    const NutsWs w = gemm_nuts_carve(d, n_rows, max_depth, 1, nullptr);
+    const NutsWs w = gemm_nuts_carve(d, n_rows, max_depth, 1, bounded, nullptr);
     return (w.n_doubles - w.fixed) * sizeof(double);
 }
-size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows) { return gemm_nuts_carve(d, n_rows, 1, 1, nullptr).fixed * sizeof(double); }
+size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows) { return gemm_nuts_carve(d, n_rows, 1, 1, false, nullptr).fixed * sizeof(double); }
 // chains per range when `budget` bytes are there for the route's own workspace: all of them (rounded up to the chain tile) if they fit, else the largest multiple
 // of 128 that does; 0: not even one tile -- the call stays on the literal kernel
 uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_bytes, size_t budget)
@@ -519,17 +569,20 @@ uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_byt
     return fit < Cp ? fit : Cp;
 }
 
-template <int TGT>
+template <int TGT, bool BOX>
 static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_name)
 {
     if (r.max_depth < 1 || r.max_depth > (uint32_t)nuts::MAX_DEPTH || r.C == 0) return (int)hipErrorInvalidValue;      // (the caller routes these elsewhere)
+    if (BOX && (!r.btype || !r.lb || !r.ub || !r.box_blocks)) return (int)hipErrorInvalidValue;
     const uint32_t n_rows = TGT == TGT_LOGISTIC ? r.n_rows : 0u;
-    const NutsWs w = gemm_nuts_carve(r.d, n_rows, r.max_depth, padded_chains(r.C), static_cast<double*>(r.ws));
+    const NutsWs w = gemm_nuts_carve(r.d, n_rows, r.max_depth, padded_chains(r.C), BOX, static_cast<double*>(r.ws));
     const Layout& l = w.l;
     TickParams tp{};
     tp.d = r.d; tp.dK = l.dK; tp.n_rec = gemm_nuts_points(r.max_depth); tp.C = r.C; tp.Cp = l.Cp; tp.Ct = r.C_total; tp.c_off = r.c_off; tp.chain0 = r.chain0; tp.vec = l.vec;
     tp.X = w.fix[0]; tp.pm = w.fix[1]; tp.G = w.fix[2]; tp.prev0 = w.fix[3]; tp.prev1 = w.fix[4]; tp.gprev = w.fix[5]; tp.mntm = w.fix[6];
     tp.tpos_t = w.fix[7]; tp.tpos_p = w.fix[8]; tp.tneg_t = w.fix[9]; tp.tneg_p = w.fix[10];
+    tp.TH = w.th;
+    if (BOX) { tp.lk.bx.bt = r.btype; tp.lk.bx.lb = r.lb; tp.lk.bx.ub = r.ub; tp.lk.bx.blocks = r.box_blocks; }
     tp.rec = w.rec; tp.sc = w.sc; tp.ecol = w.ecol; tp.colmode = w.colmode; tp.pbsel = w.pbsel; tp.didx = w.didx;
     tp.running = reinterpret_cast<uint32_t*>(w.ctr);
     tp.points = reinterpret_cast<unsigned long long*>(w.ctr + 1);
@@ -551,11 +604,12 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
     const dim3 prep_grid((unsigned)(l.Cp / 256 + (l.Cp % 256 ? 1 : 0)), l.dK / 2);
     // the launches of ONE tick: the same every tick (what differs lives in device memory)
     auto enqueue_tick = [&](hipStream_t s) -> int {
-        hipLaunchKernelGGL(nuts_prepare_kernel, prep_grid, dim3(256), 0, s, tp);
+        hipLaunchKernelGGL(nuts_prepare_kernel<BOX>, prep_grid, dim3(256), 0, s, tp);
         StepParams sp{};
         sp.n_ntiles = n_ntiles; sp.Cp = l.Cp; sp.pm = tp.pm; sp.pos = tp.X; sp.g_out = tp.G; sp.ecol = tp.ecol; sp.colmode = tp.colmode;
-        if (int e = gradient_product<TGT>(w, r.y, r.n_rows, tp.X, EP_NUTS, sp, s)) return e;
-        hipLaunchKernelGGL(nuts_point_kernel<TGT>, dim3(cls_grid), dim3(256), 0, s, tp);
+        if (BOX) { sp.pos = tp.TH; sp.xpos = tp.X; sp.bt = r.btype; sp.lb = r.lb; sp.ub = r.ub; sp.box_blocks = r.box_blocks; }
+        if (int e = gradient_product<TGT>(w, r.y, r.n_rows, tp.X, BOX ? EP_NUTS_BOX : EP_NUTS, sp, s)) return e;
+        hipLaunchKernelGGL((nuts_point_kernel<TGT, BOX>), dim3(cls_grid), dim3(256), 0, s, tp);
         return (int)hipGetLastError();
     };
 
@@ -581,7 +635,8 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
     r.ticks_run = ticks; r.points_taken = points; r.still_running = running;
     if (kernel_name) {
         static thread_local char name[112];
-        snprintf(name, sizeof(name), "gemm_step_kernel<%d, %d> (nuts, memoised%s%s)", (int)EP_NUTS, TGT, graphed ? ", graph" : "", r.diag_mass ? ", diagonal precond_mat" : "");
+        snprintf(name, sizeof(name), "gemm_step_kernel<%d, %d> (nuts, memoised%s%s%s)", (int)(BOX ? EP_NUTS_BOX : EP_NUTS), TGT, graphed ? ", graph" : "",
+                 r.diag_mass ? ", diagonal precond_mat" : "", BOX ? ", bounds" : "");
         *kernel_name = name;
     }
     return 0;
@@ -589,5 +644,6 @@ static int gemm_nuts_run_t(GemmNutsRun& r, hipStream_t st, const char** kernel_n
 
 int gemm_nuts_run(GemmNutsRun& r, hipStream_t st, const char** kernel_name)
 {
-    return r.X != nullptr ? gemm_nuts_run_t<TGT_LOGISTIC>(r, st, kernel_name) : gemm_nuts_run_t<TGT_DENSE>(r, st, kernel_name);
+    if (r.bounded) return r.X != nullptr ? gemm_nuts_run_t<TGT_LOGISTIC, true>(r, st, kernel_name) : gemm_nuts_run_t<TGT_DENSE, true>(r, st, kernel_name);
+    return r.X != nullptr ? gemm_nuts_run_t<TGT_LOGISTIC, false>(r, st, kernel_name) : gemm_nuts_run_t<TGT_DENSE, false>(r, st, kernel_name);
 }

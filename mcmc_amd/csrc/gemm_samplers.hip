@@ -84,7 +84,7 @@ enum : int {
     EP_LEAP = 0, EP_LAST = 1, EP_GRAD = 2, EP_ETA = 3,
     EP_PRODUCT = 4, EP_DRIFT = 5, EP_KICKS = 6, EP_MALA_PROPOSE = 7, EP_MALA_REVERSE = 8,
     EP_BOX_LEAP = 10, EP_BOX_LAST = 11,
-    EP_NUTS = 12
+    EP_NUTS = 12, EP_NUTS_BOX = 13
 };
 
 // One product D = A B over K: A^T as [Kp][ldA] (k-major: a row holds the 128 output rows of a tile contiguously), B as [Kp][Cp]
@@ -115,6 +115,7 @@ struct StepParams {
     // nuts (gemm_nuts.hpp).  MODE 12: every chain has its own signed step and takes a point this tick or does not
     const double* ecol;           // [Cp] the step of the column's chain (0: an evaluation without a kick)
     const uint32_t* colmode;      // [Cp] zero: the column's chain takes no point this tick -- its memory stays as it is
+    // MODE 13 (MODE 12 with bounds): pos = theta of the point (the transformed state), Bm = xpos = inv_transform(theta), the tables of MODE 10 / 11
 };
 
 template <int MODE, int TGT>
@@ -263,6 +264,54 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(256, 2) void gemm_step_kernel(const 
                         prm.g_out[idx] = g;
                     }
                 }
+        } else if constexpr (MODE == EP_NUTS_BOX) {  // nuts with bounds: p += (e_c (J(theta) g)) / 2 (nuts.cpp:108-135), the RAW gradient (with respect to x) kept
+            const bool boxed = prm.box_blocks[row0 >> 4] != 0u;            // (the same for the whole wave)
+            [[maybe_unused]] double xs[4][4];
+            double ec[4], pv[4][4], tv[4][4], lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {0.0, 0.0, 0.0, 0.0};
+            int bt[4] = {1, 1, 1, 1};
+            bool on[4];
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                const size_t col = n0 + (size_t)(64 * wn + 16 * ni + c16);
+                ec[ni] = prm.ecol[col];
+                on[ni] = prm.colmode[col] != 0u;
+            }
+            if (boxed) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { const size_t i = row0 + (size_t)(4 * r + j); bt[r] = prm.bt[i]; lo[r] = prm.lb[i]; hi[r] = prm.ub[i]; }
+            }
+            // two batches of 8 elements per block, as EP_BOX_LEAP / EP_BOX_LAST
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int r = 2 * h; r < 2 * h + 2; ++r)
+#pragma unroll
+                    for (int ni = 0; ni < 4; ++ni) {
+                        pv[r][ni] = 0.0; tv[r][ni] = 0.0;
+                        if constexpr (TGT == TGT_LOGISTIC) xs[r][ni] = 0.0;
+                        if (on[ni]) {
+                            pv[r][ni] = prm.pm[at(r, ni)];
+                            if (boxed) tv[r][ni] = prm.pos[at(r, ni)];
+                            if constexpr (TGT == TGT_LOGISTIC) xs[r][ni] = prm.xpos[at(r, ni)];
+                        }
+                    }
+#pragma unroll
+                for (int r = 2 * h; r < 2 * h + 2; ++r)
+#pragma unroll
+                    for (int ni = 0; ni < 4; ++ni) {
+                        const size_t idx = at(r, ni);
+                        const double v = acc[ti][ni][r];
+                        double g;
+                        if constexpr (TGT == TGT_DENSE) g = -v;            // grad log K at x: -(P x)
+                        else g = v - xs[r][ni];                            // X^T (y - sigmoid(eta)) - x
+                        double jg = g;                                     // an unbounded block: J = I
+                        if (boxed) jg = dfma(box_inv_jacobian(tv[r][ni], bt[r], lo[r], hi[r]), g, 0.0);     // nuts.cpp:121-131
+                        if (on[ni]) {
+                            prm.pm[idx] = pv[r][ni] + (ec[ni] * jg) / 2.0;    // the second half-step of the chain's leapfrog
+                            prm.g_out[idx] = g;
+                        }
+                    }
+            }
         } else if constexpr (MODE == EP_BOX_LEAP || MODE == EP_BOX_LAST) {      // a leapfrog step in the transformed space (hmc.cpp:107-122,171)
             const bool boxed = prm.box_blocks[row0 >> 4] != 0u;            // (the same for the whole wave)
             [[maybe_unused]] double pv[4][4], tv[4][4], xs[4][4], mi[4], lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {0.0, 0.0, 0.0, 0.0};
@@ -833,7 +882,7 @@ static int launch_step(const StepParams& sp, hipStream_t st)
 // The instantiations of gemm_step_kernel, listed ONCE, for a run on target TGT: X(mode, target).  (The products with a mass matrix have no target: they exist once;
 // eta exists for the logistic target alone)
 #define GEMM_STEP_MODES(X, TGT) \
-    X(EP_LEAP, TGT) X(EP_LAST, TGT) X(EP_GRAD, TGT) X(EP_KICKS, TGT) X(EP_BOX_LEAP, TGT) X(EP_BOX_LAST, TGT) X(EP_NUTS, TGT) X(EP_ETA, TGT_LOGISTIC) \
+    X(EP_LEAP, TGT) X(EP_LAST, TGT) X(EP_GRAD, TGT) X(EP_KICKS, TGT) X(EP_BOX_LEAP, TGT) X(EP_BOX_LAST, TGT) X(EP_NUTS, TGT) X(EP_NUTS_BOX, TGT) X(EP_ETA, TGT_LOGISTIC) \
     X(EP_PRODUCT, TGT_DENSE) X(EP_DRIFT, TGT_DENSE) X(EP_MALA_PROPOSE, TGT_DENSE) X(EP_MALA_REVERSE, TGT_DENSE)
 template <int TGT>
 static int step_attrs()      // once per process and target: 73 728 bytes of dynamic LDS are above the 64 KiB default

@@ -50,7 +50,7 @@ size_t gemm_ws_bytes(uint32_t d, uint32_t n_rows, uint64_t C, bool dense_mass = 
 // enqueues the whole run on `st`; returns a hipError_t as int (0 = enqueued).  *kernel_name: what ran, for mi_mcmc_last_kernel()
 int gemm_run(const GemmRun& r, hipStream_t st, const char** kernel_name);
 
-// ---- mcmc::nuts on this route (gemm_nuts.hpp): identity or a DIAGONAL precond_mat, no bounds, 1 <= max_tree_depth <= 10.  One RANGE of the call's chains per run:
+// ---- mcmc::nuts on this route (gemm_nuts.hpp): identity or a DIAGONAL precond_mat, with or without settings.vals_bound (the caller sends bounded calls of fewer than 16 chains elsewhere), 1 <= max_tree_depth <= 10.  One RANGE of the call's chains per run:
 // the caller's arrays are indexed by column c_off + c with the call's chain count C_total as their stride, the random numbers by chain0 + c_off + c.
 struct GemmNutsRun {
     uint32_t d = 0;
@@ -73,7 +73,11 @@ struct GemmNutsRun {
     double eps_bar0 = 0.0, delta = 0.0, gamma = 0.0, t0 = 0.0, kappa = 0.0;
     const double* mass_tables = nullptr;   // as GemmRun
     bool diag_mass = false;
-    void* ws = nullptr;               // gemm_nuts_fixed_bytes + round_up(C, 128) * gemm_nuts_chain_bytes bytes
+    bool bounded = false;             // settings.vals_bound: as GemmRun (the chains live in the transformed space, the products are taken at x = inv_transform(theta))
+    const int* btype = nullptr;
+    const double *lb = nullptr, *ub = nullptr;
+    const uint32_t* box_blocks = nullptr;
+    void* ws = nullptr;               // gemm_nuts_fixed_bytes + round_up(C, 128) * gemm_nuts_chain_bytes(.., bounded) bytes
     bool pack = true;                 // pack the matrices into ws (false: a later range of the same call finds them there)
     bool use_graph = true;
     // out
@@ -81,7 +85,7 @@ struct GemmNutsRun {
 };
 uint32_t gemm_nuts_points(uint32_t max_depth);
 uint64_t gemm_nuts_tick_ceiling(uint32_t max_depth, uint64_t n_total, bool search);
-size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth);
+size_t gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_depth, bool bounded = false);      // bounded: one more vector of gemm_padded_d(d) doubles
 size_t gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows);
 uint64_t gemm_nuts_range_chains(uint64_t C, size_t chain_bytes, size_t fixed_bytes, size_t budget);
 // runs the range to its end (the host polls the device's counter of running chains: nothing waits on the device); returns a hipError_t as int

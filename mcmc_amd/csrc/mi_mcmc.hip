@@ -162,6 +162,7 @@ extern "C" void mi_mcmc_test_gemm_nuts_last_ticks(uint64_t* ticks, uint64_t* bus
 }
 extern "C" uint64_t mi_mcmc_test_gemm_nuts_tick_ceiling(uint32_t max_tree_depth, uint64_t n_draws, int search) { return mi::gemm::gemm_nuts_tick_ceiling(max_tree_depth, n_draws, search != 0); }
 extern "C" uint64_t mi_mcmc_test_gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth) { return mi::gemm::gemm_nuts_chain_bytes(d, n_rows, max_tree_depth); }
+extern "C" uint64_t mi_mcmc_test_gemm_nuts_bounded_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth) { return mi::gemm::gemm_nuts_chain_bytes(d, n_rows, max_tree_depth, true); }
 extern "C" uint64_t mi_mcmc_test_gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows) { return mi::gemm::gemm_nuts_fixed_bytes(d, n_rows); }
 extern "C" uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint64_t chain_bytes, uint64_t fixed_bytes, uint64_t budget)
 {
@@ -1052,6 +1053,29 @@ void gemm_mass_tables(const mi::lit::LitPrep& prep, uint64_t d, uint32_t dK, int
     mi::settings::pad_table(prep.m_sqrt.data(), d, dK, 1.0, &tabs[dK]);
     mi::settings::pad_table(prep.m_inv.data(), d, dK, 1.0, &tabs[2 * (size_t)dK]);
 }
+// vals_bound on the matrix-product route (run_gemm, run_gemm_nuts): bounds type, lower and upper bound per dimension (determine_bounds_type.hpp:27-57, from lit_prepare)
+// padded with type 1, and per 16-dimension block whether it holds a bounded dimension at all -- the others skip every exp / log
+struct GemmBoxTables {
+    DevBuf dev;
+    const int* btype = nullptr;
+    const double *lb = nullptr, *ub = nullptr;
+    const uint32_t* blocks = nullptr;
+};
+int gemm_box_tables(const mi::lit::LitPrep& prep, uint64_t d, uint32_t dK, GemmBoxTables& t)
+{
+    const size_t off_lb = (size_t)dK * sizeof(int), off_ub = off_lb + (size_t)dK * 8, off_blk = off_ub + (size_t)dK * 8, bytes = off_blk + (size_t)(dK / 16) * sizeof(uint32_t);
+    std::vector<unsigned char> host(bytes, 0);
+    mi::settings::pad_table(prep.bt.data(), d, dK, 1, reinterpret_cast<int*>(host.data()));
+    mi::settings::pad_table(prep.lb.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_lb));
+    mi::settings::pad_table(prep.ub.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_ub));
+    uint32_t* blk = reinterpret_cast<uint32_t*>(host.data() + off_blk);
+    for (uint64_t i = 0; i < d; ++i) if (prep.bt[i] != 1) blk[i / 16] = 1u;
+    if (int rc = upload_padded(t.dev, host.data(), bytes, bytes, (unsigned char)0)) return rc;
+    unsigned char* base = static_cast<unsigned char*>(t.dev.p);
+    t.btype = reinterpret_cast<const int*>(base); t.lb = reinterpret_cast<const double*>(base + off_lb);
+    t.ub = reinterpret_cast<const double*>(base + off_ub); t.blocks = reinterpret_cast<const uint32_t*>(base + off_blk);
+    return 0;
+}
 int run_gemm(const char* who, int algo, const mi_target* target, const mi_settings* settings, mi_chains* chains, hipStream_t st)
 {
     int rc;
@@ -1079,21 +1103,10 @@ int run_gemm(const char* who, int algo, const mi_target* target, const mi_settin
     rc = mi::lit::lit_prepare(algo == 1 ? 1 : 0, (uint32_t)d, settings->step_size, bounded ? 1 : 0, settings->lower_bounds, settings->upper_bounds, settings->precond_mat, prep);
     if (rc) return rc;
     const uint32_t dK = mi::gemm::gemm_padded_d((uint32_t)d);
-    // vals_bound: bounds type, lower and upper bound per dimension (determine_bounds_type.hpp:27-57, from lit_prepare) padded with type 1, and per 16-dimension block
-    // whether it holds a bounded dimension at all -- the others skip every exp / log
-    DevBuf box_dev;
+    GemmBoxTables box;
     if (bounded) {
-        const size_t off_lb = (size_t)dK * sizeof(int), off_ub = off_lb + (size_t)dK * 8, off_blk = off_ub + (size_t)dK * 8, bytes = off_blk + (size_t)(dK / 16) * sizeof(uint32_t);
-        std::vector<unsigned char> host(bytes, 0);
-        mi::settings::pad_table(prep.bt.data(), d, dK, 1, reinterpret_cast<int*>(host.data()));
-        mi::settings::pad_table(prep.lb.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_lb));
-        mi::settings::pad_table(prep.ub.data(), d, dK, 0.0, reinterpret_cast<double*>(host.data() + off_ub));
-        uint32_t* blk = reinterpret_cast<uint32_t*>(host.data() + off_blk);
-        for (uint64_t i = 0; i < d; ++i) if (prep.bt[i] != 1) blk[i / 16] = 1u;
-        if ((rc = upload_padded(box_dev, host.data(), bytes, bytes, (unsigned char)0))) return rc;
-        unsigned char* base = static_cast<unsigned char*>(box_dev.p);
-        g.bounded = true; g.btype = reinterpret_cast<const int*>(base); g.lb = reinterpret_cast<const double*>(base + off_lb);
-        g.ub = reinterpret_cast<const double*>(base + off_ub); g.box_blocks = reinterpret_cast<const uint32_t*>(base + off_blk);
+        if ((rc = gemm_box_tables(prep, d, dK, box))) return rc;
+        g.bounded = true; g.btype = box.btype; g.lb = box.lb; g.ub = box.ub; g.box_blocks = box.blocks;
     }
     std::vector<double> tabs;
     gemm_mass_tables(prep, d, dK, 4, tabs);
@@ -2316,21 +2329,26 @@ bool lds_nuts_case(const mi_target* target, const mi_settings* settings)
 // 65 536 chains, 135 / 156 at 8 192; d = 64: 209 / 208; d = 32: 71 / 72) and within 13 % at d = 16 (37 / 33 ms) -- one tick to maintain instead of
 // four.  Their hints stay valid and are ignored.  MI_KERNEL_NUTS_TICK_LOCAL keeps the independent tick-local kernel for A/B runs.
 
-// nuts on the matrix-product route (gemm_nuts.hpp): the dense Gaussian and the logistic target BEYOND d = 512, identity or a DIAGONAL precond_mat, no bounds,
-// 1 <= max_tree_depth <= 10 -- per-chain memoised trees, one product per tick for all chains.  Capacity is a routing condition, then chunking: a chain holds
-// gemm_nuts_chain_bytes of workspace (0.85 MB at d = 1024, max_tree_depth 10), so a call whose chains do not fit the free device memory (plus this stream's cached
+// nuts on the matrix-product route (gemm_nuts.hpp): the dense Gaussian and the logistic target BEYOND d = 512, identity or a DIAGONAL precond_mat, with or without
+// vals_bound, 1 <= max_tree_depth <= 10 -- per-chain memoised trees, one product per tick for all chains.  Capacity is a routing condition, then chunking: a chain holds
+// gemm_nuts_chain_bytes of workspace (0.85 MB at d = 1024, max_tree_depth 10; with bounds one vector of padded d more), so a call whose chains do not fit the free device memory (plus this stream's cached
 // workspace) together runs them as consecutive RANGES, in multiples of 128, through the same code -- chains are independent and their random numbers are
 // counter-based on the global chain index, so the bits do not change -- and a call for which not even one range of 128 fits stays on the literal kernel.
 struct GemmNutsPlan { uint64_t range = 0; size_t own_bytes = 0; };
+constexpr uint64_t GEMM_NUTS_BOUNDED_MIN_CHAINS = 16;
 bool gemm_nuts_case(const mi_target* target, const mi_settings* settings, const mi_chains* chains, hipStream_t st, GemmNutsPlan& plan)
 {
     if (!((target->kind == MI_TARGET_GAUSS_DENSE || target->kind == MI_TARGET_LOGISTIC) && target->d > 512 && target->kernel_hint != MI_KERNEL_LITERAL)) return false;
-    if (settings->vals_bound || chains->mass_diag || settings->max_tree_depth < 1 || settings->max_tree_depth > 10) return false;
+    if (chains->mass_diag || settings->max_tree_depth < 1 || settings->max_tree_depth > 10) return false;
     if (settings->precond_mat && !precond_is_diagonal(settings, target->d)) return false;
     const uint64_t d = target->d, C = chains->n_chains, n = target->kind == MI_TARGET_LOGISTIC ? target->n_rows : 0;
     if (d > 131056ULL || n > 0x7fffffffULL) return false;                                   // (grid.y of the element-wise kernel: padded d / 2)
     const uint32_t D = (uint32_t)settings->max_tree_depth;
-    const size_t chain_b = mi::gemm::gemm_nuts_chain_bytes((uint32_t)d, (uint32_t)n, D), fixed_b = mi::gemm::gemm_nuts_fixed_bytes((uint32_t)d, (uint32_t)n);
+    const bool bounded = settings->vals_bound != 0;      // (missing bound arrays: run_gemm_nuts reports them.  The replay's work areas do not grow with bounds: `rest` below)
+    // A bounded call of fewer than 16 chains -- less than one wave of the per-chain kernel (16 chains x 4 lanes) -- stays on the literal kernel, as before: the routing
+    // tests of the suite hold such calls there (6 chains), and the route was measured from 128 chains up only.  Not a measured crossover
+    if (bounded && C < GEMM_NUTS_BOUNDED_MIN_CHAINS) return false;
+    const size_t chain_b = mi::gemm::gemm_nuts_chain_bytes((uint32_t)d, (uint32_t)n, D, bounded), fixed_b = mi::gemm::gemm_nuts_fixed_bytes((uint32_t)d, (uint32_t)n);
     size_t budget = (size_t)g_gemm_nuts_ws_bytes.load(std::memory_order_relaxed);           // (the test hook: the route's own workspace, as if this were all there is)
     if (budget == 0) {
         // next to the route's own: the flags and the literal replay's matrix and work areas, a host target's matrix and the tables
@@ -2365,6 +2383,8 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     const uint64_t n = logit ? target->n_rows : 0;
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;
     if (n_total > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "too many draws");
+    const bool bounded = settings->vals_bound != 0;
+    if (bounded && (!settings->lower_bounds || !settings->upper_bounds)) return fail(MI_ERR_BAD_ARG, "nuts: vals_bound needs lower_bounds and upper_bounds");
     StagedTarget tg;
     if ((rc = stage_target(target, tg, st))) return rc;
     StagedChains sc;
@@ -2381,9 +2401,15 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
     g.eps_bar0 = settings->step_size;
     // identity or a DIAGONAL precond_mat: diag(M), CHOL_LOWER (sqrt), INV (reciprocal) from lit_prepare, in the oracle's operation order; the identity as tables of ones
     mi::lit::LitPrep prep;
-    rc = mi::lit::lit_prepare(0, (uint32_t)d, settings->step_size, 0, nullptr, nullptr, settings->precond_mat, prep);
+    // (and, vals_bound, the bounds tables of the same derivation: what bounded hmc on this route reads)
+    rc = mi::lit::lit_prepare(0, (uint32_t)d, settings->step_size, bounded ? 1 : 0, settings->lower_bounds, settings->upper_bounds, settings->precond_mat, prep);
     if (rc) return rc;
     const uint32_t dK = mi::gemm::gemm_padded_d((uint32_t)d);
+    GemmBoxTables box;
+    if (bounded) {
+        if ((rc = gemm_box_tables(prep, d, dK, box))) return rc;
+        g.bounded = true; g.btype = box.btype; g.lb = box.lb; g.ub = box.ub; g.box_blocks = box.blocks;
+    }
     std::vector<double> tabs;
     gemm_mass_tables(prep, d, dK, 3, tabs);
     DevBuf tabs_dev;
@@ -2426,6 +2452,7 @@ int run_gemm_nuts(const mi_target* target, const mi_settings* settings, mi_chain
         lit_common(lp, settings, &sc.dev, rp, false);
         if ((rc = fill_nuts(lp, settings, chains, sc))) return rc;
         if (prep.precond == 1) { lp.precond = 1; lp.m = g.mass_tables; lp.m_sqrt = g.mass_tables + dK; lp.m_inv = g.mass_tables + 2 * (size_t)dK; }
+        if (bounded) { lp.vals_bound = 1; lp.btype = g.btype; lp.lb = g.lb; lp.ub = g.ub; }      // (the replay starts from theta, the untouched initial values: it transforms them itself)
         rc = launched("matrix-product nuts (literal replay)", mi::launch_literal(2, lp, rp.n_wg, st));
         if (rc) return rc;
         if (g.n_exec && (rc = copy_flagged_counts(rp.flag, g.n_leap, g.n_exec, C, st))) return rc;      // a replayed chain executed every leapfrog it counts
@@ -2604,7 +2631,7 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
         if (d <= (uint64_t)mi::SMALL_MAX_D && settings->max_tree_depth <= 10) return run_small_logistic("nuts", 2, target, settings, chains, st);
         if (d <= 512 && lds_nuts_case(target, settings)) return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_LOGISTIC);
         GemmNutsPlan plan;
-        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, two matrix products per tick
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain or bounded: memoised trees, two matrix products per tick
         return run_literal("nuts", 2, target, settings, chains, st);
     }
     if (target->kind != MI_TARGET_GAUSS_ISO && target->kind != MI_TARGET_GAUSS_DIAG && target->kind != MI_TARGET_GAUSS_DENSE)
@@ -2614,7 +2641,7 @@ int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_ch
         return run_lds_nuts(target, settings, chains, st, mi::LOGIT_TARGET_DENSE);     // P streamed through LDS (nuts_lds.hpp)
     {
         GemmNutsPlan plan;
-        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain: memoised trees, one matrix product per tick (gemm_nuts.hpp)
+        if (gemm_nuts_case(target, settings, chains, st, plan)) return run_gemm_nuts(target, settings, chains, st, plan);      // d > 512, plain or bounded: memoised trees, one matrix product per tick (gemm_nuts.hpp)
     }
     if (d > 128 || settings->max_tree_depth > (uint64_t)mi::NUTS_MAX_DEPTH) return run_literal("nuts", 2, target, settings, chains, st);
     const uint64_t n_total = settings->n_burnin_draws + settings->n_keep_draws;

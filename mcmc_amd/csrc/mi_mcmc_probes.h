@@ -45,6 +45,8 @@ void mi_mcmc_test_gemm_nuts_last_ticks(uint64_t* ticks, uint64_t* busy_slots, ui
 uint64_t mi_mcmc_test_gemm_nuts_tick_ceiling(uint32_t max_tree_depth, uint64_t n_draws, int search);
 uint64_t mi_mcmc_test_gemm_nuts_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth);
 uint64_t mi_mcmc_test_gemm_nuts_fixed_bytes(uint32_t d, uint32_t n_rows);
+/* ... the bytes per chain of a call with settings.vals_bound: one vector of padded d doubles more (theta of the last point next to x) */
+uint64_t mi_mcmc_test_gemm_nuts_bounded_chain_bytes(uint32_t d, uint32_t n_rows, uint32_t max_tree_depth);
 uint64_t mi_mcmc_test_gemm_nuts_range_chains(uint64_t n_chains, uint64_t chain_bytes, uint64_t fixed_bytes, uint64_t budget);
 /* Defined in libmi_mcmc.so itself (test hooks like the ones above), for hmc / mala / rwmh and nuts beyond d = 512 on the matrix-product route:
  * mode 1 never captures the launches of a draw / a tick into a graph -- every draw enqueues them itself, what a call of 65 536 chains does (its launches are long,
