@@ -243,7 +243,9 @@ int mi_mcmc_release_workspace(void* stream, int all_streams, uint64_t* bytes_fre
  * Also blocking with MI_MEM_DEVICE: every configuration that owns temporary device tables for the call -- settings.vals_bound or
  * settings.precond_mat (bounds / preconditioner tables), a target given in host memory, and the runs that go to the literal kernels
  * with such tables -- ends in a stream synchronisation before those tables are freed.  The plain configurations (no bounds, no
- * precond_mat, target in device memory: every BASELINE config) do return after enqueueing. */
+ * precond_mat, target in device memory: every BASELINE config) do return after enqueueing.
+ * With MI_MEM_DEVICE every device input (chains, target, mass_diag, the nuts continuation state) is read in the order of `stream` and every
+ * output is written in the order of `stream`: work the caller queued on it before the call is seen, work queued after it sees the results. */
 int mi_mcmc_hmc_run (const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream);
 int mi_mcmc_mala_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream);
 int mi_mcmc_nuts_run(const mi_target* target, const mi_settings* settings, mi_chains* chains, void* stream);

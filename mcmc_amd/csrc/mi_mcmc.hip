@@ -352,8 +352,10 @@ int dense_precision_on_device(const mi_target* t, DevBuf& owned, const double** 
     std::vector<double> diag(d, 1.0);
     if (t->kind == MI_TARGET_GAUSS_DIAG) {
         if (!t->prec) return fail(MI_ERR_BAD_ARG, "GAUSS_DIAG needs prec (d)");
-        if (t->mem == MI_MEM_DEVICE)
-            HIP_TRY(hipMemcpy(diag.data(), t->prec, d * sizeof(double), hipMemcpyDeviceToHost));
+        if (t->mem == MI_MEM_DEVICE) {                   // in the order of the caller's stream: a non-blocking stream that produced prec does not order itself before a NULL-stream copy
+            HIP_TRY(hipMemcpyAsync(diag.data(), t->prec, d * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
         else
             std::memcpy(diag.data(), t->prec, d * sizeof(double));
     } else if (t->kind != MI_TARGET_GAUSS_ISO) {

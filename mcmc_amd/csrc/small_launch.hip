@@ -20,6 +20,7 @@ int launch_small_normal_model(int algo, const SmallParams& prm, hipStream_t st)
     case 4: hipLaunchKernelGGL(rmhmc_small_kernel<NormalModel>, grid, dim3(block), 0, st, prm, tgt); break;
     default: return (int)hipErrorInvalidValue;
     }
+    note_kernel("%s_small_kernel<NormalModel>", small_algo_name(algo));
     return (int)hipGetLastError();
 }
 

@@ -7,6 +7,13 @@
 
 namespace mi {
 
+// the one-lane kernels by name, for note_kernel: algo 0 hmc, 1 mala, 2 nuts, 3 rwmh, 4 rmhmc
+inline const char* small_algo_name(int algo)
+{
+    static const char* const names[5] = {"hmc", "mala", "nuts", "rwmh", "rmhmc"};
+    return (algo >= 0 && algo < 5) ? names[algo] : "?";
+}
+
 template <int D>
 int launch_small_logistic_d(int algo, const SmallParams& prm, const double* X_dev, const double* y_dev, uint32_t n_rows, hipStream_t st)
 {
@@ -24,6 +31,7 @@ int launch_small_logistic_d(int algo, const SmallParams& prm, const double* X_de
         else return (int)hipErrorInvalidValue;
     default: return (int)hipErrorInvalidValue;
     }
+    note_kernel("%s_small_kernel<LogisticSmallModel<%d>>", small_algo_name(algo), D);
     return (int)hipGetLastError();
 }
 
