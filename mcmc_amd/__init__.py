@@ -13,66 +13,19 @@ import os
 
 import numpy as np
 
+from . import _abi
+from ._abi import (EXPORTS, PROBE_EXPORTS,               # noqa: F401 -- the boundary as _abi states it, under the names this package has always had
+                   MI_OK, MI_ERR_BAD_ARG, MI_ERR_HIP, MI_ERR_UNSUPPORTED, MI_ERR_OOM, MI_ERR_NO_DEVICE,
+                   TARGET_GAUSS_ISO, TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_NORMAL_MODEL, TARGET_GAUSS_MIXTURE,
+                   MEM_HOST, MEM_DEVICE, KERNEL_AUTO, KERNEL_ELEMENTWISE_1LANE, KERNEL_ELEMENTWISE_4LANE, KERNEL_NUTS_LOCKSTEP,
+                   KERNEL_HMC_TWO_WAVES_PER_SIMD, KERNEL_HMC_ONE_WAVE_PER_SIMD, KERNEL_HMC_SPLIT2, KERNEL_HMC_SPLIT4, KERNEL_HMC_SPLIT4_TWO_WAVES,
+                   KERNEL_NUTS_TICK_LOCAL, KERNEL_NUTS_REG, KERNEL_NUTS_SPLIT, KERNEL_LITERAL, KERNEL_NUTS_DYN, KERNEL_NUTS_MEMO, KERNEL_NUTS_MEMO_INTICK,
+                   STATS_ALL_LAGS, RANK_AVERAGE, RANK_NORMAL, RANK_SPLIT, RANK_FOLD, LOGLIK_ROWS, LOGLIK_SLAB, GEMM_PLAIN, GEMM_DENSE_M, GEMM_BOUNDED,
+                   mi_target, mi_settings, mi_chains, mi_de_settings, mi_populations, mi_aees_settings, mi_aees_runs)
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_mcmc.so")
-
-MI_OK, MI_ERR_BAD_ARG, MI_ERR_HIP, MI_ERR_UNSUPPORTED, MI_ERR_OOM, MI_ERR_NO_DEVICE = range(6)
-TARGET_GAUSS_ISO, TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_NORMAL_MODEL = 1, 2, 3, 4, 5
-TARGET_GAUSS_MIXTURE = 6                  # value only: mcmc::aees alone (mixture_target builds one)
-MEM_HOST, MEM_DEVICE = 0, 1
-KERNEL_AUTO, KERNEL_ELEMENTWISE_1LANE, KERNEL_ELEMENTWISE_4LANE, KERNEL_NUTS_LOCKSTEP = 0, 1, 2, 3   # mi_kernel_hint
-KERNEL_HMC_TWO_WAVES_PER_SIMD, KERNEL_HMC_ONE_WAVE_PER_SIMD, KERNEL_HMC_SPLIT2, KERNEL_HMC_SPLIT4, KERNEL_HMC_SPLIT4_TWO_WAVES = 4, 5, 6, 7, 8
-KERNEL_NUTS_TICK_LOCAL, KERNEL_NUTS_REG, KERNEL_NUTS_SPLIT, KERNEL_LITERAL, KERNEL_NUTS_DYN, KERNEL_NUTS_MEMO, KERNEL_NUTS_MEMO_INTICK = 9, 10, 11, 12, 13, 14, 15
-
-_dp = C.POINTER(C.c_double)
-_u64p = C.POINTER(C.c_uint64)
-
-
-class mi_target(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("d", C.c_uint64),
-                ("prec", C.c_void_p), ("X", C.c_void_p), ("y", C.c_void_p),
-                ("n_rows", C.c_uint64), ("mem", C.c_int32), ("kernel_hint", C.c_int32)]
-
-
-class mi_settings(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("vals_bound", C.c_int32),
-                ("rng_seed_value", C.c_uint64), ("lower_bounds", C.c_void_p),
-                ("upper_bounds", C.c_void_p), ("n_burnin_draws", C.c_uint64),
-                ("n_keep_draws", C.c_uint64), ("n_leap_steps", C.c_uint64),
-                ("step_size", C.c_double), ("precond_mat", C.c_void_p),
-                ("n_adapt_draws", C.c_uint64), ("target_accept_rate", C.c_double),
-                ("max_tree_depth", C.c_uint64), ("gamma_val", C.c_double),
-                ("t0_val", C.c_double), ("kappa_val", C.c_double), ("n_fp_steps", C.c_uint64)]
-
-
-class mi_chains(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("mem", C.c_int32), ("n_chains", C.c_uint64),
-                ("chain0", C.c_uint64), ("theta", C.c_void_p), ("draws", C.c_void_p),
-                ("n_accept", C.c_void_p), ("step_size", C.c_void_p), ("n_leapfrogs", C.c_void_p),
-                ("nuts_depth", C.c_void_p), ("draw0", C.c_uint64), ("nuts_adapt_state", C.c_void_p), ("mass_diag", C.c_void_p),
-                ("n_leapfrogs_executed", C.c_void_p)]
-
-
-class mi_de_settings(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("jumps", C.c_int32), ("n_pop", C.c_uint64), ("par_b", C.c_double),
-                ("par_gamma_jump", C.c_double), ("par_gamma", C.c_double), ("initial_lb", C.c_void_p), ("initial_ub", C.c_void_p)]
-
-
-class mi_populations(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("mem", C.c_int32), ("n_populations", C.c_uint64), ("population0", C.c_uint64),
-                ("initial_vals", C.c_void_p), ("population", C.c_void_p), ("draws", C.c_void_p), ("n_accept", C.c_void_p),
-                ("draw0", C.c_uint64)]
-
-
-class mi_aees_settings(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("n_rings", C.c_uint32), ("n_initial_draws", C.c_uint64), ("par_scale", C.c_double),
-                ("cov_mat", C.c_void_p), ("ee_prob_par", C.c_double), ("temper_vec", C.c_void_p), ("temper_len", C.c_uint64)]
-
-
-class mi_aees_runs(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("mem", C.c_int32), ("n_runs", C.c_uint64), ("run0", C.c_uint64),
-                ("initial_vals", C.c_void_p), ("draws", C.c_void_p), ("final_states", C.c_void_p), ("n_accept", C.c_void_p),
-                ("n_ee_accept", C.c_void_p)]
 
 
 class MiMcmcError(RuntimeError):
@@ -82,26 +35,6 @@ class MiMcmcError(RuntimeError):
 
 
 _lib = None
-
-EXPORTS = [
-    "mi_settings_default", "mi_mcmc_last_error", "mi_mcmc_last_kernel", "mi_mcmc_version", "mi_mcmc_device_count", "mi_mcmc_release_workspace", "mi_mcmc_run_user_target", "mi_mcmc_run_user_target_v", "mi_mcmc_run_tile_target",
-    "mi_mcmc_hmc_run", "mi_mcmc_mala_run", "mi_mcmc_nuts_run", "mi_mcmc_rwmh_run", "mi_mcmc_rmhmc_run", "mi_mcmc_hmc_run_mass_adapted", "mi_mcmc_hmc_run_mass_adapted_per_chain", "mi_mcmc_hmc_run_callback", "mi_mcmc_mala_run_callback", "mi_mcmc_nuts_run_callback", "mi_mcmc_rwmh_run_callback", "mi_mcmc_rmhmc_run_callback",
-    "mi_de_settings_default", "mi_mcmc_de_run", "mi_mcmc_de_run_callback",
-    "mi_aees_settings_default", "mi_mcmc_aees_run", "mi_mcmc_aees_run_callback",
-    "mi_mcmc_draws_to_chain_major", "mi_mcmc_draws_to_chain_major_device", "mi_mcmc_shard_bounds", "mi_mcmc_allgather_draws", "mi_mcmc_allgather_draws_ragged", "mi_mcmc_merge_shards", "mi_mcmc_draw_stats",
-    "mi_mcmc_allgather_draws_rank_major", "mi_mcmc_rank_major_index", "mi_mcmc_allgather_draws_begin", "mi_mcmc_allgather_draws_wait",
-    "mi_mcmc_mat_inverse", "mi_mcmc_mat_cholesky_lower",
-    "mi_mcmc_draws_covariance", "mi_mcmc_hmc_run_mass_adapted_dense", "mi_mcmc_mala_run_mass_adapted_dense",
-    "mi_mcmc_draws_order_stats", "mi_mcmc_draws_quantiles",
-    "mi_mcmc_draws_rank_transform", "mi_mcmc_draw_stats_ranked", "mi_mcmc_norm_ppf",
-    "mi_mcmc_draws_log_kernel", "mi_mcmc_draws_waic", "mi_mcmc_draws_psis_loo",
-    "mi_mcmc_loglik_waic", "mi_mcmc_loglik_psis_loo",
-    "mi_mcmc_bridge_proposal", "mi_mcmc_bridge_estimate", "mi_mcmc_draws_bridge",
-    "mi_mcmc_draws_predict",
-    "mi_mcmc_draw_stats_lags", "mi_mcmc_draw_stats_ranked_lags",
-]
-# test / measurement infrastructure: libmi_mcmc_probes.so (mcmc_amd/csrc/mi_mcmc_probes.h), not part of the shipped library
-PROBE_EXPORTS = ["mi_probe_mfma_f64", "mi_probe_math", "mi_probe_normals", "mi_probe_uniform", "mi_probe_fp64_peak", "mi_probe_mfma_cycles"]
 
 
 def _one_hip_runtime():
@@ -137,9 +70,7 @@ def lib():
         if not os.path.exists(path):
             raise MiMcmcError(-1, f"{path} not built: run `make -C mcmc_amd/csrc` (no CPU fallback)")
         _one_hip_runtime()
-        _lib = C.CDLL(path)
-        _lib.mi_mcmc_last_error.restype = C.c_char_p
-        _lib.mi_mcmc_last_kernel.restype = C.c_char_p
+        _lib = _abi.declare(C.CDLL(path), _abi.EXPORTS + _abi.TEST_HOOKS, path)
     return _lib
 
 
@@ -154,7 +85,7 @@ def probes_lib():
         path = os.path.join(os.path.dirname(LIB_PATH), "libmi_mcmc_probes.so")
         if not os.path.exists(path):
             raise MiMcmcError(-1, f"{path} not built: run `make -C mcmc_amd/csrc`")
-        _plib = C.CDLL(path)
+        _plib = _abi.declare(C.CDLL(path), _abi.PROBE_EXPORTS, path)
     return _plib
 
 
@@ -164,14 +95,16 @@ def _check(rc):
 
 
 def _ptr(a):
-    """Address of a numpy array (host), a torch tensor (host or device), an int, or None."""
-    if a is None:
-        return None
-    if isinstance(a, int):
+    """Address of a numpy array (host), a torch tensor (host or device), an integer, or None: a Python int, what a pointer parameter takes."""
+    if a is None or isinstance(a, int):
         return a
+    if isinstance(a, np.integer):
+        return int(a)
     if hasattr(a, "data_ptr"):
         return a.data_ptr()
-    return a.ctypes.data
+    if isinstance(a, np.ndarray):
+        return a.ctypes.data
+    raise TypeError(f"no address for a {type(a).__name__}: None, an integer, a numpy array or an object with data_ptr()")
 
 
 def default_settings(**kw):
@@ -228,15 +161,14 @@ def hmc_mass_adapted(target, settings, chains, n_windows=3, stream=None):
     """mi_mcmc_hmc_run_mass_adapted (NOT a reference mode): hmc with a diagonal mass matrix pooled over the chains and
     re-estimated after each of n_windows parts of the burn-in.  Returns the final mass diagonal [d]."""
     mass = np.zeros(int(target.d))
-    _check(lib().mi_mcmc_hmc_run_mass_adapted(C.byref(target), C.byref(settings), C.byref(chains), C.c_uint32(n_windows),
-                                              C.c_void_p(mass.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_hmc_run_mass_adapted(C.byref(target), C.byref(settings), C.byref(chains), n_windows, mass.ctypes.data, stream or 0))
     return mass
 
 
 def _mass_adapted_dense(fn, target, settings, chains, n_windows, stream):
     d = int(target.d)
     M = np.zeros((d, d))
-    _check(fn(C.byref(target), C.byref(settings), C.byref(chains), C.c_uint32(n_windows), C.c_void_p(M.ctypes.data), C.c_void_p(stream or 0)))
+    _check(fn(C.byref(target), C.byref(settings), C.byref(chains), n_windows, M.ctypes.data, stream or 0))
     return M
 
 
@@ -255,8 +187,8 @@ def hmc_mass_adapted_per_chain(target, settings, chains, n_windows=3, mass_out=N
     """mi_mcmc_hmc_run_mass_adapted_per_chain (NOT a reference mode): every chain adapts its own diagonal mass from its own burn-in
     draws.  mass_out: [d][C] in the memory space of `chains` (numpy array or torch tensor) or None; first_step_size: the step of
     part 0 (M = I on the raw target; 0 = settings.step_size, which is in the preconditioned metric)."""
-    _check(lib().mi_mcmc_hmc_run_mass_adapted_per_chain(C.byref(target), C.byref(settings), C.byref(chains), C.c_uint32(n_windows),
-                                                        C.c_double(first_step_size), C.c_void_p(_ptr(mass_out)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_hmc_run_mass_adapted_per_chain(C.byref(target), C.byref(settings), C.byref(chains), n_windows,
+                                                        first_step_size, _ptr(mass_out), stream or 0))
     return mass_out
 
 
@@ -268,56 +200,43 @@ def rmhmc_callback(initial_vals, kernel_fn, kernel_data, tensor_fn, tensor_data,
     d, n_keep = int(x0.shape[0]), int(settings.n_keep_draws)
     out = np.zeros((d, n_keep))                           # column-major n_keep x d
     nacc = C.c_uint64(0)
-    def addr(f):
-        return f if isinstance(f, int) or f is None else C.cast(f, C.c_void_p).value
-    _check(lib().mi_mcmc_rmhmc_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.c_void_p(addr(kernel_fn)), C.c_void_p(addr(kernel_data)),
-                                            C.c_void_p(addr(tensor_fn)), C.c_void_p(addr(tensor_data)), C.byref(settings),
-                                            C.c_void_p(out.ctypes.data), C.byref(nacc)))
+    _check(lib().mi_mcmc_rmhmc_run_callback(x0.ctypes.data, d, kernel_fn, kernel_data, tensor_fn, tensor_data, C.byref(settings),
+                                            out.ctypes.data, C.byref(nacc)))
     return out.T.copy(), int(nacc.value)
 
 
 def test_set_grid_cap(max_workgroups):
     """mi_mcmc_test_set_grid_cap (TEST HOOK, mi_mcmc_probes.h): cap the persistent grids of the dynamic-hand-out NUTS kernels and the grid-stride grids of the
     matrix-product route and of draws_predict (its pack and counting kernels); 0 = none."""
-    lib().mi_mcmc_test_set_grid_cap(C.c_uint32(int(max_workgroups)))
+    lib().mi_mcmc_test_set_grid_cap(int(max_workgroups))
 
 
 def test_set_linalg_stage_bytes(n_bytes):
     """mi_mcmc_test_set_linalg_stage_bytes (TEST HOOK, mi_mcmc_probes.h): the staging budget of the device INV (2 d doubles) / CHOL_LOWER (d doubles)
     in bytes, beyond which a matrix runs the host loops; 0 = the real budget (60 KB of LDS).  Empties the memoised factorisations."""
-    lib().mi_mcmc_test_set_linalg_stage_bytes(C.c_uint32(int(n_bytes)))
+    lib().mi_mcmc_test_set_linalg_stage_bytes(int(n_bytes))
 
 
 def test_linalg_computed():
     """mi_mcmc_test_linalg_computed (TEST HOOK, mi_mcmc_probes.h): INV / CHOL_LOWER factorisations computed so far, i.e. not answered by the memo."""
-    f = lib().mi_mcmc_test_linalg_computed
-    f.restype = C.c_uint64
-    return int(f())
+    return lib().mi_mcmc_test_linalg_computed()
 
 
 def test_linalg_computed_on_device():
     """mi_mcmc_test_linalg_computed_on_device (TEST HOOK, mi_mcmc_probes.h): ... those of them that ran the device kernels, not the host loops."""
-    f = lib().mi_mcmc_test_linalg_computed_on_device
-    f.restype = C.c_uint64
-    return int(f())
+    return lib().mi_mcmc_test_linalg_computed_on_device()
 
 
 def test_set_gemm_nuts_ws_bytes(n_bytes):
     """mi_mcmc_test_set_gemm_nuts_ws_bytes (TEST HOOK, mi_mcmc_probes.h): the workspace nuts on the matrix-product route may take for itself (the packed matrices
     and one range of chains), as if that were all the free device memory; 0 = the real figure.  Fewer chains than the call's fit: consecutive ranges in multiples of
     128; not even 128: the literal kernel.  Results do not depend on it."""
-    lib().mi_mcmc_test_set_gemm_nuts_ws_bytes(C.c_uint64(int(n_bytes)))
-
-
-def _u64_hook(name, *args):
-    f = getattr(lib(), name)
-    f.restype = C.c_uint64
-    return int(f(*args))
+    lib().mi_mcmc_test_set_gemm_nuts_ws_bytes(int(n_bytes))
 
 
 def test_gemm_nuts_ranges():
     """mi_mcmc_test_gemm_nuts_ranges (TEST HOOK): ranges of chains nuts on the matrix-product route has run so far in this process (monotonic)."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_ranges")
+    return lib().mi_mcmc_test_gemm_nuts_ranges()
 
 
 def test_gemm_nuts_last_ticks():
@@ -330,49 +249,46 @@ def test_gemm_nuts_last_ticks():
 
 def test_gemm_nuts_tick_ceiling(max_tree_depth, n_draws, search=True):
     """mi_mcmc_test_gemm_nuts_tick_ceiling (TEST HOOK; host arithmetic, no device): the ticks after which the route's host loop gives up."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_tick_ceiling", C.c_uint32(int(max_tree_depth)), C.c_uint64(int(n_draws)), C.c_int(1 if search else 0))
+    return lib().mi_mcmc_test_gemm_nuts_tick_ceiling(int(max_tree_depth), int(n_draws), 1 if search else 0)
 
 
 def test_gemm_nuts_chain_bytes(d, n_rows, max_tree_depth):
     """mi_mcmc_test_gemm_nuts_chain_bytes (TEST HOOK; host arithmetic): workspace bytes per chain; n_rows = 0: the dense Gaussian."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_chain_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint32(int(max_tree_depth)))
+    return lib().mi_mcmc_test_gemm_nuts_chain_bytes(int(d), int(n_rows), int(max_tree_depth))
 
 
 def test_gemm_nuts_bounded_chain_bytes(d, n_rows, max_tree_depth):
     """mi_mcmc_test_gemm_nuts_bounded_chain_bytes (TEST HOOK; host arithmetic): workspace bytes per chain of a call with vals_bound -- one vector of padded d doubles
     more than test_gemm_nuts_chain_bytes (theta of the last point next to x)."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_bounded_chain_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint32(int(max_tree_depth)))
+    return lib().mi_mcmc_test_gemm_nuts_bounded_chain_bytes(int(d), int(n_rows), int(max_tree_depth))
 
 
 def test_gemm_nuts_fixed_bytes(d, n_rows):
     """mi_mcmc_test_gemm_nuts_fixed_bytes (TEST HOOK; host arithmetic): workspace bytes that do not depend on the chains (the packed matrices, the counters)."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_fixed_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)))
+    return lib().mi_mcmc_test_gemm_nuts_fixed_bytes(int(d), int(n_rows))
 
 
 def test_gemm_nuts_range_chains(n_chains, chain_bytes, fixed_bytes, budget):
     """mi_mcmc_test_gemm_nuts_range_chains (TEST HOOK; host arithmetic): chains per range under `budget` bytes -- all of them (padded to 128) or a multiple of 128; 0: none."""
-    return _u64_hook("mi_mcmc_test_gemm_nuts_range_chains", C.c_uint64(int(n_chains)), C.c_uint64(int(chain_bytes)), C.c_uint64(int(fixed_bytes)), C.c_uint64(int(budget)))
-
-
-GEMM_PLAIN, GEMM_DENSE_M, GEMM_BOUNDED = 0, 1, 2       # the variants of hmc / mala / rwmh on the matrix-product route (test_gemm_need_bytes)
+    return lib().mi_mcmc_test_gemm_nuts_range_chains(int(n_chains), int(chain_bytes), int(fixed_bytes), int(budget))
 
 
 def test_set_gemm_graph(mode):
     """mi_mcmc_test_set_gemm_graph (TEST HOOK, mi_mcmc_probes.h): 1 = the samplers of the matrix-product route never capture the launches of a draw / a tick into a
     graph (what a call of 65 536 chains does); 0 = the rule as it is.  Results do not depend on it."""
-    lib().mi_mcmc_test_set_gemm_graph(C.c_int(int(mode)))
+    lib().mi_mcmc_test_set_gemm_graph(int(mode))
 
 
 def test_set_gemm_ws_bytes(n_bytes):
     """mi_mcmc_test_set_gemm_ws_bytes (TEST HOOK, mi_mcmc_probes.h): the device memory the capacity condition of hmc / mala / rwmh on the matrix-product route sees
     (0 = the real figure); a call that needs more stays on the literal kernel.  Results do not depend on it."""
-    lib().mi_mcmc_test_set_gemm_ws_bytes(C.c_uint64(int(n_bytes)))
+    lib().mi_mcmc_test_set_gemm_ws_bytes(int(n_bytes))
 
 
 def test_gemm_need_bytes(d, n_rows, n_chains, variant=GEMM_PLAIN, replay=True):
     """mi_mcmc_test_gemm_need_bytes (TEST HOOK; host arithmetic, no device): what that condition compares with the memory -- the workspace, with `replay` (hmc, mala)
     the literal replay's part behind it, and the uploads.  n_rows = 0: the dense Gaussian."""
-    return _u64_hook("mi_mcmc_test_gemm_need_bytes", C.c_uint32(int(d)), C.c_uint32(int(n_rows)), C.c_uint64(int(n_chains)), C.c_int(int(variant)), C.c_int(1 if replay else 0))
+    return lib().mi_mcmc_test_gemm_need_bytes(int(d), int(n_rows), int(n_chains), int(variant), 1 if replay else 0)
 
 
 def last_kernel():
@@ -383,14 +299,14 @@ def last_kernel():
 def release_workspace(stream=None, all_streams=True):
     """mi_mcmc_release_workspace: free the cached kernel workspaces of the current device; returns the bytes freed."""
     n = C.c_uint64(0)
-    _check(lib().mi_mcmc_release_workspace(C.c_void_p(stream or 0), C.c_int(1 if all_streams else 0), C.byref(n)))
+    _check(lib().mi_mcmc_release_workspace(stream or 0, 1 if all_streams else 0, C.byref(n)))
     return int(n.value)
 
 
 def run(algo, target, settings, chains, stream=None):
     """Raw call: mi_mcmc_<algo>_run(target, settings, chains, stream)."""
     fn = getattr(lib(), _RUN[algo])
-    _check(fn(C.byref(target), C.byref(settings), C.byref(chains), C.c_void_p(stream or 0)))
+    _check(fn(C.byref(target), C.byref(settings), C.byref(chains), stream or 0))
 
 
 def sample(algo, kind, init, settings, prec=None, X=None, y=None, chain0=0, want_draws=True, draw0=0, step_size_in=None,
@@ -495,10 +411,9 @@ def hmc_callback(initial_vals, callback, settings, target_data=None, algo="hmc")
     else:
         cb = callback
     fn = getattr(lib(), f"mi_mcmc_{algo}_run_callback")
-    args = [C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
-            C.byref(settings), C.c_void_p(draws.ctypes.data), C.byref(n_acc)]
+    args = [x0.ctypes.data, d, cb, target_data or 0, C.byref(settings), draws.ctypes.data, C.byref(n_acc)]
     if algo == "nuts":
-        args.append(C.c_void_p(0))
+        args.append(None)
     _check(fn(*args))
     return draws, int(n_acc.value)
 
@@ -554,7 +469,7 @@ def de(kind, init, settings, de_settings=None, n_pop=None, prec=None, X=None, y=
     p.struct_size = C.sizeof(mi_populations)
     p.mem, p.n_populations, p.population0, p.draw0 = MEM_HOST, P, int(population0), int(draw0)
     p.initial_vals, p.population, p.draws, p.n_accept = _ptr(iv), _ptr(pop), _ptr(draws), _ptr(n_accept)
-    _check(lib().mi_mcmc_de_run(C.byref(t), C.byref(settings), C.byref(ds), C.byref(p), C.c_void_p(0)))
+    _check(lib().mi_mcmc_de_run(C.byref(t), C.byref(settings), C.byref(ds), C.byref(p), None))
     return draws, dict(population=pop, n_accept=n_accept)
 
 
@@ -574,8 +489,7 @@ def de_callback(initial_vals, callback, settings, de_settings=None, n_pop=None, 
         cb = LOG_KERNEL_CB(_tramp)
     else:
         cb = callback
-    _check(lib().mi_mcmc_de_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
-                                         C.byref(settings), C.byref(ds), C.c_void_p(draws.ctypes.data), C.byref(n_acc)))
+    _check(lib().mi_mcmc_de_run_callback(x0.ctypes.data, d, cb, target_data or 0, C.byref(settings), C.byref(ds), draws.ctypes.data, C.byref(n_acc)))
     return draws, int(n_acc.value)
 
 
@@ -634,7 +548,7 @@ def aees(target, init, settings, aees_settings=None, run0=0, want_draws=True):
     r.struct_size = C.sizeof(mi_aees_runs)
     r.mem, r.n_runs, r.run0 = MEM_HOST, P, int(run0)
     r.initial_vals, r.draws, r.final_states, r.n_accept, r.n_ee_accept = _ptr(iv), _ptr(draws), _ptr(fin), _ptr(n_acc), _ptr(n_ee)
-    _check(lib().mi_mcmc_aees_run(C.byref(t), C.byref(settings), C.byref(a), C.byref(r), C.c_void_p(0)))
+    _check(lib().mi_mcmc_aees_run(C.byref(t), C.byref(settings), C.byref(a), C.byref(r), None))
     return draws, dict(final_states=fin, n_accept=n_acc, n_ee_accept=n_ee)
 
 
@@ -654,9 +568,8 @@ def aees_callback(initial_vals, callback, settings, aees_settings=None, target_d
         cb = LOG_KERNEL_CB(_tramp)
     else:
         cb = callback
-    _check(lib().mi_mcmc_aees_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), C.c_void_p(target_data or 0),
-                                           C.byref(settings), C.byref(a), C.c_void_p(draws.ctypes.data), C.c_void_p(fin.ctypes.data),
-                                           C.c_void_p(n_acc.ctypes.data), C.c_void_p(n_ee.ctypes.data)))
+    _check(lib().mi_mcmc_aees_run_callback(x0.ctypes.data, d, cb, target_data or 0, C.byref(settings), C.byref(a), draws.ctypes.data, fin.ctypes.data,
+                                           n_acc.ctypes.data, n_ee.ctypes.data))
     return draws, dict(final_states=fin, n_accept=n_acc, n_ee_accept=n_ee)
 
 
@@ -666,30 +579,26 @@ def probe_mfma(A, B, Cin):
     B = np.ascontiguousarray(B, dtype=np.float64)
     Cin = np.ascontiguousarray(Cin, dtype=np.float64)
     D = np.zeros((16, 16))
-    _check(probes_lib().mi_probe_mfma_f64(C.c_void_p(A.ctypes.data), C.c_void_p(B.ctypes.data),
-                                   C.c_void_p(Cin.ctypes.data), C.c_void_p(D.ctypes.data)))
+    _check(probes_lib().mi_probe_mfma_f64(A.ctypes.data, B.ctypes.data, Cin.ctypes.data, D.ctypes.data))
     return D
 
 
 def probe_math(fn, x):
     x = np.ascontiguousarray(x, dtype=np.float64)
     o1, o2 = np.empty_like(x), np.empty_like(x)
-    _check(probes_lib().mi_probe_math(fn, C.c_void_p(x.ctypes.data), C.c_uint64(x.size),
-                               C.c_void_p(o1.ctypes.data), C.c_void_p(o2.ctypes.data)))
+    _check(probes_lib().mi_probe_math(fn, x.ctypes.data, x.size, o1.ctypes.data, o2.ctypes.data))
     return o1, o2
 
 
 def probe_normals(seed, chain, draw, stream, d):
     out = np.zeros(d)
-    _check(probes_lib().mi_probe_normals(C.c_uint64(seed), C.c_uint64(chain), C.c_uint32(draw),
-                                  C.c_uint32(stream), C.c_uint64(d), C.c_void_p(out.ctypes.data)))
+    _check(probes_lib().mi_probe_normals(seed, chain, draw, stream, d, out.ctypes.data))
     return out
 
 
 def probe_uniform(seed, chain, draw, slot):
     out = np.zeros(1)
-    _check(probes_lib().mi_probe_uniform(C.c_uint64(seed), C.c_uint64(chain), C.c_uint32(draw),
-                                  C.c_uint32(slot), C.c_void_p(out.ctypes.data)))
+    _check(probes_lib().mi_probe_uniform(seed, chain, draw, slot, out.ctypes.data))
     return float(out[0])
 
 
@@ -710,7 +619,7 @@ def mat_inverse(A):
     A = np.ascontiguousarray(A, dtype=np.float64)
     d = A.shape[0]
     out = np.empty((d, d))
-    _check(lib().mi_mcmc_mat_inverse(C.c_void_p(A.ctypes.data), C.c_uint64(d), C.c_void_p(out.ctypes.data)))
+    _check(lib().mi_mcmc_mat_inverse(A.ctypes.data, d, out.ctypes.data))
     return out
 
 
@@ -719,7 +628,7 @@ def mat_cholesky_lower(A):
     A = np.ascontiguousarray(A, dtype=np.float64)
     d = A.shape[0]
     out = np.empty((d, d))
-    _check(lib().mi_mcmc_mat_cholesky_lower(C.c_void_p(A.ctypes.data), C.c_uint64(d), C.c_void_p(out.ctypes.data)))
+    _check(lib().mi_mcmc_mat_cholesky_lower(A.ctypes.data, d, out.ctypes.data))
     return out
 
 
@@ -733,9 +642,7 @@ def draw_stats(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=N
     mean = np.zeros(d)
     acov = np.zeros((n_keep, d)) if want_acov else None
     rhat, ess = np.zeros(d), np.zeros(d)
-    _check(lib().mi_mcmc_draw_stats(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                    C.c_void_p(mean.ctypes.data), C.c_void_p(acov.ctypes.data if want_acov else 0), C.c_void_p(rhat.ctypes.data),
-                                    C.c_void_p(ess.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draw_stats(_ptr(draws), mem, n_keep, d, n_chains, mean.ctypes.data, _ptr(acov), rhat.ctypes.data, ess.ctypes.data, stream or 0))
     return dict(mean=mean, acov=acov, rhat=rhat, ess=ess)
 
 
@@ -762,13 +669,8 @@ def test_stats_host(acov=None, n=None, moments=None, n_chains=None):
         moments = np.ascontiguousarray(moments, dtype=np.float64)
         G, d = moments.shape[:2]
         rhat = np.zeros(d)
-    ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None else 0)
-    lib().mi_mcmc_test_stats_host(ptr(acov), C.c_uint64(nlag), C.c_uint64(d), C.c_uint64(int(n)), ptr(moments), C.c_uint32(G), C.c_uint64(int(n_chains or 0)),
-                                  ptr(ess), ptr(hit), ptr(rhat))
+    lib().mi_mcmc_test_stats_host(_ptr(acov), nlag, d, int(n), _ptr(moments), G, int(n_chains or 0), _ptr(ess), _ptr(hit), _ptr(rhat))
     return dict(ess=ess, hit=hit, rhat=rhat)
-
-
-STATS_ALL_LAGS = 0xFFFFFFFF
 
 
 def draw_stats_lags(draws, max_lag=None, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_acov=True):
@@ -785,9 +687,8 @@ def draw_stats_lags(draws, max_lag=None, n_keep=None, d=None, n_chains=None, mem
     K = min(ml, max(n_keep, 1) - 1)
     mean, rhat, ess, ended = np.zeros(d), np.zeros(d), np.zeros(d), np.zeros(d, dtype=np.uint8)
     acov = np.zeros((K + 1, d)) if want_acov else None
-    _check(lib().mi_mcmc_draw_stats_lags(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint32(ml),
-                                         C.c_void_p(mean.ctypes.data), C.c_void_p(acov.ctypes.data if want_acov else 0), C.c_void_p(rhat.ctypes.data),
-                                         C.c_void_p(ess.ctypes.data), C.c_void_p(ended.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draw_stats_lags(_ptr(draws), mem, n_keep, d, n_chains, ml, mean.ctypes.data, _ptr(acov), rhat.ctypes.data,
+                                         ess.ctypes.data, ended.ctypes.data, stream or 0))
     return dict(mean=mean, acov=acov, rhat=rhat, ess=ess, ended=ended)
 
 
@@ -811,8 +712,7 @@ def draws_covariance(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, st
         n_keep, d, n_chains = draws.shape
     mean = np.zeros(d) if want_mean else None
     cov = np.zeros((d, d)) if want_cov else None
-    _check(lib().mi_mcmc_draws_covariance(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                          C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_covariance(_ptr(draws), mem, n_keep, d, n_chains, _ptr(mean), _ptr(cov), stream or 0))
     return mean, cov
 
 
@@ -832,8 +732,8 @@ def draws_order_stats(draws, ranks, n_keep=None, d=None, n_chains=None, mem=MEM_
     draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
     ranks = np.ascontiguousarray(ranks, dtype=np.uint64).ravel()
     out = np.zeros((ranks.size, d))
-    _check(lib().mi_mcmc_draws_order_stats(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                           C.c_void_p(ranks.ctypes.data), C.c_uint32(ranks.size), C.c_void_p(out.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_order_stats(_ptr(draws), mem, n_keep, d, n_chains,
+                                           ranks.ctypes.data, ranks.size, out.ctypes.data, stream or 0))
     return out
 
 
@@ -844,19 +744,14 @@ def draws_quantiles(draws, probs, n_keep=None, d=None, n_chains=None, mem=MEM_HO
     draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
     probs = np.ascontiguousarray(probs, dtype=np.float64).ravel()
     out = np.zeros((probs.size, d))
-    _check(lib().mi_mcmc_draws_quantiles(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                         C.c_void_p(probs.ctypes.data), C.c_uint32(probs.size), C.c_void_p(out.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_quantiles(_ptr(draws), mem, n_keep, d, n_chains,
+                                         probs.ctypes.data, probs.size, out.ctypes.data, stream or 0))
     return out
 
 
 def draws_to_chain_major_device(draws, n_keep, d, n_chains, out, stream=None):
     """mi_mcmc_draws_to_chain_major_device: slab [n_keep][d][C] in HBM -> [C][d][n_keep] in HBM (device tensors / pointers)."""
-    _check(lib().mi_mcmc_draws_to_chain_major_device(C.c_void_p(_ptr(draws)), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                                     C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
-
-
-RANK_AVERAGE, RANK_NORMAL = 0, 1
-RANK_SPLIT, RANK_FOLD = 1, 2
+    _check(lib().mi_mcmc_draws_to_chain_major_device(_ptr(draws), n_keep, d, n_chains, _ptr(out), stream or 0))
 
 
 def norm_ppf(p):
@@ -864,7 +759,7 @@ def norm_ppf(p):
     deterministic logarithm; include/mi_mcmc.h).  Needs no device.  Returns an array of p's shape."""
     p = np.ascontiguousarray(p, dtype=np.float64)
     z = np.empty_like(p)
-    _check(lib().mi_mcmc_norm_ppf(C.c_void_p(p.ctypes.data), C.c_uint64(p.size), C.c_void_p(z.ctypes.data)))
+    _check(lib().mi_mcmc_norm_ppf(p.ctypes.data, p.size, z.ctypes.data))
     return z
 
 
@@ -882,8 +777,7 @@ def draws_rank_transform(draws, what="normal", split=False, fold=False, n_keep=N
         if mem != MEM_HOST:
             raise ValueError("a device slab needs a device `out`")
         out = np.zeros((n_keep // 2, d, 2 * n_chains) if split else (n_keep, d, n_chains))
-    _check(lib().mi_mcmc_draws_rank_transform(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                              C.c_int32(w), C.c_uint32(flags), C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_rank_transform(_ptr(draws), mem, n_keep, d, n_chains, w, flags, _ptr(out), stream or 0))
     return out
 
 
@@ -893,8 +787,8 @@ def draw_stats_ranked(draws, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, s
     draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
     names = ("rhat", "rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail")
     res = {k: np.zeros(d) for k in names}
-    _check(lib().mi_mcmc_draw_stats_ranked(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                           *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draw_stats_ranked(_ptr(draws), mem, n_keep, d, n_chains,
+                                           *[res[k].ctypes.data for k in names], stream or 0))
     return res
 
 
@@ -906,8 +800,8 @@ def draw_stats_ranked_lags(draws, max_lag=None, n_keep=None, d=None, n_chains=No
     res = {k: np.zeros(d) for k in names}
     res["ended"] = np.zeros(d, dtype=np.uint8)
     ml = STATS_ALL_LAGS if max_lag is None else int(max_lag)
-    _check(lib().mi_mcmc_draw_stats_ranked_lags(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint32(ml),
-                                                *[C.c_void_p(res[k].ctypes.data) for k in names], C.c_void_p(res["ended"].ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draw_stats_ranked_lags(_ptr(draws), mem, n_keep, d, n_chains, ml,
+                                                *[res[k].ctypes.data for k in names], res["ended"].ctypes.data, stream or 0))
     return res
 
 
@@ -928,8 +822,7 @@ def draws_log_kernel(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, st
         if mem != MEM_HOST:
             raise ValueError("a device slab needs a device `out`")
         out = np.zeros((int(n_keep), int(n_chains)))
-    _check(lib().mi_mcmc_draws_log_kernel(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                          C.c_void_p(_ptr(out)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_log_kernel(C.byref(target), _ptr(draws), mem, int(n_keep), int(n_chains), _ptr(out), stream or 0))
     return out
 
 
@@ -937,8 +830,8 @@ def test_logk_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     """mi_mcmc_test_logk_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_log_kernel call, host arithmetic -- a dict of route (0 one lane per column,
     1 the fused matrix product), grid, block, lds_bytes, Kp, ldA, n_row_tiles, ws_bytes."""
     o = (C.c_uint64 * 8)()
-    lib().mi_mcmc_test_logk_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
+    lib().mi_mcmc_test_logk_plan(int(kind), int(d), int(n_rows), int(n_keep), int(n_chains),
+                                 int(bool(slab_host)), int(bool(target_host)), o)
     return dict(zip(("route", "grid", "block", "lds_bytes", "Kp", "ldA", "n_row_tiles", "ws_bytes"), (int(v) for v in o)))
 
 
@@ -963,8 +856,8 @@ def draws_waic(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stream=N
         p_waic = np.zeros(n_rows) if want_p_waic else None
         loglik = np.zeros((n_rows, int(n_keep), int(n_chains))) if want_loglik else None
     summ = np.zeros(4) if want_summary else None
-    _check(lib().mi_mcmc_draws_waic(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                    C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(p_waic)), C.c_void_p(_ptr(loglik)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_waic(C.byref(target), _ptr(draws), mem, int(n_keep), int(n_chains),
+                                    _ptr(lppd), _ptr(p_waic), _ptr(loglik), _ptr(summ), stream or 0))
     summary = None if summ is None else dict(zip(("elpd_waic", "p_waic", "lppd", "se_elpd"), (float(v) for v in summ)))
     return dict(lppd=lppd, p_waic=p_waic, loglik=loglik, summary=summary)
 
@@ -973,8 +866,8 @@ def test_waic_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_hos
     """mi_mcmc_test_waic_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_waic call, host arithmetic -- a dict of route (0 elementwise, 1 the
     matrix product), chunk, n_chunks, grid, block, lds_bytes, ldR, Kp, merge_grid, ws_bytes."""
     o = (C.c_uint64 * 10)()
-    lib().mi_mcmc_test_waic_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), C.c_int(int(bool(want_loglik))), o)
+    lib().mi_mcmc_test_waic_plan(int(kind), int(d), int(n_rows), int(n_keep), int(n_chains),
+                                 int(bool(slab_host)), int(bool(target_host)), int(bool(want_loglik)), o)
     return dict(zip(("route", "chunk", "n_chunks", "grid", "block", "lds_bytes", "ldR", "Kp", "merge_grid", "ws_bytes"), (int(v) for v in o)))
 
 
@@ -1010,8 +903,8 @@ def draws_predict(target, draws, seed=0, n_keep=None, n_chains=None, mem=MEM_HOS
         ll_obs = np.zeros((n, Cn)) if want_ll_obs else None
     summ = np.zeros(4) if want_summary else None
     outs = (p_mean, p_var, rep_freq, prob, yrep, t_rep, ll_rep, ll_obs)
-    _check(lib().mi_mcmc_draws_predict(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                       C.c_uint64(int(seed)), *[C.c_void_p(_ptr(o)) for o in outs], C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_predict(C.byref(target), _ptr(draws), mem, int(n_keep), int(n_chains),
+                                       int(seed), *[_ptr(o) for o in outs], _ptr(summ), stream or 0))
     summary = None if summ is None else dict(zip(("t_obs", "ppp_t", "ppp_dev", "t_rep_mean"), (float(v) for v in summ)))
     return dict(p_mean=p_mean, p_var=p_var, rep_freq=rep_freq, prob=prob, yrep=yrep, t_rep=t_rep, ll_rep=ll_rep, ll_obs=ll_obs, summary=summary)
 
@@ -1036,32 +929,29 @@ def draws_psis_loo(target, draws, n_keep=None, n_chains=None, mem=MEM_HOST, stre
         pareto_k = np.zeros(n_rows) if want_pareto_k else None
         lppd = np.zeros(n_rows) if want_lppd else None
     summ = np.zeros(5) if want_summary else None
-    _check(lib().mi_mcmc_draws_psis_loo(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                        C.c_void_p(_ptr(elpd_loo)), C.c_void_p(_ptr(pareto_k)), C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_psis_loo(C.byref(target), _ptr(draws), mem, int(n_keep), int(n_chains),
+                                        _ptr(elpd_loo), _ptr(pareto_k), _ptr(lppd), _ptr(summ), stream or 0))
     summary = None if summ is None else dict(zip(("elpd_loo", "p_loo", "lppd", "se_elpd_loo", "n_bad"), (float(v) for v in summ)))
     return dict(elpd_loo=elpd_loo, pareto_k=pareto_k, lppd=lppd, summary=summary)
 
 
 def test_set_psis_ll_bytes(n_bytes):
     """mi_mcmc_test_set_psis_ll_bytes (TEST HOOK, mi_mcmc_probes.h): the budget of a row group's block ll of draws_psis_loo (0 = the real one)."""
-    lib().mi_mcmc_test_set_psis_ll_bytes(C.c_uint64(int(n_bytes)))
+    lib().mi_mcmc_test_set_psis_ll_bytes(int(n_bytes))
 
 
 def test_set_psis_lds_tail(n_doubles):
     """mi_mcmc_test_set_psis_lds_tail (TEST HOOK, mi_mcmc_probes.h): the tail values draws_psis_loo keeps in LDS (0 = the real capacity)."""
-    lib().mi_mcmc_test_set_psis_lds_tail(C.c_uint32(int(n_doubles)))
+    lib().mi_mcmc_test_set_psis_lds_tail(int(n_doubles))
 
 
 def test_psis_plan(kind, d, n_rows, n_keep, n_chains, slab_host=True, target_host=True):
     """mi_mcmc_test_psis_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a draws_psis_loo call under the hooks set, host arithmetic -- a dict of M, m, G,
     n_groups, last_rows, tail_route (0 LDS, 1 re-read), lds_bytes, n_pieces, piece, sort_rows, ll_bytes, ws_bytes."""
     o = (C.c_uint64 * 12)()
-    lib().mi_mcmc_test_psis_plan(C.c_int32(int(kind)), C.c_uint64(int(d)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                 C.c_int(int(bool(slab_host))), C.c_int(int(bool(target_host))), o)
+    lib().mi_mcmc_test_psis_plan(int(kind), int(d), int(n_rows), int(n_keep), int(n_chains),
+                                 int(bool(slab_host)), int(bool(target_host)), o)
     return dict(zip(("M", "m", "G", "n_groups", "last_rows", "tail_route", "lds_bytes", "n_pieces", "piece", "sort_rows", "ll_bytes", "ws_bytes"), (int(v) for v in o)))
-
-
-LOGLIK_ROWS, LOGLIK_SLAB = 0, 1
 
 
 def _loglik_shape(loglik, layout, n_rows, n_keep, n_chains, mem):
@@ -1091,8 +981,8 @@ def loglik_waic(loglik, layout=LOGLIK_ROWS, n_rows=None, n_keep=None, n_chains=N
         lppd = np.zeros(n_rows) if want_lppd else None
         p_waic = np.zeros(n_rows) if want_p_waic else None
     summ = np.zeros(4) if want_summary else None
-    _check(lib().mi_mcmc_loglik_waic(C.c_void_p(_ptr(loglik)), C.c_int32(layout), C.c_int32(mem), C.c_uint64(n_rows), C.c_uint64(n_keep), C.c_uint64(n_chains),
-                                     C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(p_waic)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_loglik_waic(_ptr(loglik), layout, mem, n_rows, n_keep, n_chains,
+                                     _ptr(lppd), _ptr(p_waic), _ptr(summ), stream or 0))
     summary = None if summ is None else dict(zip(("elpd_waic", "p_waic", "lppd", "se_elpd"), (float(v) for v in summ)))
     return dict(lppd=lppd, p_waic=p_waic, loglik=None, summary=summary)
 
@@ -1108,8 +998,8 @@ def loglik_psis_loo(loglik, layout=LOGLIK_ROWS, n_rows=None, n_keep=None, n_chai
         pareto_k = np.zeros(n_rows) if want_pareto_k else None
         lppd = np.zeros(n_rows) if want_lppd else None
     summ = np.zeros(5) if want_summary else None
-    _check(lib().mi_mcmc_loglik_psis_loo(C.c_void_p(_ptr(loglik)), C.c_int32(layout), C.c_int32(mem), C.c_uint64(n_rows), C.c_uint64(n_keep), C.c_uint64(n_chains),
-                                         C.c_void_p(_ptr(elpd_loo)), C.c_void_p(_ptr(pareto_k)), C.c_void_p(_ptr(lppd)), C.c_void_p(_ptr(summ)), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_loglik_psis_loo(_ptr(loglik), layout, mem, n_rows, n_keep, n_chains,
+                                         _ptr(elpd_loo), _ptr(pareto_k), _ptr(lppd), _ptr(summ), stream or 0))
     summary = None if summ is None else dict(zip(("elpd_loo", "p_loo", "lppd", "se_elpd_loo", "n_bad"), (float(v) for v in summ)))
     return dict(elpd_loo=elpd_loo, pareto_k=pareto_k, lppd=lppd, summary=summary)
 
@@ -1118,8 +1008,8 @@ def test_loglik_plan(layout, n_rows, n_keep, n_chains, mat_host=True, psis=True)
     """mi_mcmc_test_loglik_plan (TEST HOOK, mi_mcmc_probes.h): the plan of a loglik_waic (psis=False) or loglik_psis_loo call under the hooks set, host
     arithmetic -- a dict of n_chunks, fold_grid, M, m, sort_rows, sort_groups, tail_route (0 LDS, 1 re-read), ws_bytes."""
     o = (C.c_uint64 * 8)()
-    lib().mi_mcmc_test_loglik_plan(C.c_int32(int(layout)), C.c_uint64(int(n_rows)), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)),
-                                   C.c_int(int(bool(mat_host))), C.c_int(int(bool(psis))), o)
+    lib().mi_mcmc_test_loglik_plan(int(layout), int(n_rows), int(n_keep), int(n_chains),
+                                   int(bool(mat_host)), int(bool(psis)), o)
     return dict(zip(("n_chunks", "fold_grid", "M", "m", "sort_rows", "sort_groups", "tail_route", "ws_bytes"), (int(v) for v in o)))
 
 
@@ -1149,9 +1039,9 @@ def bridge_proposal(draws, n_fit=0, n_prop=0, seed=0, n_keep=None, d=None, n_cha
     mean = np.zeros(d) if want_mean else None
     cov = np.zeros((d, d)) if want_cov else None
     info = np.zeros(2)
-    _check(lib().mi_mcmc_bridge_proposal(C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_uint64(int(n_fit)),
-                                         C.c_uint64(int(n_prop)), C.c_uint64(int(seed)), C.c_void_p(_ptr(prop)), C.c_void_p(_ptr(logg_post)), C.c_void_p(_ptr(logg_prop)),
-                                         C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(info.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_bridge_proposal(_ptr(draws), mem, n_keep, d, n_chains, int(n_fit),
+                                         int(n_prop), int(seed), _ptr(prop), _ptr(logg_post), _ptr(logg_prop),
+                                         _ptr(mean), _ptr(cov), info.ctypes.data, stream or 0))
     return dict(prop=prop, logg_post=logg_post, logg_prop=logg_prop, mean=mean, cov=cov, status=int(info[0]), ldh=float(info[1]))
 
 
@@ -1171,9 +1061,9 @@ def bridge_estimate(logp_post, logg_post, logp_prop, logg_prop, n_it=None, n_cha
         n_prop = logp_prop.size
         f2 = np.zeros((n_it, n_chains)) if want_f2 else None
     summ = np.zeros(8)
-    _check(lib().mi_mcmc_bridge_estimate(C.c_void_p(_ptr(logp_post)), C.c_void_p(_ptr(logg_post)), C.c_void_p(_ptr(logp_prop)), C.c_void_p(_ptr(logg_prop)), C.c_int32(mem),
-                                         C.c_uint64(int(n_it)), C.c_uint64(int(n_chains)), C.c_uint64(int(n_prop)), C.c_double(float(n_eff)), C.c_double(float(tol)),
-                                         C.c_uint64(int(max_iter)), C.c_void_p(_ptr(f2)), C.c_void_p(summ.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_bridge_estimate(_ptr(logp_post), _ptr(logg_post), _ptr(logp_prop), _ptr(logg_prop), mem,
+                                         int(n_it), int(n_chains), int(n_prop), float(n_eff), float(tol),
+                                         int(max_iter), _ptr(f2), summ.ctypes.data, stream or 0))
     return dict(f2=f2, summary=_bridge_summary(summ))
 
 
@@ -1195,12 +1085,12 @@ def draws_bridge(target, draws, n_fit=0, n_prop=0, seed=0, n_eff=0.0, tol=0.0, m
     mean = np.zeros(d) if want_mean else None
     cov = np.zeros((d, d)) if want_cov else None
     summ = np.zeros(8)
-    _check(lib().mi_mcmc_draws_bridge(C.byref(target), C.c_void_p(_ptr(draws)), C.c_int32(mem), C.c_uint64(int(n_keep)), C.c_uint64(int(n_chains)), C.c_uint64(int(n_fit)),
-                                      C.c_uint64(int(n_prop)), C.c_uint64(int(seed)), C.c_double(float(n_eff)), C.c_double(float(tol)), C.c_uint64(int(max_iter)),
-                                      C.c_void_p(_ptr(f2)), C.c_void_p(_ptr(mean)), C.c_void_p(_ptr(cov)), C.c_void_p(summ.ctypes.data), C.c_void_p(stream or 0)))
+    _check(lib().mi_mcmc_draws_bridge(C.byref(target), _ptr(draws), mem, int(n_keep), int(n_chains), int(n_fit),
+                                      int(n_prop), int(seed), float(n_eff), float(tol), int(max_iter),
+                                      _ptr(f2), _ptr(mean), _ptr(cov), summ.ctypes.data, stream or 0))
     return dict(f2=f2, mean=mean, cov=cov, summary=_bridge_summary(summ))
 
 
 def test_set_bridge_prop_bytes(n_bytes):
     """mi_mcmc_test_set_bridge_prop_bytes (TEST HOOK, mi_mcmc_probes.h): the budget of one group of proposal columns of bridge sampling (0 = the real one)."""
-    lib().mi_mcmc_test_set_bridge_prop_bytes(C.c_uint64(int(n_bytes)))
+    lib().mi_mcmc_test_set_bridge_prop_bytes(int(n_bytes))

@@ -272,8 +272,7 @@ def collate_rank_major(comm, local_draws, n_chains_total, out=None, stream=None)
         out = torch.empty(n_keep * d * int(n_chains_total), dtype=torch.float64, device=local_draws.device)
     stream = torch.cuda.current_stream().cuda_stream if stream is None else stream
     mcmc_amd._check(mcmc_amd.lib().mi_mcmc_allgather_draws_rank_major(
-        comm.comm, C.c_uint32(comm.world), C.c_uint32(comm.rank), C.c_void_p(local_draws.data_ptr()), C.c_uint64(n_keep), C.c_uint64(d),
-        C.c_uint64(int(n_chains_total)), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        comm.comm, comm.world, comm.rank, local_draws.data_ptr(), n_keep, d, int(n_chains_total), out.data_ptr(), stream))
     return out
 
 
@@ -286,9 +285,8 @@ def collate_begin(comm, slab, n_chains_total, row0, n_keep_total, out, producer_
     producer_stream = torch.cuda.current_stream().cuda_stream if producer_stream is None else producer_stream
     h = C.c_void_p(0)
     mcmc_amd._check(mcmc_amd.lib().mi_mcmc_allgather_draws_begin(
-        comm.comm, C.c_uint32(comm.world), C.c_uint32(comm.rank), C.c_void_p(slab.data_ptr()), C.c_uint64(int(slab.shape[0])),
-        C.c_uint64(int(slab.shape[1])), C.c_uint64(int(n_chains_total)), C.c_uint64(int(row0)), C.c_uint64(int(n_keep_total)),
-        C.c_void_p(out.data_ptr()), C.c_void_p(producer_stream), C.byref(h)))
+        comm.comm, comm.world, comm.rank, slab.data_ptr(), int(slab.shape[0]), int(slab.shape[1]), int(n_chains_total), int(row0), int(n_keep_total),
+        out.data_ptr(), producer_stream, C.byref(h)))
     return h
 
 
@@ -297,4 +295,4 @@ def collate_wait(handle, consumer_stream=None, block_host=False):
     import torch
     import mcmc_amd
     consumer_stream = torch.cuda.current_stream().cuda_stream if consumer_stream is None else consumer_stream
-    mcmc_amd._check(mcmc_amd.lib().mi_mcmc_allgather_draws_wait(handle, C.c_void_p(consumer_stream), C.c_int(1 if block_host else 0)))
+    mcmc_amd._check(mcmc_amd.lib().mi_mcmc_allgather_draws_wait(handle, consumer_stream, 1 if block_host else 0))

@@ -218,10 +218,10 @@ def test_bad_aees_arguments_are_refused_without_a_gpu():
     cb = mcmc_amd.LOG_KERNEL_CB(lambda v, g, u: 0.0)
     x0 = np.zeros(d)
     z = mcmc_amd.aees_settings(n_rings=0)
-    rc = mcmc_amd.lib().mi_mcmc_aees_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), None, C.byref(s),
+    rc = mcmc_amd.lib().mi_mcmc_aees_run_callback(x0.ctypes.data, d, cb, None, C.byref(s),
                                                   C.byref(z), None, None, None, None)
     assert rc == mcmc_amd.MI_ERR_BAD_ARG
-    rc = mcmc_amd.lib().mi_mcmc_aees_run_callback(None, C.c_uint64(d), C.cast(cb, C.c_void_p), None, C.byref(s), C.byref(a), None, None, None, None)
+    rc = mcmc_amd.lib().mi_mcmc_aees_run_callback(None, d, cb, None, C.byref(s), C.byref(a), None, None, None, None)
     assert rc == mcmc_amd.MI_ERR_BAD_ARG
     if mcmc_amd.lib().mi_mcmc_device_count() == 0:         # valid arguments: no CPU fallback
         assert _call(t, s, a, r) == mcmc_amd.MI_ERR_NO_DEVICE

@@ -83,25 +83,25 @@ def _needs_lib():
 
 def _rc_proposal(slab, n_keep, d, Cn, n_fit=0, n_prop=0, outs=True):
     info = np.zeros(2)
-    return mcmc_amd.lib().mi_mcmc_bridge_proposal(C.c_void_p(None if slab is None else slab.ctypes.data), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d),
-                                                  C.c_uint64(Cn), C.c_uint64(n_fit), C.c_uint64(n_prop), C.c_uint64(1), None, None, None, None, None,
-                                                  C.c_void_p(info.ctypes.data if outs else None), None)
+    return mcmc_amd.lib().mi_mcmc_bridge_proposal(None if slab is None else slab.ctypes.data, mcmc_amd.MEM_HOST, n_keep, d,
+                                                  Cn, n_fit, n_prop, 1, None, None, None, None, None,
+                                                  info.ctypes.data if outs else None, None)
 
 
 def _rc_estimate(n_it, Cn, n_prop, n_eff=0.0, tol=0.0, null_input=False, outs=True):
     a = np.zeros(max(n_it * Cn, 1) if n_it * Cn < 1 << 20 else 1)
     b = np.zeros(max(n_prop, 1) if n_prop < 1 << 20 else 1)
     summ = np.zeros(8)
-    p = lambda v: C.c_void_p(v.ctypes.data)
-    return mcmc_amd.lib().mi_mcmc_bridge_estimate(None if null_input else p(a), p(a), p(b), p(b), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_it), C.c_uint64(Cn),
-                                                  C.c_uint64(n_prop), C.c_double(n_eff), C.c_double(tol), C.c_uint64(0), None, p(summ) if outs else None, None)
+    p = lambda v: v.ctypes.data
+    return mcmc_amd.lib().mi_mcmc_bridge_estimate(None if null_input else p(a), p(a), p(b), p(b), mcmc_amd.MEM_HOST, n_it, Cn,
+                                                  n_prop, n_eff, tol, 0, None, p(summ) if outs else None, None)
 
 
 def _rc_bridge(target, slab, n_keep, Cn, n_fit=0, n_prop=0, n_eff=0.0, tol=0.0, outs=True):
     summ = np.zeros(8)
-    return mcmc_amd.lib().mi_mcmc_draws_bridge(None if target is None else C.byref(target), C.c_void_p(None if slab is None else slab.ctypes.data), C.c_int32(mcmc_amd.MEM_HOST),
-                                               C.c_uint64(n_keep), C.c_uint64(Cn), C.c_uint64(n_fit), C.c_uint64(n_prop), C.c_uint64(1), C.c_double(n_eff), C.c_double(tol),
-                                               C.c_uint64(0), None, None, None, C.c_void_p(summ.ctypes.data if outs else None), None)
+    return mcmc_amd.lib().mi_mcmc_draws_bridge(None if target is None else C.byref(target), None if slab is None else slab.ctypes.data, mcmc_amd.MEM_HOST,
+                                               n_keep, Cn, n_fit, n_prop, 1, n_eff, tol,
+                                               0, None, None, None, summ.ctypes.data if outs else None, None)
 
 
 def test_bad_arguments_are_refused_without_a_device():

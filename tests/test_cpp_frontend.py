@@ -103,7 +103,7 @@ def test_host_callback_route_matches_oracle_and_fused_kernel_bitwise():
     st = mcmc_amd.default_settings(rng_seed_value=1234, n_burnin_draws=50, n_keep_draws=100, n_leap_steps=10,
                                    step_size=0.2)
     tgt = orc.TargetSpec(orc.TARGET_ISO, d, W=4)
-    cb = C.cast(orc.lib().orc_target_kernel, C.c_void_p)
+    cb = orc.lib().orc_target_kernel
     draws_cb, nacc_cb = mcmc_amd.hmc_callback(np.ones(d), cb, st, target_data=C.addressof(tgt.c))
     so = orc.make_settings(seed=1234, n_burnin=50, n_keep=100, n_leap=10, step=0.2, W=4, chain_id=0)
     t2 = orc.TargetSpec(orc.TARGET_ISO, d, W=4)
@@ -125,7 +125,7 @@ def test_mala_rwmh_and_nuts_host_callback_routes_match_oracle_and_device_kernels
     ko = {"iso": orc.TARGET_ISO, "dense": orc.TARGET_DENSE, "diag": orc.TARGET_DIAG}[kind]
     kg = {"iso": mcmc_amd.TARGET_GAUSS_ISO, "dense": mcmc_amd.TARGET_GAUSS_DENSE, "diag": mcmc_amd.TARGET_GAUSS_DIAG}[kind]
     x0 = np.linspace(-0.5, 0.8, d)
-    cb = C.cast(orc.lib().orc_target_kernel, C.c_void_p)
+    cb = orc.lib().orc_target_kernel
     # mala
     st = mcmc_amd.default_settings(rng_seed_value=99, n_burnin_draws=20, n_keep_draws=60, step_size=0.3)
     tgt = orc.TargetSpec(ko, d, prec=prec, W=4)

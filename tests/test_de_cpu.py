@@ -164,10 +164,10 @@ def test_bad_de_arguments_are_refused_without_a_gpu():
     assert _call(nm, s, ds, p) == mcmc_amd.MI_ERR_UNSUPPORTED
     cb = mcmc_amd.LOG_KERNEL_CB(lambda v, g, u: 0.0)
     x0 = np.zeros(d)
-    rc = mcmc_amd.lib().mi_mcmc_de_run_callback(C.c_void_p(x0.ctypes.data), C.c_uint64(d), C.cast(cb, C.c_void_p), None, C.byref(s),
+    rc = mcmc_amd.lib().mi_mcmc_de_run_callback(x0.ctypes.data, d, cb, None, C.byref(s),
                                                 C.byref(mcmc_amd.de_settings(n_pop=2)), None, None)
     assert rc == mcmc_amd.MI_ERR_BAD_ARG
-    rc = mcmc_amd.lib().mi_mcmc_de_run_callback(None, C.c_uint64(d), C.cast(cb, C.c_void_p), None, C.byref(s), C.byref(ds), None, None)
+    rc = mcmc_amd.lib().mi_mcmc_de_run_callback(None, d, cb, None, C.byref(s), C.byref(ds), None, None)
     assert rc == mcmc_amd.MI_ERR_BAD_ARG
     if mcmc_amd.lib().mi_mcmc_device_count() == 0:         # valid arguments: no CPU fallback
         assert _call(t, s, ds, p) == mcmc_amd.MI_ERR_NO_DEVICE

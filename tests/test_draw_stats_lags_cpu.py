@@ -1,7 +1,6 @@
 """No GPU: the host side of mi_mcmc_draw_stats_lags / mi_mcmc_draw_stats_ranked_lags -- the numpy statement mcmc_amd/acov.py against the exact reference
 tests/draw_stats_lags_ref.py inside its bounds, against ess_per_chain (FFT against direct sums), the margin of every input the GPU tests use, the band
 schedule, the argument checks of the C ABI (returned before any HIP call) and the symbols."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -91,16 +90,14 @@ def test_band_plan_covers_every_offset_once(n):
 
 def _lags(slab, n_keep, d, n_chains, outs=(1, 1, 1, 1, 1), max_lag=0xFFFFFFFF):
     buf = np.zeros(8)
-    ptr = lambda on: C.c_void_p(buf.ctypes.data if on else 0)
-    return mcmc_amd.lib().mi_mcmc_draw_stats_lags(C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                                  C.c_uint32(max_lag), *[ptr(o) for o in outs], C.c_void_p(0))
+    ptr = lambda on: buf.ctypes.data if on else None
+    return mcmc_amd.lib().mi_mcmc_draw_stats_lags(slab, mcmc_amd.MEM_HOST, n_keep, d, n_chains, max_lag, *[ptr(o) for o in outs], None)
 
 
 def _ranked(slab, n_keep, d, n_chains, outs=(1,) * 6):
     buf = np.zeros(8)
-    ptr = lambda on: C.c_void_p(buf.ctypes.data if on else 0)
-    return mcmc_amd.lib().mi_mcmc_draw_stats_ranked_lags(C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                                         C.c_uint32(0xFFFFFFFF), *[ptr(o) for o in outs], C.c_void_p(0))
+    ptr = lambda on: buf.ctypes.data if on else None
+    return mcmc_amd.lib().mi_mcmc_draw_stats_ranked_lags(slab, mcmc_amd.MEM_HOST, n_keep, d, n_chains, 0xFFFFFFFF, *[ptr(o) for o in outs], None)
 
 
 X = np.zeros(64)

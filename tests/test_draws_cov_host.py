@@ -1,6 +1,5 @@
 """No GPU: mi_mcmc_draws_covariance and the dense mass adaptations reject bad arguments before any device call (MI_ERR_BAD_ARG even where no
 device is visible -- a call that reached the device probe would answer MI_ERR_NO_DEVICE there)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -9,8 +8,8 @@ import mcmc_amd
 
 
 def _cov_rc(slab_ptr, n_keep, d, n_chains, mean, cov):
-    return mcmc_amd.lib().mi_mcmc_draws_covariance(C.c_void_p(slab_ptr), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d),
-                                                   C.c_uint64(n_chains), C.c_void_p(mean), C.c_void_p(cov), C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draws_covariance(slab_ptr, mcmc_amd.MEM_HOST, n_keep, d,
+                                                   n_chains, mean, cov, None)
 
 
 @pytest.mark.parametrize("case", ["K_is_1", "K_is_0_keep", "K_is_0_chains", "d_is_0", "null_slab", "both_outputs_null"])

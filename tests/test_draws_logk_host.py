@@ -25,8 +25,8 @@ def _target(kind=mcmc_amd.TARGET_GAUSS_DENSE, d=3, prec=_PREC, X=None, y=None, n
 
 
 def _rc(target, slab=_X.ctypes.data, n_keep=2, n_chains=4, out=_OUT.ctypes.data):
-    return mcmc_amd.lib().mi_mcmc_draws_log_kernel(None if target is None else C.byref(target), C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST),
-                                                  C.c_uint64(n_keep), C.c_uint64(n_chains), C.c_void_p(out), C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draws_log_kernel(None if target is None else C.byref(target), slab, mcmc_amd.MEM_HOST,
+                                                  n_keep, n_chains, out, None)
 
 
 _LOGIT = dict(kind=mcmc_amd.TARGET_LOGISTIC, prec=None, X=_ROWS, y=_Y)

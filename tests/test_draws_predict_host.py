@@ -34,8 +34,8 @@ def _target(kind=mcmc_amd.TARGET_LOGISTIC, d=3, prec=None, X=_ROWS, y=_Y, n_rows
 
 def _rc(target, slab=_X.ctypes.data, n_keep=2, n_chains=4, outs=_ALL):
     ptrs = [_OUT[k].ctypes.data if k in outs else None for k in _NAMES]
-    return mcmc_amd.lib().mi_mcmc_draws_predict(None if target is None else C.byref(target), C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST),
-                                               C.c_uint64(n_keep), C.c_uint64(n_chains), C.c_uint64(7), *[C.c_void_p(p) for p in ptrs], C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draws_predict(None if target is None else C.byref(target), slab, mcmc_amd.MEM_HOST,
+                                               n_keep, n_chains, 7, *[p for p in ptrs], None)
 
 
 _BAD = {

@@ -5,7 +5,6 @@ is held to bit for bit, is itself checked against np.sort and np.quantile.
 The bound of the np.quantile comparison is derived, not fitted: numpy computes the same type-7 quantile by another formula of at most three
 roundings, ours has three (the difference, the product, the sum), each on a magnitude of at most 2 max(|x_lo|, |x_hi|): 6 eps max(|x_lo|, |x_hi|).  It
 is asked only where 0 < g < 1 on finite data; at g = 0 the rule `x_lo` is the definition (numpy's lerp gives NaN next to an infinity there)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -23,8 +22,7 @@ def _rc(fn, slab=_X.ctypes.data, n_keep=2, d=3, n_chains=4, sel=None, n_sel=2, o
     if sel is None:
         sel = (_RANKS if fn == "order_stats" else _PROBS).ctypes.data
     f = getattr(mcmc_amd.lib(), "mi_mcmc_draws_" + ("order_stats" if fn == "order_stats" else "quantiles"))
-    return f(C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains), C.c_void_p(sel), C.c_uint32(n_sel),
-             C.c_void_p(out), C.c_void_p(0))
+    return f(slab, mcmc_amd.MEM_HOST, n_keep, d, n_chains, sel, n_sel, out, None)
 
 
 _SHARED = {"null_slab": (dict(slab=None), "slab"), "null_out": (dict(out=None), "out"), "d_is_0": (dict(d=0), "d "),

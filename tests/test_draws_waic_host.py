@@ -37,8 +37,8 @@ def _target(kind=mcmc_amd.TARGET_LOGISTIC, d=3, prec=None, X=_ROWS, y=_Y, n_rows
 
 def _rc(target, slab=_X.ctypes.data, n_keep=2, n_chains=4, outs=(True, True, True, True)):
     ptrs = [a.ctypes.data if on else None for a, on in zip((_LPPD, _PW, _LL, _SUMM), outs)]
-    return mcmc_amd.lib().mi_mcmc_draws_waic(None if target is None else C.byref(target), C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST),
-                                            C.c_uint64(n_keep), C.c_uint64(n_chains), *[C.c_void_p(p) for p in ptrs], C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draws_waic(None if target is None else C.byref(target), slab, mcmc_amd.MEM_HOST,
+                                            n_keep, n_chains, *[p for p in ptrs], None)
 
 
 _NORMAL = dict(kind=mcmc_amd.TARGET_NORMAL_MODEL, d=2, X=None)

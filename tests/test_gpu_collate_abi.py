@@ -15,7 +15,7 @@ def test_c_shard_bounds_equal_the_python_ones():
     for total, world in [(65536, 8), (13, 2), (5, 8), (1 << 20, 8), (7, 3), (0, 4)]:
         for r in range(world):
             c0, nl = C.c_uint64(0), C.c_uint64(0)
-            lib.mi_mcmc_shard_bounds(C.c_uint64(total), C.c_uint32(world), C.c_uint32(r), C.byref(c0), C.byref(nl))
+            lib.mi_mcmc_shard_bounds(total, world, r, C.byref(c0), C.byref(nl))
             assert (c0.value, nl.value) == shard_bounds(total, world, r)
 
 
@@ -31,8 +31,8 @@ def test_merge_shards_interleaves_ragged_rank_major_slabs(world, n_keep, d, Ct):
         parts.append(np.ascontiguousarray(full[:, :, c0:c0 + nl]).ravel())
     src = torch.from_numpy(np.concatenate(parts)).cuda()
     dst = torch.zeros((n_keep, d, Ct), dtype=torch.float64, device="cuda")
-    rc = mcmc_amd.lib().mi_mcmc_merge_shards(C.c_void_p(src.data_ptr()), C.c_uint32(world), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(Ct),
-                                            C.c_void_p(dst.data_ptr()), C.c_void_p(0))
+    rc = mcmc_amd.lib().mi_mcmc_merge_shards(src.data_ptr(), world, n_keep, d, Ct,
+                                            dst.data_ptr(), None)
     assert rc == 0, mcmc_amd.lib().mi_mcmc_last_error().decode()
     torch.cuda.synchronize()
     assert np.array_equal(dst.cpu().numpy(), full)
@@ -51,8 +51,7 @@ def test_allgather_draws_over_an_rccl_communicator_of_one_rank(fn):
     local = torch.randn((n_keep, d, Ct), dtype=torch.float64, device="cuda")
     scratch = torch.zeros(n_keep * d * Ct, dtype=torch.float64, device="cuda")
     out = torch.zeros((n_keep, d, Ct), dtype=torch.float64, device="cuda")
-    rc = getattr(mcmc_amd.lib(), fn)(comm, C.c_uint32(1), C.c_uint32(0), C.c_void_p(local.data_ptr()), C.c_uint64(n_keep), C.c_uint64(d),
-                                               C.c_uint64(Ct), C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(0))
+    rc = getattr(mcmc_amd.lib(), fn)(comm, 1, 0, local.data_ptr(), n_keep, d, Ct, scratch.data_ptr(), out.data_ptr(), None)
     assert rc == 0, mcmc_amd.lib().mi_mcmc_last_error().decode()
     torch.cuda.synchronize()
     assert torch.equal(out, local)
@@ -111,16 +110,15 @@ def test_rank_major_index_addresses_every_chain_of_equal_and_ragged_splits():
     """mi_mcmc_rank_major_index against the layout it documents: shard r packed at n_keep * d * chain0(r) with row length n_local(r)
     (equal shards: [G][n_keep][d][C / G])."""
     lib = mcmc_amd.lib()
-    lib.mi_mcmc_rank_major_index.restype = C.c_uint64
     for Ct, world, n_keep, d in [(16, 4, 3, 2), (13, 4, 2, 3), (5, 8, 2, 2), (9, 1, 2, 2)]:
         full = np.arange(n_keep * d * Ct, dtype=np.float64).reshape(n_keep, d, Ct)
         packed = np.concatenate([np.ascontiguousarray(full[:, :, c0:c0 + nl]).ravel() for c0, nl in (shard_bounds(Ct, world, r) for r in range(world))])
         for i in range(n_keep):
             for j in range(d):
                 for c in range(Ct):
-                    k = lib.mi_mcmc_rank_major_index(C.c_uint64(Ct), C.c_uint32(world), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(i), C.c_uint64(j), C.c_uint64(c))
+                    k = lib.mi_mcmc_rank_major_index(Ct, world, n_keep, d, i, j, c)
                     assert packed[k] == full[i, j, c]
-        assert lib.mi_mcmc_rank_major_index(C.c_uint64(Ct), C.c_uint32(world), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(0), C.c_uint64(0), C.c_uint64(Ct)) == 2 ** 64 - 1
+        assert lib.mi_mcmc_rank_major_index(Ct, world, n_keep, d, 0, 0, Ct) == 2 ** 64 - 1
 
 
 @pytest.mark.gpu
@@ -145,8 +143,8 @@ def test_rank_major_allgather_and_the_overlapped_begin_wait_form_on_one_rank():
     draws = torch.zeros((n_keep, d, Ct), dtype=torch.float64, device="cuda")
     mcmc_amd.run("hmc", t, st_all, mcmc_amd.make_chains(theta, Ct, draws=draws, mem=mcmc_amd.MEM_DEVICE), stream=stream)
     ref = torch.zeros_like(draws)
-    rc = lib.mi_mcmc_allgather_draws_rank_major(comm, C.c_uint32(1), C.c_uint32(0), C.c_void_p(draws.data_ptr()), C.c_uint64(n_keep), C.c_uint64(d),
-                                                C.c_uint64(Ct), C.c_void_p(ref.data_ptr()), C.c_void_p(stream))
+    rc = lib.mi_mcmc_allgather_draws_rank_major(comm, 1, 0, draws.data_ptr(), n_keep, d,
+                                                Ct, ref.data_ptr(), stream)
     assert rc == 0, lib.mi_mcmc_last_error().decode()
     torch.cuda.synchronize()
     assert torch.equal(ref, draws)
@@ -161,18 +159,18 @@ def test_rank_major_allgather_and_the_overlapped_begin_wait_form_on_one_rank():
         slabs.append(slab)
         mcmc_amd.run("hmc", t, s_k, mcmc_amd.make_chains(theta, Ct, draws=slab, mem=mcmc_amd.MEM_DEVICE, draw0=0 if k == 0 else n_burn + bounds[k]), stream=stream)
         h = C.c_void_p(0)
-        rc = lib.mi_mcmc_allgather_draws_begin(comm, C.c_uint32(1), C.c_uint32(0), C.c_void_p(slab.data_ptr()), C.c_uint64(nk), C.c_uint64(d), C.c_uint64(Ct),
-                                               C.c_uint64(bounds[k]), C.c_uint64(n_keep), C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(h))
+        rc = lib.mi_mcmc_allgather_draws_begin(comm, 1, 0, slab.data_ptr(), nk, d, Ct,
+                                               bounds[k], n_keep, out.data_ptr(), stream, C.byref(h))
         assert rc == 0 and h.value, lib.mi_mcmc_last_error().decode()
         handles.append(h)
     for k, h in enumerate(handles):
-        assert lib.mi_mcmc_allgather_draws_wait(h, C.c_void_p(stream), C.c_int(k == 2)) == 0
+        assert lib.mi_mcmc_allgather_draws_wait(h, stream, k == 2) == 0
     torch.cuda.synchronize()
     assert torch.equal(out, draws)
     # a row range outside the run is refused, not gathered somewhere
     h = C.c_void_p(0)
-    assert lib.mi_mcmc_allgather_draws_begin(comm, C.c_uint32(1), C.c_uint32(0), C.c_void_p(draws.data_ptr()), C.c_uint64(4), C.c_uint64(d), C.c_uint64(Ct),
-                                             C.c_uint64(7), C.c_uint64(n_keep), C.c_void_p(out.data_ptr()), C.c_void_p(stream), C.byref(h)) == mcmc_amd.MI_ERR_BAD_ARG
+    assert lib.mi_mcmc_allgather_draws_begin(comm, 1, 0, draws.data_ptr(), 4, d, Ct,
+                                             7, n_keep, out.data_ptr(), stream, C.byref(h)) == mcmc_amd.MI_ERR_BAD_ARG
     rccl.ncclCommDestroy(comm)
 
 

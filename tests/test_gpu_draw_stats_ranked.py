@@ -5,7 +5,6 @@ The function is the rank transform (held to numpy bit for bit by tests/test_gpu_
 EXISTING mi_mcmc_draw_stats on slabs of 2C half-chains.  The normal-score and indicator slabs are bitwise the reference's, so nothing new enters the
 comparison and the tolerances are that reducer's own (tests/test_gpu_draw_stats.py): rtol 1e-10 for the three R-hat, 1e-8 for the two ESS; where
 that file relaxes the ESS (phi >= 0.9 on series beyond 160 draws: the device sums 128 lags) the same relaxation applies to half-chains beyond 160."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -67,15 +66,13 @@ def test_dimensions_processed_in_three_groups(n, d, C_, phi):
     count depends on the d it is called with, so bits may differ from the one-group call; values may not."""
     x, want = _case(n, d, C_, phi)
     lib = mcmc_amd.lib()
-    lib.mi_mcmc_test_rank_dim_bytes.restype = C.c_uint64
-    lib.mi_mcmc_test_rank_dims_per_group.restype = C.c_uint64
     try:
-        b = lib.mi_mcmc_test_rank_dim_bytes(C.c_uint64(n), C.c_uint64(C_), C.c_uint32(1), C.c_int(1))
-        lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(2 * b))
-        assert lib.mi_mcmc_test_rank_dims_per_group(C.c_uint64(n), C.c_uint64(d), C.c_uint64(C_), C.c_uint32(1), C.c_int(1)) == 2
+        b = lib.mi_mcmc_test_rank_dim_bytes(n, C_, 1, 1)
+        lib.mi_mcmc_test_set_rank_ws_bytes(2 * b)
+        assert lib.mi_mcmc_test_rank_dims_per_group(n, d, C_, 1, 1) == 2
         got = mcmc_amd.draw_stats_ranked(x)
     finally:
-        lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(0))
+        lib.mi_mcmc_test_set_rank_ws_bytes(0)
     _agree(got, want, n // 2, phi)
 
 

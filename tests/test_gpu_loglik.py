@@ -155,17 +155,16 @@ def test_several_sort_groups_give_the_bits_of_one(layout):
     ref = _reference(shape)
     mat = _matrix(shape)
     lib = mcmc_amd.lib()
-    lib.mi_mcmc_test_rank_dim_bytes.restype = C.c_uint64
     assert mcmc_amd.test_loglik_plan(layout, *shape)["sort_groups"] == 1
     _both(mat, layout, ref, "one group")
-    b = lib.mi_mcmc_test_rank_dim_bytes(C.c_uint64(1), C.c_uint64(100), C.c_uint32(0), C.c_int(0))
+    b = lib.mi_mcmc_test_rank_dim_bytes(1, 100, 0, 0)
     try:
-        lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(128 * b + 17))
+        lib.mi_mcmc_test_set_rank_ws_bytes(128 * b + 17)
         plan = mcmc_amd.test_loglik_plan(layout, *shape)
         assert (plan["sort_rows"], plan["sort_groups"]) == (128, 3)                           # 128 + 128 + 44
         res = mcmc_amd.loglik_psis_loo(_laid_out(mat, layout), layout)
     finally:
-        lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(0))
+        lib.mi_mcmc_test_set_rank_ws_bytes(0)
     _assert_psis(res, ref, "128 + 128 + 44")
 
 

@@ -146,7 +146,7 @@ def test_device_memory():
     r.initial_vals, r.draws, r.final_states = iv.data_ptr(), draws.data_ptr(), fin.data_ptr()
     r.n_accept, r.n_ee_accept = acc.data_ptr(), ee.data_ptr()
     st = torch.cuda.current_stream(dev).cuda_stream
-    assert mcmc_amd.lib().mi_mcmc_aees_run(C.byref(t), C.byref(s), C.byref(a), C.byref(r), C.c_void_p(st)) == 0
+    assert mcmc_amd.lib().mi_mcmc_aees_run(C.byref(t), C.byref(s), C.byref(a), C.byref(r), st) == 0
     torch.cuda.synchronize()
     assert np.array_equal(draws.cpu().numpy(), ref) and np.array_equal(fin.cpu().numpy(), iref["final_states"])
     assert np.array_equal(acc.cpu().numpy().astype(np.uint64), iref["n_accept"])

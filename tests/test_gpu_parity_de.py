@@ -154,7 +154,7 @@ def test_device_memory():
     p.struct_size, p.mem, p.n_populations = C.sizeof(mcmc_amd.mi_populations), mcmc_amd.MEM_DEVICE, P
     p.initial_vals, p.population, p.draws, p.n_accept = iv.data_ptr(), pop.data_ptr(), draws.data_ptr(), acc.data_ptr()
     st = torch.cuda.current_stream(dev).cuda_stream
-    assert mcmc_amd.lib().mi_mcmc_de_run(C.byref(t), C.byref(s), C.byref(ds), C.byref(p), C.c_void_p(st)) == 0
+    assert mcmc_amd.lib().mi_mcmc_de_run(C.byref(t), C.byref(s), C.byref(ds), C.byref(p), st) == 0
     torch.cuda.synchronize()
     assert np.array_equal(draws.cpu().numpy(), ref) and np.array_equal(pop.cpu().numpy(), iref["population"])
     assert np.array_equal(acc.cpu().numpy().astype(np.uint64), iref["n_accept"])

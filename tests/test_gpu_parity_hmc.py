@@ -60,6 +60,14 @@ def test_device_rng_matches_oracle_bitwise():
         assert mcmc_amd.probe_uniform(*args) == orc.uniform(*args)
 
 
+def test_throughput_probes_return_their_figures():
+    """probe_fp64_peak / probe_mfma_cycles (tools' measurements) at a few iterations: the status and the kind of what comes back, no figure"""
+    for use_mfma in (0, 1):
+        assert isinstance(mcmc_amd.probe_fp64_peak(use_mfma, iters=4), float)
+    cyc, tf = mcmc_amd.probe_mfma_cycles(1, 0, iters=4)
+    assert isinstance(cyc, float) and isinstance(tf, float)
+
+
 def _oracle_many(kind_orc, d, init, st, prec=None, chain0=0):
     t = orc.TargetSpec(kind_orc, d, prec=prec, W=4)
     s = orc.make_settings(seed=int(st.rng_seed_value), n_burnin=int(st.n_burnin_draws),

@@ -173,13 +173,11 @@ def test_non_finite_samples(what, flags):
 
 
 def _set_budget(b):
-    mcmc_amd.lib().mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(b))
+    mcmc_amd.lib().mi_mcmc_test_set_rank_ws_bytes(b)
 
 
 def _dim_bytes(n_keep, C_, flags):
-    f = mcmc_amd.lib().mi_mcmc_test_rank_dim_bytes
-    f.restype = C.c_uint64
-    return f(C.c_uint64(n_keep), C.c_uint64(C_), C.c_uint32(flags), C.c_int(0))
+    return mcmc_amd.lib().mi_mcmc_test_rank_dim_bytes(n_keep, C_, flags, 0)
 
 
 @pytest.mark.parametrize("flags", FLAGS, ids=lambda f: _FLAG_ID[f])
@@ -189,10 +187,9 @@ def test_dimensions_processed_in_three_groups(flags):
     slab = _slab(shape)
     whole = [_check(slab, what, split, fold) for what in WHATS]
     f = mcmc_amd.lib().mi_mcmc_test_rank_dims_per_group
-    f.restype = C.c_uint64
     try:
         _set_budget(2 * _dim_bytes(7, 45, int(split) | 2 * int(fold)))
-        assert f(C.c_uint64(7), C.c_uint64(5), C.c_uint64(45), C.c_uint32(int(split) | 2 * int(fold)), C.c_int(0)) == 2     # groups of 2, 2, 1
+        assert f(7, 5, 45, int(split) | 2 * int(fold), 0) == 2     # groups of 2, 2, 1
         for what, w in zip(WHATS, whole):
             assert _same(mcmc_amd.draws_rank_transform(slab, what, split=split, fold=fold), w)
     finally:

@@ -2,7 +2,6 @@
 before any device call, in the order include/mi_mcmc.h states; the smallest K of each entry passes the checks as far as the device probe; and the plan of
 a call (draws_loglik.hpp: chunks, fold grid, tail, sort groups, tail route, workspace) is the stated function of the shape, of where the matrix lives
 and of the two budgets."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -28,9 +27,9 @@ def _rc(entry, mat=_MAT.ctypes.data, layout=ROWS, n_rows=5, n_keep=1, n_chains=2
     outs = (True,) * n_out if outs is None else outs
     assert len(outs) == n_out
     assert n_rows <= _OUT[0].size or n_rows > 1 << 20     # the outputs hold what a call that runs writes; the larger calls are refused before they write
-    ptrs = [C.c_void_p(a.ctypes.data if on else None) for a, on in zip(_OUT, outs)]
+    ptrs = [a.ctypes.data if on else None for a, on in zip(_OUT, outs)]
     fn = mcmc_amd.lib().mi_mcmc_loglik_waic if entry == "waic" else mcmc_amd.lib().mi_mcmc_loglik_psis_loo
-    return fn(C.c_void_p(mat), C.c_int32(layout), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_rows), C.c_uint64(n_keep), C.c_uint64(n_chains), *ptrs, C.c_void_p(0))
+    return fn(mat, layout, mcmc_amd.MEM_HOST, n_rows, n_keep, n_chains, *ptrs, None)
 
 
 def _none(entry):
@@ -170,21 +169,20 @@ def test_the_measured_shape():
 
 def test_the_sort_groups_follow_the_rank_budget():
     lib = mcmc_amd.lib()
-    lib.mi_mcmc_test_rank_dim_bytes.restype = C.c_uint64
     n_rows, n_keep, C_ = 300, 2, 50
     try:
         for layout in (ROWS, SLAB):
             shape = (1, n_keep * C_) if layout == ROWS else (n_keep, C_)       # the slab the sorter sees
-            b = lib.mi_mcmc_test_rank_dim_bytes(C.c_uint64(shape[0]), C.c_uint64(shape[1]), C.c_uint32(0), C.c_int(0))
+            b = lib.mi_mcmc_test_rank_dim_bytes(shape[0], shape[1], 0, 0)
             assert b == 16 * 100 + 1024 + 8192
             assert mcmc_amd.test_loglik_plan(layout, n_rows, n_keep, C_)["sort_groups"] == 1
             for budget, rows in ((128 * b, 128), (129 * b - 1, 128), (129 * b, 129), (1, 1), (300 * b, 300)):
-                lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(budget))
+                lib.mi_mcmc_test_set_rank_ws_bytes(budget)
                 p = mcmc_amd.test_loglik_plan(layout, n_rows, n_keep, C_)
                 assert (p["sort_rows"], p["sort_groups"]) == (rows, _ceil(n_rows, rows)), (layout, budget, p)
-            lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(0))
+            lib.mi_mcmc_test_set_rank_ws_bytes(0)
     finally:
-        lib.mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(0))
+        lib.mi_mcmc_test_set_rank_ws_bytes(0)
 
 
 def test_the_tail_route_on_both_sides_of_the_lds_capacity():

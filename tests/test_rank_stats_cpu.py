@@ -9,7 +9,6 @@ norm_ppf is AS 241 PPND16 with CPython's coefficients and nesting, so statistics
    2.61e-16 (1.17 eps; 5 in 10 000 points differ at all).  The test asserts 8 x that: the grid is a sample, the margin covers the points between.
  * independently of CPython, 0.5 erfc(-z / sqrt 2) returns to p within 4 ulp(p) + 1e-16 for p >= 1e-300 (measured worst: 0.71 of that bound, and
    the same 0.71 for CPython's own function)."""
-import ctypes as C
 import math
 import statistics
 
@@ -173,14 +172,14 @@ _D5 = [np.zeros(3) for _ in range(5)]
 
 
 def _rc_transform(slab=_X.ctypes.data, n_keep=4, d=3, n_chains=5, what=1, flags=0, out=_OUT.ctypes.data):
-    return mcmc_amd.lib().mi_mcmc_draws_rank_transform(C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                                       C.c_int32(what), C.c_uint32(flags), C.c_void_p(out), C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draws_rank_transform(slab, mcmc_amd.MEM_HOST, n_keep, d, n_chains,
+                                                       what, flags, out, None)
 
 
 def _rc_stats(slab=_X.ctypes.data, n_keep=4, d=3, n_chains=5, outs=None):
     outs = [o.ctypes.data for o in _D5] if outs is None else outs
-    return mcmc_amd.lib().mi_mcmc_draw_stats_ranked(C.c_void_p(slab), C.c_int32(mcmc_amd.MEM_HOST), C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(n_chains),
-                                                    *[C.c_void_p(o) for o in outs], C.c_void_p(0))
+    return mcmc_amd.lib().mi_mcmc_draw_stats_ranked(slab, mcmc_amd.MEM_HOST, n_keep, d, n_chains,
+                                                    *[o for o in outs], None)
 
 
 _SHARED = {"null_slab": (dict(slab=None), "slab"), "d_is_0": (dict(d=0), "d "), "d_past_65536": (dict(d=65537), "d = 65537"),
@@ -228,19 +227,15 @@ def test_front_ends_raise_and_the_entries_are_exported():
 # ---- the group rule (draws_rank.hpp), as host arithmetic
 
 def _dim_bytes(n_keep, C_, flags, stats):
-    f = mcmc_amd.lib().mi_mcmc_test_rank_dim_bytes
-    f.restype = C.c_uint64
-    return f(C.c_uint64(n_keep), C.c_uint64(C_), C.c_uint32(flags), C.c_int(stats))
+    return mcmc_amd.lib().mi_mcmc_test_rank_dim_bytes(n_keep, C_, flags, stats)
 
 
 def _dims_per_group(n_keep, d, C_, flags, stats):
-    f = mcmc_amd.lib().mi_mcmc_test_rank_dims_per_group
-    f.restype = C.c_uint64
-    return f(C.c_uint64(n_keep), C.c_uint64(d), C.c_uint64(C_), C.c_uint32(flags), C.c_int(stats))
+    return mcmc_amd.lib().mi_mcmc_test_rank_dims_per_group(n_keep, d, C_, flags, stats)
 
 
 def _set_budget(b):
-    mcmc_amd.lib().mi_mcmc_test_set_rank_ws_bytes(C.c_uint64(b))
+    mcmc_amd.lib().mi_mcmc_test_set_rank_ws_bytes(b)
 
 
 def test_the_group_rule():

@@ -76,7 +76,7 @@ def run(case, P, ee_override=None):
     r = mcmc_amd.mi_aees_runs()
     r.struct_size, r.mem, r.n_runs = C.sizeof(mcmc_amd.mi_aees_runs), mcmc_amd.MEM_DEVICE, P
     r.initial_vals, r.draws, r.final_states, r.n_accept, r.n_ee_accept = iv.data_ptr(), draws.data_ptr(), fin.data_ptr(), acc.data_ptr(), eea.data_ptr()
-    fn = lambda: mcmc_amd._check(mcmc_amd.lib().mi_mcmc_aees_run(C.byref(t), C.byref(s), C.byref(ae), C.byref(r), C.c_void_p(stream)))
+    fn = lambda: mcmc_amd._check(mcmc_amd.lib().mi_mcmc_aees_run(C.byref(t), C.byref(s), C.byref(ae), C.byref(r), stream))
     fn(); torch.cuda.synchronize()                     # first call: workspace, code objects
     ms = timed(fn)
     level_steps = P * sum(n_total - (k * S + 1 if k else 0) for k in range(K))     # active level-steps (level k: draws n > k S)

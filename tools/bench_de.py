@@ -46,7 +46,7 @@ def run_de(hint, burn, keep):
     p = mcmc_amd.mi_populations()
     p.struct_size, p.mem, p.n_populations = C.sizeof(mcmc_amd.mi_populations), mcmc_amd.MEM_DEVICE, P
     p.initial_vals, p.population, p.draws, p.n_accept = init.data_ptr(), pop.data_ptr(), draws.data_ptr(), acc.data_ptr()
-    fn = lambda: mcmc_amd._check(mcmc_amd.lib().mi_mcmc_de_run(C.byref(t), C.byref(s), C.byref(ds), C.byref(p), C.c_void_p(stream)))
+    fn = lambda: mcmc_amd._check(mcmc_amd.lib().mi_mcmc_de_run(C.byref(t), C.byref(s), C.byref(ds), C.byref(p), stream))
     fn(); torch.cuda.synchronize()                    # first call: workspace, code objects
     ms = timed(fn)
     gens = burn + keep

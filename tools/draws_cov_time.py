@@ -40,8 +40,8 @@ for shp in args.shapes.split(","):
     slab = torch.randn((n_keep, d, C), dtype=torch.float64, device="cuda", generator=g) + torch.linspace(-10, 10, d, dtype=torch.float64, device="cuda")[None, :, None]
     mean_t, cov_t = torch.empty(d, dtype=torch.float64).pin_memory(), torch.empty((d, d), dtype=torch.float64).pin_memory()     # the caller's host arrays: pinned
     def call():
-        rc = mcmc_amd.lib().mi_mcmc_draws_covariance(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                                     C_.c_void_p(mean_t.data_ptr()), C_.c_void_p(cov_t.data_ptr()), C_.c_void_p(stream))
+        rc = mcmc_amd.lib().mi_mcmc_draws_covariance(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                                     mean_t.data_ptr(), cov_t.data_ptr(), stream)
         assert rc == 0, mcmc_amd.lib().mi_mcmc_last_error()
     ms, ts = median_ms(call)
     t_hbm, t_mfma = 8.0 * d * K / HBM, float(d) * d * K / PEAK

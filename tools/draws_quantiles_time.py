@@ -44,16 +44,16 @@ for shp in args.shapes.split(","):
         ranks_a = np.array(ranks, dtype=np.uint64)
         out_t = torch.empty((n_ranks, d), dtype=torch.float64).pin_memory()
         def call():
-            rc = lib.mi_mcmc_draws_order_stats(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                               C_.c_void_p(ranks_a.ctypes.data), C_.c_uint32(n_ranks), C_.c_void_p(out_t.data_ptr()), C_.c_void_p(stream))
+            rc = lib.mi_mcmc_draws_order_stats(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                               ranks_a.ctypes.data, n_ranks, out_t.data_ptr(), stream)
             assert rc == 0, lib.mi_mcmc_last_error()
         ms, lo, hi = timed(call)
         rate = nbytes / (ms * 1e-3)
         say(f"  draws_order_stats, {n_ranks:2d} ranks: {ms:.3f} ms ({lo:.3f} .. {hi:.3f}); {rate / 1e12:.3f} TB/s effective = {rate / HBM:.3f} of peak")
     mean_t, rhat_t, ess_t = (torch.empty(d, dtype=torch.float64).pin_memory() for _ in range(3))
     def stats():
-        rc = lib.mi_mcmc_draw_stats(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                    C_.c_void_p(mean_t.data_ptr()), C_.c_void_p(0), C_.c_void_p(rhat_t.data_ptr()), C_.c_void_p(ess_t.data_ptr()), C_.c_void_p(stream))
+        rc = lib.mi_mcmc_draw_stats(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                    mean_t.data_ptr(), None, rhat_t.data_ptr(), ess_t.data_ptr(), stream)
         assert rc == 0, lib.mi_mcmc_last_error()
     try:
         ms, lo, hi = timed(stats)

@@ -52,8 +52,8 @@ for shp in args.shapes.split(","):
         n = float(d) * rows * C
         out = torch.empty((h, d, 2 * C) if flags & 1 else (n_keep, d, C), dtype=torch.float64, device="cuda")
         def call():
-            rc = lib.mi_mcmc_draws_rank_transform(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                                  C_.c_int32(1), C_.c_uint32(flags), C_.c_void_p(out.data_ptr()), C_.c_void_p(stream))
+            rc = lib.mi_mcmc_draws_rank_transform(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                                  1, flags, out.data_ptr(), stream)
             assert rc == 0, lib.mi_mcmc_last_error()
         ms, lo, hi = timed(call)
         s0, p0 = counts(); call(); s1, p1 = counts()
@@ -64,16 +64,16 @@ for shp in args.shapes.split(","):
         del out
     outs = [torch.empty(d, dtype=torch.float64).pin_memory() for _ in range(5)]
     def ranked():
-        rc = lib.mi_mcmc_draw_stats_ranked(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                           *[C_.c_void_p(o.data_ptr()) for o in outs], C_.c_void_p(stream))
+        rc = lib.mi_mcmc_draw_stats_ranked(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                           *[o.data_ptr() for o in outs], stream)
         assert rc == 0, lib.mi_mcmc_last_error()
     ms_r, lo, hi = timed(ranked)
     say(f"  draw_stats_ranked (all five outputs: two sorts, two lookups, two indicator slabs, four passes of draw_stats): {ms_r:.3f} ms ({lo:.3f} .. {hi:.3f})")
     say(f"    rhat max {outs[0].max().item():.5f}, ess_bulk per half-chain min {outs[3].min().item():.2f} of {h}, ess_tail min {outs[4].min().item():.2f}")
     mean_t, rhat_t, ess_t = (torch.empty(d, dtype=torch.float64).pin_memory() for _ in range(3))
     def stats():
-        rc = lib.mi_mcmc_draw_stats(C_.c_void_p(slab.data_ptr()), C_.c_int32(mcmc_amd.MEM_DEVICE), C_.c_uint64(n_keep), C_.c_uint64(d), C_.c_uint64(C),
-                                    C_.c_void_p(mean_t.data_ptr()), C_.c_void_p(0), C_.c_void_p(rhat_t.data_ptr()), C_.c_void_p(ess_t.data_ptr()), C_.c_void_p(stream))
+        rc = lib.mi_mcmc_draw_stats(slab.data_ptr(), mcmc_amd.MEM_DEVICE, n_keep, d, C,
+                                    mean_t.data_ptr(), None, rhat_t.data_ptr(), ess_t.data_ptr(), stream)
         assert rc == 0, lib.mi_mcmc_last_error()
     ms, lo, hi = timed(stats)
     say(f"  context: mi_mcmc_draw_stats (no acov) on the same slab: {ms:.3f} ms ({lo:.3f} .. {hi:.3f})")
