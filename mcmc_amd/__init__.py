@@ -583,16 +583,40 @@ def probe_mfma(A, B, Cin):
     return D
 
 
-def probe_math(fn, x):
+def probe_math(fn, x, kc2=False):
+    """fn 0..5: exp, log, sincos2pi (sin, cos), softplus, sigmoid, norm_ppf on the device; kc2: from the unit built with MI_KC_MODE 2 (probes_kc2.hip)"""
     x = np.ascontiguousarray(x, dtype=np.float64)
     o1, o2 = np.empty_like(x), np.empty_like(x)
-    _check(probes_lib().mi_probe_math(fn, x.ctypes.data, x.size, o1.ctypes.data, o2.ctypes.data))
+    f = probes_lib().mi_probe_math_kc2 if kc2 else probes_lib().mi_probe_math
+    _check(f(fn, x.ctypes.data, x.size, o1.ctypes.data, o2.ctypes.data))
     return o1, o2
+
+
+def probe_math2(fn, x, y, kc2=False):
+    """fn 0: det_pow(x, y) on the device, elementwise over two arrays of one shape"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if x.shape != y.shape:
+        raise ValueError(f"probe_math2: x {x.shape} and y {y.shape} differ in shape")
+    out = np.empty_like(x)
+    f = probes_lib().mi_probe_math2_kc2 if kc2 else probes_lib().mi_probe_math2
+    _check(f(fn, x.ctypes.data, y.ctypes.data, x.size, out.ctypes.data))
+    return out
 
 
 def probe_normals(seed, chain, draw, stream, d):
     out = np.zeros(d)
     _check(probes_lib().mi_probe_normals(seed, chain, draw, stream, d, out.ctypes.data))
+    return out
+
+
+def probe_normals_variant(variant, seed, chain, draw, stream, d, kc2=False):
+    """the same d normals through variant 0 rng_normal_pair, 1 rng_normal_pair_at, 2 rng_normal_two_pairs, 3 rng_normal_four_pairs"""
+    out = np.zeros(d)
+    if kc2:
+        _check(probes_lib().mi_probe_normals_kc2(variant, seed, chain, draw, stream, d, out.ctypes.data))
+    else:
+        _check(probes_lib().mi_probe_normals_variant(variant, seed, chain, draw, stream, d, out.ctypes.data))
     return out
 
 

@@ -136,7 +136,12 @@ PROTOTYPES = {
     # mcmc_amd/csrc/mi_mcmc_probes.h: the probes (their own library) ...
     "mi_probe_mfma_f64": (_i, [_p, _p, _p, _p]),
     "mi_probe_math": (_i, [_i, _p, _u64, _p, _p]),
+    "mi_probe_math2": (_i, [_i, _p, _p, _u64, _p]),
     "mi_probe_normals": (_i, [_u64, _u64, _u32, _u32, _u64, _p]),
+    "mi_probe_normals_variant": (_i, [_i, _u64, _u64, _u32, _u32, _u64, _p]),
+    "mi_probe_math_kc2": (_i, [_i, _p, _u64, _p, _p]),
+    "mi_probe_math2_kc2": (_i, [_i, _p, _p, _u64, _p]),
+    "mi_probe_normals_kc2": (_i, [_i, _u64, _u64, _u32, _u32, _u64, _p]),
     "mi_probe_uniform": (_i, [_u64, _u64, _u32, _u32, _p]),
     "mi_probe_fp64_peak": (_i, [_i, _i, _p]),
     "mi_probe_mfma_cycles": (_i, [_i, _i, _i, _p, _p]),

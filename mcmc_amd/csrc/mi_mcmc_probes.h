@@ -1,5 +1,5 @@
-/* mi_mcmc_probes.h -- TEST / MEASUREMENT infrastructure, not part of the product: the diagnostics of libmi_mcmc_probes.so (probes.hip;
- * built next to libmi_mcmc.so and linked against it): one MFMA tile, the deterministic math functions, the per-chain RNG, fp64
+/* mi_mcmc_probes.h -- TEST / MEASUREMENT infrastructure, not part of the product: the diagnostics of libmi_mcmc_probes.so (probes.hip,
+ * probes_kc2.hip; built next to libmi_mcmc.so and linked against it): one MFMA tile, the deterministic math functions, the per-chain RNG, fp64
  * throughput ceilings.  Host pointers, blocking; status codes and mi_mcmc_last_error() as in mi_mcmc.h. */
 #pragma once
 #include <stdint.h>
@@ -7,8 +7,18 @@
 extern "C" {
 #endif
 int mi_probe_mfma_f64(const double* A16x4, const double* B4x16, const double* C16x16, double* D16x16);
+/* fn: 0 exp, 1 log, 2 sincos2pi of x in [0, 1) (out = sin, out2 = cos), 3 softplus, 4 sigmoid, 5 norm_ppf; out2 is 0 for every fn but 2 */
 int mi_probe_math(int fn, const double* x, uint64_t n, double* out, double* out2);
+/* two operands; fn: 0 det_pow(x, y) */
+int mi_probe_math2(int fn, const double* x, const double* y, uint64_t n, double* out);
 int mi_probe_normals(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out);
+/* the d normals of one (chain, draw) in the canonical dimension <-> slot map through variant 0 rng_normal_pair (= mi_probe_normals), 1 rng_normal_pair_at,
+ * 2 rng_normal_two_pairs, 3 rng_normal_four_pairs; d <= 2^24 */
+int mi_probe_normals_variant(int variant, uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out);
+/* probes_kc2.hip: the three above from a translation unit that builds det_math.hpp with MI_KC_MODE 2 and MI_RNG_NOINLINE, as the logistic kernels do */
+int mi_probe_math_kc2(int fn, const double* x, uint64_t n, double* out, double* out2);
+int mi_probe_math2_kc2(int fn, const double* x, const double* y, uint64_t n, double* out);
+int mi_probe_normals_kc2(int variant, uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out);
 int mi_probe_uniform(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t slot, double* out);
 int mi_probe_fp64_peak(int use_mfma, int iters, double* tflops_out);
 int mi_probe_mfma_cycles(int waves_per_simd, int use_lds, int iters, double* cycles_per_mfma, double* tflops_out);

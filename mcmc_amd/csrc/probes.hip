@@ -8,6 +8,7 @@
 #include "mi_mcmc_probes.h"
 #include "det_math.hpp"
 #include "hmc_dense.hpp"
+#include "probe_kernels.hpp"
 
 using mi::host::fail;
 using mi::host::DevBuf;
@@ -24,36 +25,6 @@ __global__ void probe_mfma_kernel(const double* A, const double* B, const double
     for (int r = 0; r < 4; ++r) c[r] = Cin[((l >> 4) + 4 * r) * 16 + (l & 15)];
     c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
     for (int r = 0; r < 4; ++r) D[((l >> 4) + 4 * r) * 16 + (l & 15)] = c[r];
-}
-
-__global__ void probe_math_kernel(int fn, const double* x, uint64_t n, double* out, double* out2)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0, c = 0.0;
-    switch (fn) {
-    case 0: s = mi::det_exp(x[i]); break;
-    case 1: s = mi::det_log(x[i]); break;
-    case 2: mi::det_sincos2pi(x[i], s, c); break;
-    case 3: s = mi::softplus(x[i]); break;
-    case 4: s = mi::sigmoid(x[i]); break;
-    default: s = __builtin_nan("");
-    }
-    out[i] = s;
-    out2[i] = c;
-}
-
-__global__ void probe_normals_kernel(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out)
-{
-    const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t nslots = 4 * ((d + 7) / 8);
-    if (slot >= nslots) return;
-    const uint64_t b = slot / 4, j = slot % 4;
-    const uint64_t i0 = 8 * b + j, i1 = i0 + 4;
-    double z0, z1;
-    mi::rng_normal_pair(seed, chain, draw, (uint32_t)slot, stream, z0, z1);
-    if (i0 < d) out[i0] = z0;
-    if (i1 < d) out[i1] = z1;
 }
 
 __global__ void probe_uniform_kernel(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t slot, double* out)
@@ -134,29 +105,21 @@ int mi_probe_mfma_f64(const double* A, const double* B, const double* Cin, doubl
     return MI_OK;
 }
 
-int mi_probe_math(int fn, const double* x, uint64_t n, double* out, double* out2)
-{
-    if (!x || !out || !out2) return fail(MI_ERR_BAD_ARG, "null buffer");
-    DevBuf dx, d1, d2;
-    HIP_TRY(dx.alloc(n * 8)); HIP_TRY(d1.alloc(n * 8)); HIP_TRY(d2.alloc(n * 8));
-    HIP_TRY(hipMemcpy(dx.p, x, n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(probe_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, dx.as<double>(), n, d1.as<double>(), d2.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d1.p, n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out2, d2.p, n * 8, hipMemcpyDeviceToHost));
-    return MI_OK;
-}
+// fn 0..5: exp, log, sincos2pi, softplus, sigmoid, norm_ppf (probe_kernels.hpp)
+int mi_probe_math(int fn, const double* x, uint64_t n, double* out, double* out2) { return mi::probe::run_math<MI_KC_MODE>(fn, x, n, out, out2); }
+
+// fn 0: det_pow(x, y)
+int mi_probe_math2(int fn, const double* x, const double* y, uint64_t n, double* out) { return mi::probe::run_math2<MI_KC_MODE>(fn, x, y, n, out); }
 
 int mi_probe_normals(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out)
 {
-    if (!out || d == 0) return fail(MI_ERR_BAD_ARG, "bad args");
-    DevBuf o;
-    HIP_TRY(o.alloc(d * 8));
-    const uint64_t nslots = 4 * ((d + 7) / 8);
-    hipLaunchKernelGGL(probe_normals_kernel, dim3((unsigned)((nslots + 63) / 64)), dim3(64), 0, 0, seed, chain, draw, stream, d, o.as<double>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, o.p, d * 8, hipMemcpyDeviceToHost));
-    return MI_OK;
+    return mi::probe::run_normals<MI_KC_MODE>(0, seed, chain, draw, stream, d, out);
+}
+
+// variant 0..3: rng_normal_pair, rng_normal_pair_at, rng_normal_two_pairs, rng_normal_four_pairs
+int mi_probe_normals_variant(int variant, uint64_t seed, uint64_t chain, uint32_t draw, uint32_t stream, uint64_t d, double* out)
+{
+    return mi::probe::run_normals<MI_KC_MODE>(variant, seed, chain, draw, stream, d, out);
 }
 
 int mi_probe_uniform(uint64_t seed, uint64_t chain, uint32_t draw, uint32_t slot, double* out)

@@ -1599,6 +1599,7 @@ int orc_run_many(int algo, const orc_target* tgt, const orc_settings* s, size_t 
 
 /* ------------------------------------------------------------------ unit-test exports */
 
+/* fn: 0 exp, 1 log, 2 sincos2pi (out = sin, out2 = cos), 3 softplus, 4 sigmoid, 5 norm_ppf, 6 pow(x, y) with y READ from out2 (left as it is) */
 void orc_math_eval(int fn, const double* x, size_t n, double* out, double* out2)
 {
     for (size_t i = 0; i < n; ++i) {
@@ -1608,6 +1609,8 @@ void orc_math_eval(int fn, const double* x, size_t n, double* out, double* out2)
         case 2: orc_sincos2pi(x[i], &out[i], &out2[i]); break;
         case 3: out[i] = orc_softplus(x[i]); break;
         case 4: out[i] = orc_sigmoid(x[i]); break;
+        case 5: out[i] = orc_norm_ppf(x[i]); break;
+        case 6: out[i] = orc_pow(x[i], out2[i]); break;
         default: out[i] = NAN;
         }
     }

@@ -110,6 +110,50 @@ static inline double orc_log(double x)
  * /root/reference/src/nuts.cpp:299 and nuts.ipp:74). */
 static inline double orc_pow(double x, double y) { return orc_exp(y * orc_log(x)); }
 
+/* ---------------------------------------------------------------- standard normal quantile
+ * Wichura, Algorithm AS 241 (Appl. Statist. 37 (1988) 477-484), routine PPND16: three
+ * rational functions of degree 7.  Centre |p - 1/2| <= 0.425 in r = 0.180625 - q^2;
+ * tails in r = sqrt(-log(min(p, 1 - p))), one pair for r <= 5 (shifted by 1.6) and one
+ * beyond (shifted by 5).  Each polynomial is a Horner chain of one rounded multiply and
+ * one rounded add per coefficient (no fma), highest degree first; the logarithm is
+ * orc_log.  p <= 0 gives -inf, p >= 1 gives +inf, NaN gives NaN. */
+static inline double orc_horner7(const double c[8], double r)
+{
+    double v = c[7];
+    for (int i = 6; i >= 0; --i) v = v * r + c[i];
+    return v;
+}
+
+static inline double orc_norm_ppf(double p)
+{
+    /* coefficients in ascending degree: a/b centre, c/d intermediate tail, e/f far tail */
+    static const double a[8] = { 3.3871328727963666080e+0, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
+                                 4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3 };
+    static const double b[8] = { 1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3,
+                                 2.1213794301586595867e+4, 3.9307895800092710610e+4, 2.8729085735721942674e+4, 5.2264952788528545610e+3 };
+    static const double c[8] = { 1.42343711074968357734e+0, 4.63033784615654529590e+0, 5.76949722146069140550e+0, 3.64784832476320460504e+0,
+                                 1.27045825245236838258e+0, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4 };
+    static const double d[8] = { 1.0, 2.05319162663775882187e+0, 1.67638483018380384940e+0, 6.89767334985100004550e-1,
+                                 1.48103976427480074590e-1, 1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9 };
+    static const double e[8] = { 6.65790464350110377720e+0, 5.46378491116411436990e+0, 1.78482653991729133580e+0, 2.96560571828504891230e-1,
+                                 2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7 };
+    static const double f[8] = { 1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2,
+                                 7.86869131145613259100e-4, 1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15 };
+    if (p != p) return p;
+    if (p <= 0.0) return -INFINITY;
+    if (p >= 1.0) return INFINITY;
+    const double q = p - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        return (orc_horner7(a, r) * q) / orc_horner7(b, r);
+    }
+    double r = sqrt(-orc_log(q <= 0.0 ? p : 1.0 - p));
+    double x;
+    if (r <= 5.0) { r = r - 1.6; x = orc_horner7(c, r) / orc_horner7(d, r); }
+    else          { r = r - 5.0; x = orc_horner7(e, r) / orc_horner7(f, r); }
+    return q < 0.0 ? -x : x;
+}
+
 /* ---------------------------------------------------------------- sincos(2 pi u), u in [0,1)
  * octant q = floor(8u), t = 8u - q; odd octants are reflected (t -> 1-t); the
  * reduced angle a = t*pi/4 in [0, pi/4] goes through Taylor polynomials. */

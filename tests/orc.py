@@ -153,10 +153,12 @@ def run_many(algo, target, init, settings, chain0=0, n_threads=0, want_draws=Tru
     return draws, dict(n_accept=nacc, n_leap=nleap, eps=eps)
 
 
-def math_eval(fn, x):
+def math_eval(fn, x, y=None):
+    """fn 0..5: exp, log, sincos2pi (sin, cos), softplus, sigmoid, norm_ppf of x; fn 6: pow(x, y).  Returns (out, out2); out2 is cos for fn 2, y for fn 6."""
     x = _f64(x)
     out = np.empty_like(x)
-    out2 = np.empty_like(x)
+    out2 = np.zeros_like(x) if y is None else np.array(y, dtype=np.float64).reshape(x.shape)
+    assert (fn == 6) == (y is not None), "fn 6 (pow) alone takes a second operand"
     lib().orc_math_eval(fn, _p(x), C.c_size_t(x.size), _p(out), _p(out2))
     return out, out2
 
