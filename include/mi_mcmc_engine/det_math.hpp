@@ -240,13 +240,23 @@ struct u32x4 { uint32_t x, y, z, w; };
 
 MI_HD uint32_t mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
 
+// a ^ b ^ c: on the device one three-input bit operation (v_bitop3_b32, truth table 0x96) where the compiler left two xors
+MI_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 MI_HD u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1)
 {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         // one 32x32->64 product per multiplier (a single v_mad_u64_u32 on the device) instead of a mul_hi and a mul_lo
         const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = u32x4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
+        c = u32x4{xor3((uint32_t)(p1 >> 32), c.y, k0), (uint32_t)p1, xor3((uint32_t)(p0 >> 32), c.w, k1), (uint32_t)p0};
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }

@@ -308,7 +308,8 @@ __device__ MI_BOX_INLINE double box_log_jacobian_term(double v, int bt, double l
 }
 
 // WPB = waves per workgroup: 4 (one wave per SIMD, 512-register budget) or 8 (two waves per SIMD,
-// 256 registers each: one wave's VALU phases -- kick/drift, RNG, accept -- hide under the other's MFMAs).
+// 256 registers each: meant to hide one wave's VALU phases -- kick/drift, RNG, accept -- under the other's MFMAs; the counters say
+// that matrix and vector time add up instead).
 // BOUNDED (the general variant): settings.vals_bound and / or a diagonal precond_mat.
 // vals_bound (hmc.cpp:84-95,107-122,134-136,211-218): the chain lives in the transformed
 // space; the target is evaluated at x = inv_transform(theta), the kick uses inv_jacobian * grad, the energy
@@ -324,15 +325,20 @@ __device__ MI_BOX_INLINE double box_log_jacobian_term(double v, int bt, double l
 // PCM (with DIAGM): PER-CHAIN diagonal masses (mi_chains.mass_diag: chain c runs with precond_mat = diag(mass[:, c])): the two tables are
 // [d][C] in global memory, this lane's entry of slice s at [(4 s + j) C + c], read where it is used (a chain's column is 2 KB at d = 128;
 // the 16 chains of a wave make 128-byte segments).
-template <int NT, int WPB, bool BOUNDED = false, bool DENSE_M = false, bool DIAGM = false, bool PCM = false>
+// FULL_TILE (the plain kernel only; the launcher picks it when d == 16 NT): d is the compile-time 16 NT, so every `dim < d` is true --
+// no momentum selects, no per-slice masks parked in SGPRs (and from there in VGPR lanes), no branch around each store of a row --
+// and the three per-draw memory streams (the accepted theta / P theta in the workspace, the kept row) are addressed as a wave-uniform
+// base in an SGPR pair + one 32-bit byte offset per lane + the instruction's immediate: no vector instruction per access but the access.
+template <int NT, int WPB, bool BOUNDED = false, bool DENSE_M = false, bool DIAGM = false, bool PCM = false, bool FULL_TILE = false>
 __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mfma_kernel(const HmcParams prm)
 {
     static_assert(!PCM || DIAGM, "per-chain masses ride the diagonal-mass variant");
     static_assert(!DENSE_M || BOUNDED, "the dense preconditioner rides the general variant");
     static_assert(!DIAGM || !BOUNDED, "DIAGM is the plain kernel with a diagonal mass; bounds take the general variant");
+    static_assert(!FULL_TILE || (!BOUNDED && !DIAGM), "the full-tile path is the plain kernel's");
     constexpr int NS = 4 * NT;
     extern __shared__ __attribute__((aligned(16))) double lds_P[];
-    stage_precision<NT>(prm.P, prm.d, lds_P);
+    stage_precision<NT>(prm.P, FULL_TILE ? 16u * NT : prm.d, lds_P);
     double* lds_lb = lds_P + NT * NS * 64;                 // [16*NT] each, BOUNDED only
     double* lds_ub = lds_lb + 16 * NT;
     double* lds_ms = lds_ub + 16 * NT;                     // diag of chol(M) and of inv(M): a DIAGONAL precond_mat
@@ -401,7 +407,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
         if constexpr (PCM) return pcm_at(prm.m_inv, s); else return mic[4 * s];
     };
     const uint64_t chain = prm.chain0 + cl;           // global chain id (Philox counter)
-    const uint32_t d = prm.d;
+    const uint32_t d = FULL_TILE ? 16u * NT : prm.d;
     const uint64_t C = prm.C;
     const double eps = prm.eps;
     const double* afrag = lds_P + lane;
@@ -426,8 +432,41 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
         asm volatile("" : "+v"(b));
         return b + (k & 7) * 64;
     };
-    auto th_mem = [&](int s) -> double* { return ws_group(s); };
-    auto w_mem = [&](int s) -> double* { return ws_group(NS + s); };
+    // FULL_TILE: the same words through a wave-uniform base (an SGPR pair; the wave index is taken from lane 0) + this lane's 8 bytes as a
+    // 32-bit offset (ws_lane: redefined opaquely at the top of every draw, so it is one live register and nothing to hoist or spill) + the
+    // slice stride inside a group of 8 as the immediate.  The group's 4 KB are added on the scalar side where the access is (opaque, like
+    // ws_group's base).  Spelled as address-space-1 pointers these are global_* accesses with an SGPR base, which FLAT ones cannot have,
+    // and they no longer count in lgkmcnt next to the LDS reads of the mat-vec.
+    typedef double __attribute__((address_space(1)))* gbl_dptr;
+    typedef char __attribute__((address_space(1)))* gbl_bptr;
+    [[maybe_unused]] const uintptr_t ws_u = (uintptr_t)prm.wsave
+        + ((size_t)blockIdx.x * WPB + (size_t)__builtin_amdgcn_readfirstlane(wave)) * ((size_t)3 * NS * 64 * sizeof(double));
+    [[maybe_unused]] uint32_t ws_lane = (uint32_t)lane * 8u;
+    [[maybe_unused]] auto ws_group_u = [&](int k) __attribute__((always_inline)) -> gbl_dptr {
+        uintptr_t b = ws_u + (uintptr_t)(k & ~7) * 512u;
+        asm volatile("" : "+s"(b));
+        return (gbl_dptr)((gbl_bptr)b + ws_lane + (k & 7) * 512);
+    };
+    // ... and the rows of prm.draws / prm.theta ([d][C]: slice s, this lane at [(4 s + j) C + chain]): the row base runs on the scalar side,
+    // 32 C bytes per slice; the lane's part (j C + chain) 8 is the 32-bit offset row_lane.  That needs 32 C < 2^32: the launcher picks this
+    // instantiation only then (a launch with more chains keeps the 64-bit per-lane addresses of the ragged instantiations).
+    [[maybe_unused]] uint32_t row_lane = (uint32_t)(lane_off * sizeof(double));
+    [[maybe_unused]] auto store_row_u = [&](double* row0) __attribute__((always_inline)) {
+        uintptr_t rb = (uintptr_t)row0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            asm volatile("" : "+s"(rb));                 // (a running base: as 32 loop-invariant row bases they were SGPR pairs spilled to VGPR lanes)
+            *(gbl_dptr)((gbl_bptr)rb + row_lane) = th[s];
+            rb += (uintptr_t)(4 * sizeof(double)) * C;
+        }
+    };
+    // The workspace accesses are in-order VMEM now, and the compiler counts them one by one (vmcnt) wherever a register they touch is used
+    // next -- on every static path, so in the leapfrog loop as well, 32 s_waitcnt per kick.  One full wait where the loads of a rejection
+    // have long returned (behind the momentum draw; in front of the kept row, where the FLAT loads made the first store wait as well)
+    // tells it that nothing is pending.  s_waitcnt vmcnt(0) with the other counters left alone:
+    [[maybe_unused]] auto vmem_settled = [&]() __attribute__((always_inline)) { __builtin_amdgcn_s_waitcnt(0x0F70); };
+    auto th_mem = [&](int s) __attribute__((always_inline)) { if constexpr (FULL_TILE) return ws_group_u(s); else return ws_group(s); };
+    auto w_mem = [&](int s) __attribute__((always_inline)) { if constexpr (FULL_TILE) return ws_group_u(NS + s); else return ws_group(NS + s); };
     [[maybe_unused]] auto z_mem = [&](int s) -> double* { return ws_wave + (size_t)(2 * NS + s) * 64; };   // fresh normals, staged
 
     // w = P * (theta or inv_transform(theta)); BOUNDED also refreshes xs and kw
@@ -541,6 +580,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
     const unsigned long long t_loop0 = clock64();
 #pragma unroll 1
     for (uint32_t draw = 0; draw < n_total; ++draw) {
+        if constexpr (FULL_TILE) asm volatile("" : "+v"(ws_lane), "+v"(row_lane));
 #if MI_HMC_RNG_STAGED
         // momentum ~ N(0, I): hmc.cpp:156-158.  The 16 Philox blocks + Box-Muller pairs run as a ROLLED loop that
         // stages the normals through the wave-local workspace (16 KiB, cache-resident): few live registers next
@@ -594,6 +634,7 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
             matvec_m2<NT>(afrag_l, zz, pm);
         }
 #endif
+        if constexpr (FULL_TILE) vmem_settled();
         const double prev_K = kinetic();                // hmc.cpp:160
 
         if constexpr (!BOUNDED) {
@@ -705,6 +746,21 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
                 }
                 gradient();
             }
+        } else if constexpr (FULL_TILE) {
+            // Two ifs, the stores first: behind `else` the compiler lays the loads out first, and every store of the accepting chains then waits,
+            // register by register, for the load the rejecting chains of the same wave have just issued into it
+            if (accept) {                               // prev_draw = new_draw (:192-194)
+                prev_U = prop_U;
+                if (live && !(prm.ablate & 8u)) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) { *th_mem(s) = th[s]; *w_mem(s) = w[s]; }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (!accept) {                              // keep prev_draw: reload it
+#pragma unroll
+                for (int s = 0; s < NS; ++s) { th[s] = *th_mem(s); w[s] = *w_mem(s); }
+            }
         } else
         if (accept) {                                   // prev_draw = new_draw (:192-194)
             prev_U = prop_U;
@@ -720,12 +776,15 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
             n_acc += accept ? 1u : 0u;
             if (prm.draws != nullptr && live && !(prm.ablate & 16u)) {
                 double* out = prm.draws + (size_t)(draw - prm.n_burnin) * d * C;
+                if constexpr (FULL_TILE) { vmem_settled(); store_row_u(out); }
+                else {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const uint32_t dim = 4 * s + j;
-                    // bounded runs store inv_transform(row) (the reference does it in the epilogue, :211-218)
-                    if (dim < d) (out + (size_t)(4 * s) * C)[lane_off] =
-                        (BOUNDED && slice_bounded(s)) ? box_inv_transform(th[s], lds_bt[dim], lds_lb[dim], lds_ub[dim]) : th[s];
+                    for (int s = 0; s < NS; ++s) {
+                        const uint32_t dim = 4 * s + j;
+                        // bounded runs store inv_transform(row) (the reference does it in the epilogue, :211-218)
+                        if (dim < d) (out + (size_t)(4 * s) * C)[lane_off] =
+                            (BOUNDED && slice_bounded(s)) ? box_inv_transform(th[s], lds_bt[dim], lds_lb[dim], lds_ub[dim]) : th[s];
+                    }
                 }
             }
         }
@@ -735,11 +794,14 @@ __global__ MI_NO_DS_MERGE __launch_bounds__(64 * WPB, WPB / 4) void hmc_gauss_mf
     if constexpr (!BOUNDED) replay = nf_seen && prm.nf_flag != nullptr;
     if (live && replay && j == 0) { prm.nf_flag[cl] = 1u; prm.nf_flag[C] = 1u; }
     if (live && !replay) {
+        if constexpr (FULL_TILE) store_row_u(prm.theta);   // (live: cld = cl)
+        else {
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const uint32_t dim = 4 * s + j;
-            if (dim < d) prm.theta[(size_t)dim * C + cl] =
-                (BOUNDED && slice_bounded(s)) ? box_inv_transform(th[s], lds_bt[dim], lds_lb[dim], lds_ub[dim]) : th[s];
+            for (int s = 0; s < NS; ++s) {
+                const uint32_t dim = 4 * s + j;
+                if (dim < d) prm.theta[(size_t)dim * C + cl] =
+                    (BOUNDED && slice_bounded(s)) ? box_inv_transform(th[s], lds_bt[dim], lds_lb[dim], lds_ub[dim]) : th[s];
+            }
         }
     }
     if (live && !replay && j == 0) {

@@ -7,12 +7,22 @@
 namespace mi {
 namespace {
 
+// d == 16 NT: the instantiation without the `dim < d` predicates (hmc_dense.hpp, FULL_TILE); the same name is reported for both.
+// Its rows are addressed with a 32-bit byte offset per lane, (3 C + chain) 8 at most, and a row stride of 32 C bytes on the scalar side:
+// from 2^27 chains on, the launch stays on the 64-bit per-lane addresses of the other instantiation.
+template <int NT, int WPB>
+auto plain_kernel(const HmcParams& prm)
+{
+    const bool full = prm.d == 16u * NT && prm.C < (1ull << 27);
+    return full ? hmc_gauss_mfma_kernel<NT, WPB, false, false, false, false, true> : hmc_gauss_mfma_kernel<NT, WPB>;
+}
+
 template <int NT>
 int plain(const HmcParams& prm, hipStream_t st)
 {
     constexpr int WPB = MI_HMC_WPB;
     const size_t lds = (size_t)NT * 4 * NT * 64 * sizeof(double);
-    auto kern = hmc_gauss_mfma_kernel<NT, WPB>;
+    auto kern = plain_kernel<NT, WPB>(prm);
     MI_LAUNCH_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned grid = (unsigned)((prm.C + 16 * WPB - 1) / (16 * WPB));
     note_kernel("hmc_gauss_mfma_kernel<%d, %d, false, false, false>", NT, WPB);
@@ -39,7 +49,7 @@ template <int NT>
 int plain4(const HmcParams& prm, hipStream_t st)
 {
     const size_t lds = (size_t)NT * 4 * NT * 64 * sizeof(double);
-    auto kern = hmc_gauss_mfma_kernel<NT, 4>;
+    auto kern = plain_kernel<NT, 4>(prm);
     MI_LAUNCH_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     note_kernel("hmc_gauss_mfma_kernel<%d, 4, false, false, false>", NT);
     hipLaunchKernelGGL(kern, dim3((unsigned)((prm.C + 63) / 64)), dim3(256), lds, st, prm);

@@ -8,6 +8,9 @@ import csv, glob, json, os, sys
 from collections import defaultdict
 
 root, cfg, cmd = sys.argv[1], int(sys.argv[2]), (sys.argv[3] if len(sys.argv) > 3 else "")
+# optional: the MFMA wave-instructions one launch of the dominant kernel executes (a static count: tools/valu_count.py x waves x draws).
+# SQ_INSTS_VALU counts them as vector instructions; with this the non-MFMA figure is derived next to it
+mfma_per_launch = float(sys.argv[4]) if len(sys.argv) > 4 else None
 out = {"command": cmd}
 
 # kernels whose global reads are 16-byte-per-lane streams (the guide's calibrated case)
@@ -60,6 +63,9 @@ if out["kernel_stats"]:
     v = per_launch("sq", "SQ_INSTS_VALU")
     if v is not None:
         d["valu_insts_per_launch"] = v
+        if mfma_per_launch is not None:      # SQ_INSTS_VALU includes the MFMAs (the static count reproduces it only with them)
+            d["mfma_insts_per_launch_static"] = mfma_per_launch
+            d["valu_non_mfma_insts_per_launch"] = v - mfma_per_launch
     wa = per_launch("sq", "SQ_WAIT_INST_ANY")
     if wa is not None:
         d["wait_inst_any_per_launch"] = wa
