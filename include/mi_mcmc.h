@@ -618,6 +618,45 @@ int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_ke
                              double* mean /* [d] host, may be NULL */, double* cov /* [d*d] host, row-major, may be NULL */,
                              void* stream);
 
+/* Nested R-hat of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: the convergence diagnostic of MANY SHORT chains (Margossian,
+ * Hoffman, Sountsov, Riou-Durand, Vehtari and Gelman, "Nested R-hat: assessing the convergence of Markov chain Monte Carlo when running many short
+ * chains", Bayesian Analysis 2024).  The C = n_chains chains are K = C / M superchains of M = chains_per_super chains each, whose members were
+ * started from one point: chain c is member m = c mod M of superchain k = c / M (integer division), so a superchain is a contiguous range of chains
+ * and survives mi_mcmc_shard_bounds sharding whenever M divides the shard.  The variance of the superchain means (between) is compared with the
+ * variance inside the superchains (within).  Defined for N = n_keep = 1: the chains' current state mi_chains.theta ([d][C]) is that case, no draws
+ * slab is needed.  between / K is the Monte Carlo variance of the pooled mean.  Outputs are HOST arrays, any of them may be NULL (not all):
+ * nrhat, mean, between, within, mcse_mean [d], super_mean [K][d].  Blocking.  Workspace: the stream's cached one (mi_mcmc_release_workspace).  No CPU
+ * path: no device is MI_ERR_NO_DEVICE.  MI_ERR_BAD_ARG, before any HIP call: a NULL slab; all six outputs NULL; d = 0 or d > 65 536; n_keep or
+ * n_chains 0 or beyond 32 bits; M = 0; C mod M != 0; K < 2; N = 1 together with M = 1 (within is identically 0).
+ * DEFINITION (fp64, every operation rounded once, nothing fused).  SUM64(u_0 .. u_{n-1}): r[s] = sum_j u[s + 64 j], j ascending from +0.0, for
+ * s = 0 .. 63 (a lane without elements stays +0.0); then r[s] = r[s] + r[s + h] for h = 32, 16, .., 1; the result is r[0].
+ *   per column (i, c):                    s = sum_t x[t][i][c], t ascending from +0.0;  a = s / N
+ *                                         N >= 2:  e = x - a,  p = e * e,  q = sum_t p ascending from +0.0,  v = q / (N - 1);   N = 1:  v = +0.0
+ *   per (i, k), the members m ascending:  A_k = SUM64(a) / M
+ *                                         M >= 2:  Bt_k = SUM64((a - A_k) * (a - A_k)) / (M - 1);   M = 1:  Bt_k = +0.0
+ *                                         Wt_k = SUM64(v) / M;   w_k = Bt_k + Wt_k
+ *   per dimension i, k ascending:         mean = SUM64(A) / K;   between = SUM64((A_k - mean) * (A_k - mean)) / (K - 1);   within = SUM64(w) / K
+ *   on the host (sqrt correctly rounded): nrhat = sqrt(1.0 + between / within);   mcse_mean = sqrt(between / K);   super_mean[k][i] = A_k
+ * The bits of every output depend on (slab, N, d, C, M) alone -- not on which outputs are NULL, on `mem`, the grid, timing or atomics (there are
+ * none).  Non-finite samples propagate by the IEEE rules inside their own dimension and nowhere else; a constant dimension gives whatever 0 / 0 or
+ * x / 0 gives; nothing is clamped or flagged.  For stationary superchains with independent members between / within is about
+ * 1 / (M * ESS of one chain's N draws): a threshold on nrhat is a statement about M, and the choice stays with the caller.  The numpy statement is
+ * mcmc_amd/nested_rhat.py. */
+int mi_mcmc_draw_stats_nested(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                              uint64_t chains_per_super /* M */,
+                              double* nrhat /*[d]*/, double* mean /*[d]*/, double* between /*[d]*/, double* within /*[d]*/,
+                              double* mcse_mean /*[d]*/, double* super_mean /*[K][d]*/, void* stream);
+/* The rank-normalised form, composed of mi_mcmc_draws_rank_transform (below) and the reducer above (outputs: HOST arrays [d], any may be NULL, not all):
+ *   nrhat_bulk   nrhat of the MI_RANK_NORMAL slab with flags 0
+ *   nrhat_tail   nrhat of the MI_RANK_NORMAL slab with MI_RANK_FOLD
+ *   nrhat        the larger of the two, NaN if either is NaN
+ * There is no MI_RANK_SPLIT: the diagnostic is defined at n_keep = 1.  Argument checks: those of mi_mcmc_draw_stats_nested (all three outputs NULL),
+ * and n_keep * n_chains below 2^32 as the transform asks. */
+int mi_mcmc_draw_stats_nested_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains,
+                                     uint64_t chains_per_super,
+                                     double* nrhat, double* nrhat_bulk, double* nrhat_tail, /* host [d], any may be NULL, not all */
+                                     void* stream);
+
 /* Exact pooled order statistics and quantiles of a slab [n_keep][d][C] (in `mem`; a host slab is staged), on the device: the samples of
  * dimension i are the K = n_keep * C values x[t][i][c], pooled over draws and chains.  Outputs are HOST arrays.  Blocking.  Workspace: the
  * stream's cached one (mi_mcmc_release_workspace).  No CPU path: no device is MI_ERR_NO_DEVICE.  MI_ERR_BAD_ARG, before any HIP call: a NULL

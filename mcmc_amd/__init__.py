@@ -749,6 +749,36 @@ def _slab_shape(draws, n_keep, d, n_chains, mem):
     return draws, int(n_keep), int(d), int(n_chains)
 
 
+def draw_stats_nested(draws, chains_per_super, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_nrhat=True, want_mean=True,
+                      want_between=True, want_within=True, want_mcse_mean=True, want_super_mean=True):
+    """mi_mcmc_draw_stats_nested: the nested R-hat of a slab [n_keep, d, C] whose C chains are K = C // chains_per_super superchains of chains_per_super
+    consecutive chains started from one point (Margossian et al. 2024; numpy array -- a 2-D [d, C] array is the case n_keep = 1, the chains' state --,
+    or a device tensor / pointer with mem=MEM_DEVICE and explicit shape).  Returns a dict of nrhat, mean, between, within, mcse_mean [d] and
+    super_mean [K, d]; an output that is not wanted is None.  mcmc_amd.nested_rhat.nested_ref states the result bit for bit."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    M = int(chains_per_super)
+    K = n_chains // M if M > 0 else 0
+    want = dict(nrhat=want_nrhat, mean=want_mean, between=want_between, within=want_within, mcse_mean=want_mcse_mean)
+    res = {k: (np.zeros(d) if w else None) for k, w in want.items()}
+    res["super_mean"] = np.zeros((K, d)) if want_super_mean else None
+    _check(lib().mi_mcmc_draw_stats_nested(_ptr(draws), mem, n_keep, d, n_chains, M, *[_ptr(res[k]) for k in
+                                           ("nrhat", "mean", "between", "within", "mcse_mean", "super_mean")], stream or 0))
+    return res
+
+
+def draw_stats_nested_ranked(draws, chains_per_super, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None, want_nrhat=True, want_nrhat_bulk=True,
+                             want_nrhat_tail=True):
+    """mi_mcmc_draw_stats_nested_ranked: the nested R-hat of the normal scores of x (nrhat_bulk) and of |x - median| (nrhat_tail), and the larger of
+    the two (nrhat), per dimension of a slab as draw_stats_nested takes it; no split, so n_keep = 1 works.  Returns a dict of [d] arrays; an output that
+    is not wanted is None.  mcmc_amd.nested_rhat.nested_ranked_ref states the result bit for bit."""
+    draws, n_keep, d, n_chains = _slab_shape(draws, n_keep, d, n_chains, mem)
+    want = dict(nrhat=want_nrhat, nrhat_bulk=want_nrhat_bulk, nrhat_tail=want_nrhat_tail)
+    res = {k: (np.zeros(d) if w else None) for k, w in want.items()}
+    _check(lib().mi_mcmc_draw_stats_nested_ranked(_ptr(draws), mem, n_keep, d, n_chains, int(chains_per_super),
+                                                  *[_ptr(res[k]) for k in ("nrhat", "nrhat_bulk", "nrhat_tail")], stream or 0))
+    return res
+
+
 def draws_order_stats(draws, ranks, n_keep=None, d=None, n_chains=None, mem=MEM_HOST, stream=None):
     """mi_mcmc_draws_order_stats: out[a, i] = the value with the ranks[a]-th smallest key (0-based) among the n_keep * C pooled samples of
     dimension i of a slab [n_keep, d, C] (numpy array, or a device tensor / pointer with mem=MEM_DEVICE and explicit shape) -- exact; the order

@@ -118,6 +118,8 @@ PROTOTYPES = {
     "mi_mcmc_draw_stats": (_i, [_p, _i32, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
     "mi_mcmc_draw_stats_lags": (_i, [_p, _i32, _u64, _u64, _u64, _u32, _p, _p, _p, _p, _p, _p]),
     "mi_mcmc_draws_covariance": (_i, [_p, _i32, _u64, _u64, _u64, _p, _p, _p]),
+    "mi_mcmc_draw_stats_nested": (_i, [_p, _i32, _u64, _u64, _u64, _u64, _p, _p, _p, _p, _p, _p, _p]),
+    "mi_mcmc_draw_stats_nested_ranked": (_i, [_p, _i32, _u64, _u64, _u64, _u64, _p, _p, _p, _p]),
     "mi_mcmc_draws_order_stats": (_i, [_p, _i32, _u64, _u64, _u64, _p, _u32, _p, _p]),
     "mi_mcmc_draws_quantiles": (_i, [_p, _i32, _u64, _u64, _u64, _p, _u32, _p, _p]),
     "mi_mcmc_draws_rank_transform": (_i, [_p, _i32, _u64, _u64, _u64, _i32, _u32, _p, _p]),

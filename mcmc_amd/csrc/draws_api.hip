@@ -1,5 +1,5 @@
 // draws_api.hip -- the C ABI's reducers over a draws slab [n_keep][d][C] (include/mi_mcmc.h): host drivers around the kernels of
-// draws_cov.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip, draws_bridge.hip and draws_predict.hip.  Validation first (it needs no device), then the device probe, then the slab
+// draws_cov.hip, draws_nested.hip, draws_select.hip, draws_rank.hip, draws_logk.hip, draws_waic.hip, draws_psis.hip, draws_loglik.hip, draws_bridge.hip and draws_predict.hip.  Validation first (it needs no device), then the device probe, then the slab
 // staged on the device where the caller holds it on the host, the workspace of the stream (workspace.hpp) and the launches.  No sampler lives here.
 // mi_mcmc_draw_stats and mi_mcmc_draw_stats_lags are draw_stats.hip; the ranked drivers below reach them through the C ABI.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "workspace.hpp"
 #include "det_math.hpp"
 #include "draws_cov.hpp"
+#include "draws_nested.hpp"
 #include "draws_select.hpp"
 #include "draws_rank.hpp"
 #include "draws_logk.hpp"
@@ -95,6 +96,63 @@ int mi_mcmc_draws_covariance(const double* draws_kdc, int32_t mem, uint64_t n_ke
     if (mean) HIP_TRY(hipMemcpyAsync(mean, ws.as<double>() + plan.o_mean, d * 8, hipMemcpyDeviceToHost, st));
     if (cov) HIP_TRY(hipMemcpyAsync(cov, ws.as<double>() + plan.o_cov, d * d * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));                   // blocking: the outputs are the caller's host arrays, the staged slab and the workspace are ours
+    return MI_OK;
+}
+
+// The checks that mi_mcmc_draw_stats_nested and mi_mcmc_draw_stats_nested_ranked share: they need no device
+static int nested_check(const char* who, const double* draws_kdc, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t M, bool any_output, const char* n_outputs)
+{
+    if (!draws_kdc) return fail(MI_ERR_BAD_ARG, "%s: null slab", who);
+    if (!any_output) return fail(MI_ERR_BAD_ARG, "%s: all %s outputs are NULL, nothing is asked for", who, n_outputs);
+    if (d == 0) return fail(MI_ERR_BAD_ARG, "%s: d must be positive", who);
+    if (d > mi::dnest::NESTED_MAX_D) return fail(MI_ERR_BAD_ARG, "%s: d = %llu is beyond %llu", who, (unsigned long long)d, (unsigned long long)mi::dnest::NESTED_MAX_D);
+    if (n_keep == 0 || n_chains == 0) return fail(MI_ERR_BAD_ARG, "%s: n_keep and n_chains must be positive", who);
+    if (n_keep > 0xffffffffULL || n_chains > 0xffffffffULL) return fail(MI_ERR_BAD_ARG, "%s: n_keep / n_chains do not fit 32 bits", who);
+    if (M == 0) return fail(MI_ERR_BAD_ARG, "%s: chains_per_super must be positive", who);
+    if (n_chains % M != 0)
+        return fail(MI_ERR_BAD_ARG, "%s: n_chains = %llu is not a multiple of chains_per_super = %llu", who, (unsigned long long)n_chains, (unsigned long long)M);
+    if (n_chains / M < 2) return fail(MI_ERR_BAD_ARG, "%s: K = n_chains / chains_per_super = %llu, at least 2 superchains are needed", who, (unsigned long long)(n_chains / M));
+    if (n_keep == 1 && M == 1) return fail(MI_ERR_BAD_ARG, "%s: n_keep = 1 with chains_per_super = 1, the within variance is identically 0", who);
+    return MI_OK;
+}
+
+// nrhat and mcse_mean from between and within, on the host (the arithmetic: include/mi_mcmc.h)
+static double nested_rhat(double between, double within)
+{
+    const double ratio = between / within;
+    const double u = 1.0 + ratio;
+    return std::sqrt(u);
+}
+
+// Nested R-hat of a slab [n_keep][d][C] whose chains are K = C / M superchains of M consecutive chains (draws_nested.hip; the arithmetic: include/mi_mcmc.h)
+int mi_mcmc_draw_stats_nested(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t chains_per_super, double* nrhat,
+                              double* mean, double* between, double* within, double* mcse_mean, double* super_mean, void* stream)
+{
+    int rc = nested_check("draw_stats_nested", draws_kdc, n_keep, d, n_chains, chains_per_super, nrhat || mean || between || within || mcse_mean || super_mean, "six");
+    if (rc) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DevBuf staged;
+    const double* x = nullptr;
+    if ((rc = stage_slab(draws_kdc, mem, n_keep, d, n_chains, st, staged, &x))) return rc;
+    const mi::dnest::NestedPlan plan = mi::dnest::nested_plan(n_keep, d, n_chains, chains_per_super, super_mean != nullptr);
+    WsLease ws;
+    rc = ws_get(st, plan.bytes, ws);
+    if (rc) return rc;
+    HIP_TRY((hipError_t)mi::dnest::nested_run(x, plan, ws.p, super_mean != nullptr, st));
+    std::vector<double> out(3 * d);
+    HIP_TRY(hipMemcpyAsync(out.data(), ws.as<double>() + plan.o_out, 3 * d * 8, hipMemcpyDeviceToHost, st));
+    if (super_mean) HIP_TRY(hipMemcpyAsync(super_mean, ws.as<double>() + plan.o_super, plan.K * d * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                   // blocking: the outputs are the caller's host arrays, the staged slab and the workspace are ours
+    const double Kd = (double)plan.K;
+    for (uint64_t i = 0; i < d; ++i) {
+        const double b = out[d + i], w = out[2 * d + i];
+        if (mean) mean[i] = out[i];
+        if (between) between[i] = b;
+        if (within) within[i] = w;
+        if (nrhat) nrhat[i] = nested_rhat(b, w);
+        if (mcse_mean) mcse_mean[i] = std::sqrt(b / Kd);
+    }
     return MI_OK;
 }
 
@@ -349,6 +407,67 @@ int mi_mcmc_draw_stats_ranked_lags(const double* draws_kdc, int32_t mem, uint64_
                                  [&](const double* slab, uint64_t h, uint64_t nd, uint64_t C2, double* r, double* e, uint8_t* en) {
                                      return mi_mcmc_draw_stats_lags(slab, MI_MEM_DEVICE, h, nd, C2, max_lag, nullptr, nullptr, r, e, en, stream);
                                  });
+}
+
+// Rank-normalised nested R-hat: the normal scores of x and of |x - med| (draws_rank.hip, no split: the diagnostic is defined at n_keep = 1) composed
+// group by group of dimensions into a slab [n_keep][nd][C], and draws_nested.hip's reducer over it.  Every step is per dimension, so the grouping
+// decides memory only.
+int mi_mcmc_draw_stats_nested_ranked(const double* draws_kdc, int32_t mem, uint64_t n_keep, uint64_t d, uint64_t n_chains, uint64_t chains_per_super,
+                                     double* nrhat, double* nrhat_bulk, double* nrhat_tail, void* stream)
+{
+    const char* who = "draw_stats_nested_ranked";
+    int rc = nested_check(who, draws_kdc, n_keep, d, n_chains, chains_per_super, nrhat || nrhat_bulk || nrhat_tail, "three");
+    if (rc) return rc;
+    if ((rc = rank_check(who, draws_kdc, n_keep, d, n_chains, 0))) return rc;
+    if ((rc = need_device())) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const mi::drank::RankPlan plan = mi::drank::rank_plan(n_keep, d, n_chains, 0, true, g_rank_ws_bytes.load(std::memory_order_relaxed));
+    const mi::dnest::NestedPlan nplan = mi::dnest::nested_plan(n_keep, plan.dims_per_group, n_chains, chains_per_super, false);
+    DevBuf staged;
+    const double* x = nullptr;
+    if ((rc = stage_slab(draws_kdc, mem, n_keep, d, n_chains, st, staged, &x))) return rc;
+    const size_t o_nested = (plan.bytes + 255) & ~(size_t)255;      // the reducer's workspace behind the rank transform's
+    WsLease ws;
+    rc = ws_get(st, o_nested + nplan.bytes, ws);
+    if (rc) return rc;
+    char* W = ws.as<char>();
+    double* slab = reinterpret_cast<double*>(W + plan.o_slab);
+    const bool want_bulk = nrhat || nrhat_bulk, want_fold = nrhat || nrhat_tail;
+    std::vector<double> bw_bulk(3 * d), bw_fold(3 * d), os, q;      // per group [3][nd] at 3 * dim0: mean, between, within of the composed slab
+    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
+        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
+        const mi::dnest::NestedPlan gp = mi::dnest::nested_plan(n_keep, nd, n_chains, chains_per_super, false);      // within nplan.bytes: nd <= dims_per_group
+        const uint64_t* sorted = nullptr;
+        HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, false, W, st, &sorted));
+        if (want_bulk) {
+            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, false, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
+            HIP_TRY((hipError_t)mi::dnest::nested_run(slab, gp, W + o_nested, false, st));
+            HIP_TRY(hipMemcpyAsync(bw_bulk.data() + 3 * dim0, reinterpret_cast<double*>(W + o_nested) + gp.o_out, 3 * nd * 8, hipMemcpyDeviceToHost, st));
+        }
+        if (want_fold) {                                 // the medians out of the un-folded image, then the sort of |x - med|
+            rc = rank_group_quantiles(plan, dim0, nd, sorted, false, W, st, os, q, nullptr);
+            if (rc) return rc;
+            HIP_TRY((hipError_t)mi::drank::rank_sort_group(x, plan, dim0, nd, true, W, st, &sorted));
+            HIP_TRY((hipError_t)mi::drank::rank_lookup_group(x, plan, dim0, nd, true, MI_RANK_NORMAL, sorted, W, slab, nd, 0, st));
+            HIP_TRY((hipError_t)mi::dnest::nested_run(slab, gp, W + o_nested, false, st));
+            HIP_TRY(hipMemcpyAsync(bw_fold.data() + 3 * dim0, reinterpret_cast<double*>(W + o_nested) + gp.o_out, 3 * nd * 8, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    const double nan = std::nan("");
+    for (uint64_t dim0 = 0; dim0 < d; dim0 += plan.dims_per_group) {
+        const uint64_t nd = std::min<uint64_t>(plan.dims_per_group, d - dim0);
+        for (uint64_t j = 0; j < nd; ++j) {
+            const double* gb = bw_bulk.data() + 3 * dim0;
+            const double* gf = bw_fold.data() + 3 * dim0;
+            const double rb = want_bulk ? nested_rhat(gb[nd + j], gb[2 * nd + j]) : 0.0;
+            const double rt = want_fold ? nested_rhat(gf[nd + j], gf[2 * nd + j]) : 0.0;
+            if (nrhat_bulk) nrhat_bulk[dim0 + j] = rb;
+            if (nrhat_tail) nrhat_tail[dim0 + j] = rt;
+            if (nrhat) nrhat[dim0 + j] = (rb != rb || rt != rt) ? nan : (rb > rt ? rb : rt);
+        }
+    }
+    return MI_OK;
 }
 
 int mi_mcmc_norm_ppf(const double* p, uint64_t n, double* z)
